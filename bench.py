@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- 512x512 frames/sec of the Feature2FaceGenerator forward on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (frames/s, ms_per_step); --dump-outputs DIR
+then also writes the frames the last timed step rendered to DIR/*.npy (fp32, seeded inputs: two builds compare output for
+output).  --full adds everything else the benchmark measures: the shader clock, the per-class roofline (--layers), the CPU
+baseline and the `extra` block (other configurations, the MIOpen comparator, side paths; configs[3] when N > 1).
 
 N > 1: either launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or started bare,
 in which case this process becomes the launcher: it starts N rank processes of itself (one per GPU, backend nccl = RCCL), waits
@@ -11,7 +16,7 @@ ranks share devices: control-flow tests on a 1-GPU box only).
 A step = one pass of the hot path (lspf2f_forward) over one batch of synthetic frames per GPU,
 inputs already resident in HBM.  Default workload = BASELINE.json configs[1]: May ('large'),
 batch 1, fp32.  Weak scaling: per-GPU work is fixed, value = frames all ranks rendered / time.
-Rank 0 prints ONE JSON line (+ roofline and cpu_baseline objects).
+Rank 0 prints ONE JSON line (+ roofline and cpu_baseline objects with --full).
 """
 import argparse
 import json
@@ -106,10 +111,18 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f16"],
                     help="f32 = the parity configuration (default); bf16 = BASELINE.json configs[2] storage path; f16 = the reference's opt.fp16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--layers", default=None, help="write the per-layer timing table to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: shader clock, per-class roofline, CPU baseline, extra configurations and side paths")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frames the last step rendered to DIR/out.npy (fp32, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra block; in every run: plan the handle for --batch frames only")
+    ap.add_argument("--layers", default=None, help="with --full: write the per-layer timing table to this file")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.layers and not a.full:
+        ap.error("--layers is part of the roofline: it needs --full")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a.gpus)          # does not return
 
@@ -161,10 +174,12 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, rank, world)
     # The shader clock the chip holds under this load, measured OUTSIDE the timed region (rank 0): the same loop once more while one wave on a side
     # stream counts shader cycles against the constant 100 MHz counter (lspf2f_clock_probe) for 80 % of the time the timed loop just took.
     clock_ghz = None
-    if rank == 0:
+    if a.full and rank == 0:
         probe_stream = torch.cuda.Stream(device=dev)
         probe_buf = torch.zeros(2, dtype=torch.int64, device=dev)
         torch.cuda.synchronize()
@@ -184,7 +199,7 @@ def main():
     # the batch, distinct feature maps per rank and frame (seed 99 + 1000*rank + i), same barrier / MAX-over-ranks protocol.
     # Efficiency = this aggregate / (N x the 1-GPU `extra.batch8_frames_per_s` of the N = 1 run) -- computed by the reader.
     config3 = None
-    if world > 1 and not a.no_extra:
+    if a.full and world > 1 and not a.no_extra:
         f8 = torch.from_numpy(synth.make_inputs(8, a.size, seed=99 + 1000 * rank, cand_batch=1)[0]).to(dev)
         o8 = torch.empty((8, 3, a.size, a.size), device=dev)
         for _ in range(3):
@@ -213,6 +228,23 @@ def main():
     ms_per_step = 1e3 * elapsed / a.steps
     fps = world * B * a.steps / elapsed
     flops_step = topo.flops_per_frame() * B
+    line = {
+        "metric": "512x512 frames/sec (Feature2FaceGenerator fwd)", "value": round(fps, 3), "unit": "frames/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
+        "config": {"workload": "%s generator (%s), batch %d per GPU, %dx%d, %s, synthetic weights+inputs"
+                               % (a.variant, "May" if a.variant == "large" else "Obama1", B, a.size, a.size,
+                                  {"f32": "fp32", "bf16": "bf16 storage / fp32 accumulate (parity-unpinned: tolerance declared in tests)",
+                                   "f16": "fp16 storage / fp32 accumulate (the reference's opt.fp16; pinned on the autocast oracle in tests)"}[a.dtype]),
+                   "global_batch": world * B, "parallelism": "dp%d (frames sharded, one RCCL weight broadcast)" % world,
+                   "gflop_per_frame": round(topo.flops_per_frame() / 1e9, 2)},
+    }
+    if world > 1:
+        line["config"]["collective_backend"] = dist.get_backend()
+        line["config"]["ranks_in_group"] = dist.get_world_size()
+    if not a.full:
+        print_line(line, world)
+        return
 
     # ---- roofline: live, per kernel class.  ROCm 7.2 cannot time events recorded by graph nodes, so a kernel cannot be bracketed inside
     # the replay of the whole forward; instead the launches of ONE class (in network order, reading what the last forward left in the
@@ -442,29 +474,35 @@ def main():
               "max_abs_vs_fp32_oracle": max(vo.get("max_abs_per_frame") or [float("nan")]), "mean_abs_vs_fp32_oracle": max(vo.get("mean_abs_per_frame") or [float("nan")]),
               "declared_tolerance": "1e-2 max / 2.5e-3 mean per frame (parity-unpinned: the reference has no bf16 path)"}
 
-    line = {
-        "metric": "512x512 frames/sec (Feature2FaceGenerator fwd)", "value": round(fps, 3), "unit": "frames/s",
-        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
-        "config": {"workload": "%s generator (%s), batch %d per GPU, %dx%d, %s, synthetic weights+inputs"
-                               % (a.variant, "May" if a.variant == "large" else "Obama1", B, a.size, a.size,
-                                  {"f32": "fp32", "bf16": "bf16 storage / fp32 accumulate (parity-unpinned: tolerance declared in tests)",
-                                   "f16": "fp16 storage / fp32 accumulate (the reference's opt.fp16; pinned on the autocast oracle in tests)"}[a.dtype]),
-                   "global_batch": world * B, "parallelism": "dp%d (frames sharded, one RCCL weight broadcast)" % world,
-                   "gflop_per_frame": round(topo.flops_per_frame() / 1e9, 2)},
-        "roofline": roofline, "cpu_baseline": cpu_baseline,
-    }
+    line.update(roofline=roofline, cpu_baseline=cpu_baseline)
     if config3:
         extra = dict(extra or {}, config3_batch8_per_gpu=config3)
-    if world > 1:
-        line["config"]["collective_backend"] = dist.get_backend()
-        line["config"]["ranks_in_group"] = dist.get_world_size()
     if extra:
         line["extra"] = extra
+    print_line(line, world)
+
+
+def print_line(line, world):
+    """rank 0: the one JSON line, then out of the group"""
     print(json.dumps(line))
     sys.stdout.flush()
     if world > 1:
         leave_group()
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, out, rank, world):
+    """--dump-outputs: what lspf2f_forward handed back in the last timed step, the fp32 frames [B, 3, H, W], as DIR/out.npy
+    (DIR/out_rank<r>.npy from every rank when N > 1).  Beyond 64 MB in all, the file holds a fixed sample instead: the flattened
+    frames at the distinct ascending indices of 0-seeded uniform draws, the same for every run of the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    arr = out.detach().float().cpu().numpy()
+    cap = DUMP_BYTES // (4 * world)
+    if arr.size > cap:
+        arr = arr.reshape(-1)[np.unique(np.random.default_rng(0).integers(0, arr.size, cap))]
+    np.save(os.path.join(dirname, "out.npy" if world == 1 else "out_rank%d.npy" % rank), np.ascontiguousarray(arr, np.float32))
 
 
 def torch_rocm_extra(dev, sd, topo, feat_np, cand_np, a):

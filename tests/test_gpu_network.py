@@ -468,7 +468,7 @@ def test_bench_runs_with_two_ranks_on_one_gpu(tmp_path):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    LSP_DIST_BACKEND="gloo")
         procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                                       "--variant", "normal", "--no-cpu-baseline"],
+                                       "--variant", "normal", "--no-cpu-baseline", "--full"],
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=300) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-600:] for o in outs]
@@ -496,7 +496,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["LSP_DIST_BACKEND"] = "gloo"
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                        "--variant", "normal", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--variant", "normal", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-800:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -510,3 +510,28 @@ def test_bench_launches_its_own_ranks(tmp_path):
     q = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(torch.cuda.device_count() + 1), "--steps", "1", "--warmup", "0",
                         "--no-cpu-baseline", "--no-extra"], env=env, capture_output=True, text=True, timeout=300)
     assert q.returncode != 0 and "device(s) visible" in q.stderr and not [ln for ln in q.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run is the headline alone: the timed steps it was asked for and ms_per_step, no roofline / cpu_baseline /
+    extra (those need --full).  --dump-outputs writes the frames of the last timed step: bench.py's seeded weights and inputs are
+    those of the normal_512 golden, so the file must hold the reference's output."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--variant", "normal",
+                        "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-800:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    assert not {"roofline", "cpu_baseline", "extra"} & set(d)
+    assert os.listdir(str(tmp_path / "dump")) == ["out.npy"]
+    got = np.load(str(tmp_path / "dump" / "out.npy"))
+    meta, arrays, topo, sd, feat, cand = golden_problem("normal_512")
+    assert got.dtype == np.float32 and got.shape == arrays["out"].shape
+    assert np.abs(got - arrays["out"]).max() <= TIGHT

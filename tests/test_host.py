@@ -598,3 +598,23 @@ def test_planner_choices_of_the_small_levels_per_batch():
     # one-frame handles carry no full-K tiles for the 4x4 / 2x2 levels (the blob holds only what the batch range reads)
     assert Engine("large", max_batch=1).packed_bytes() < Engine("large", max_batch=2).packed_bytes() < e.packed_bytes()
     e.close()
+
+
+# ---- bench.py --dump-outputs -----------------------------------------------------------------
+def test_bench_dump_outputs_writes_the_frames_or_a_fixed_sample(tmp_path):
+    """The frames go out whole up to 64 MB; beyond that as the same seeded, ascending sample on every call (two builds compare
+    file for file), split across the ranks' files."""
+    import bench
+    small = torch.linspace(-1, 1, 2 * 3 * 8 * 8).reshape(2, 3, 8, 8)
+    bench.dump_outputs(str(tmp_path / "s"), small, 0, 1)
+    assert os.listdir(str(tmp_path / "s")) == ["out.npy"]
+    got = np.load(str(tmp_path / "s" / "out.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    big = torch.arange(20 * 1024 * 1024, dtype=torch.float32).reshape(5, 4, 1024, 1024)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big, 0, 1)
+    a, b = (np.load(str(tmp_path / d / "out.npy")) for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.nbytes <= 64 << 20 and a.size > (8 << 20)
+    assert np.array_equal(a, b) and (np.diff(a) >= 0).all()
+    bench.dump_outputs(str(tmp_path / "r"), big, 1, 2)
+    assert os.listdir(str(tmp_path / "r")) == ["out_rank1.npy"] and np.load(str(tmp_path / "r" / "out_rank1.npy")).nbytes <= 32 << 20

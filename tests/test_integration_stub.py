@@ -1,8 +1,10 @@
 """The reference-side binding of INTEGRATION.md section 2 (integration/lsp_hip_generator.py), executed:
-  * here in the build container against the REFERENCE's own Feature2FaceModel / Feature2Face_G (CPU: construction, every
-    state-dict key through lspf2f_set_tensor, host packing -- the blob must equal the one this package packs);
-  * on the GPU box (no reference there) against a stand-in module with the reference's key names: forward vs the golden."""
+  * on the host against a module with the reference Feature2Face_G's state-dict keys and shapes, frozen from the reference in
+    tests/golden/keys_<variant>.json (every state-dict key through lspf2f_set_tensor, host packing -- the blob must equal
+    the one this package packs);
+  * on the GPU against a stand-in module with the reference's key names: forward vs the golden."""
 import argparse
+import json
 import os
 import sys
 import types
@@ -11,9 +13,8 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, golden_problem
+from conftest import GOLDEN, ROOT, golden_problem
 
-REF = "/root/reference"
 sys.path.insert(0, os.path.join(ROOT, "integration"))
 
 
@@ -21,39 +22,31 @@ def _lib():
     return os.path.join(ROOT, "livespeechportraits_amd", "liblspf2f.so")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs /root/reference (build container only)")
 @pytest.mark.parametrize("variant", ["normal", "large"])
-def test_stub_binds_the_reference_model_on_the_host(variant, tmp_path):
-    import subprocess
-    # the reference's `models` / `util` packages shadow nothing of ours, but keep them out of this interpreter anyway
-    code = r"""
-import sys, types, argparse, torch, numpy as np
-for name in ("torchvision", "torchvision.models", "cv2"):
-    sys.modules.setdefault(name, types.ModuleType(name))
-sys.path.insert(0, %(ref)r); sys.path.insert(0, %(integ)r); sys.path.insert(0, %(root)r)
-from models import create_model                                   # the REFERENCE's factory
-import lsp_hip_generator as G
-opt = argparse.Namespace(model="feature2face", gpu_ids=[], isTrain=False, size=%(variant)r, ngf=64, n_downsample_G=8, fp16=0,
-                         checkpoints_dir=%(tmp)r, name="t", load_epoch="none", verbose=False, task="Feature2Face", dataset_mode="face")
-torch.manual_seed(3)
-model = create_model(opt)                                         # reference Feature2FaceModel, init_weights'd
-model.eval()
-net = model.Feature2Face_G
-gen = G.HipGenerator(net, opt, size=512, max_batch=2, library=%(lib)r)      # host half of install(): every key accepted, packed
-from livespeechportraits_amd.engine import Engine
-e = Engine(%(variant)r, size=512, max_batch=2)
-e.load_state_dict({k: v for k, v in net.state_dict().items()})
-assert torch.equal(e.pack(), gen.blob), "stub and package pack different blobs"
-nkeys = len([k for k in net.state_dict() if not k.endswith("num_batches_tracked")])
-print("OK", type(model).__module__, nkeys, gen.blob.numel())
-"""
-    p = subprocess.run([sys.executable, "-c", code % {"ref": REF, "integ": os.path.join(ROOT, "integration"), "root": ROOT,
-                                                      "variant": variant, "tmp": str(tmp_path), "lib": _lib()}],
-                       capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    last = p.stdout.strip().splitlines()[-1].split()
-    assert last[0] == "OK" and last[1] == "models.feature2face_model"          # it really was the reference's class
-    assert int(last[2]) == (368 if variant == "large" else 218)
+def test_stub_binds_the_reference_model_on_the_host(variant):
+    """The host half of install() on a module whose state dict has exactly the reference Feature2Face_G's keys, order and
+    shapes (tests/golden/keys_<variant>.json, dumped from the reference model by oracle/make_golden.py, num_batches_tracked
+    included): every key is accepted through lspf2f_set_tensor and the stub packs the blob this package packs."""
+    import collections
+    import lsp_hip_generator as G
+    from livespeechportraits_amd import synth
+    from livespeechportraits_amd.engine import Engine
+    with open(os.path.join(GOLDEN, "keys_%s.json" % variant)) as f:
+        ref = json.load(f, object_pairs_hook=collections.OrderedDict)
+    sd = synth.make_state_dict(types.SimpleNamespace(tensors=ref), 3)          # values made from the dump's keys and shapes alone
+
+    class RefKeyed:                               # the reference module's state_dict(): its keys, in its order, at its shapes
+        def state_dict(self):
+            return collections.OrderedDict((k, torch.as_tensor(sd[k])) for k in ref)
+    net = RefKeyed()
+    opt = argparse.Namespace(size=variant, ngf=64, n_downsample_G=8, fp16=0)
+    gen = G.HipGenerator(net, opt, size=512, max_batch=2, library=_lib())      # host half of install(): every key accepted, packed
+    e = Engine(variant, size=512, max_batch=2)
+    e.load_state_dict(dict(net.state_dict()))
+    assert torch.equal(e.pack(), gen.blob), "stub and package pack different blobs"
+    # guards the fixture, not the stub: the dump is the whole reference generator, with the tensor counts the reference model itself had
+    nkeys = len([k for k in ref if not k.endswith("num_batches_tracked")])
+    assert nkeys == (368 if variant == "large" else 218)
 
 
 @pytest.mark.gpu

@@ -1,10 +1,10 @@
 #!/bin/bash
 # Run on the GPU box: the bench line of every configuration quoted in README.md / DESIGN.md, one JSON file each under gpurun_out/<tag>/.
 R=$GRAFT_REPO_ROOT; TAG=${1:-r03_bench_all}; OUT=$R/gpurun_out/$TAG; mkdir -p "$OUT"; cd "$R"
-python bench.py > "$OUT/default.json" 2> "$OUT/default.err"
+python bench.py --full > "$OUT/default.json" 2> "$OUT/default.err"
 for cfg in "large 8 f32" "normal 1 f32" "normal 8 f32" "normal 8 bf16" "large 8 bf16" "large 1 bf16" "normal 1 bf16"; do
   set -- $cfg
-  python bench.py --variant $1 --batch $2 --dtype $3 --no-cpu-baseline --no-extra > "$OUT/$1_b$2_$3.json" 2> "$OUT/$1_b$2_$3.err"
+  python bench.py --full --variant $1 --batch $2 --dtype $3 --no-cpu-baseline --no-extra > "$OUT/$1_b$2_$3.json" 2> "$OUT/$1_b$2_$3.err"
 done
 python - "$OUT" <<'PY'
 import json, glob, sys, os

@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for cfg in $CONFIGS; do
   IFS=_ read -r variant b dt <<< "$cfg"; b=${b#b}
-  ARGS="--variant $variant --batch $b --dtype $dt --no-cpu-baseline --no-extra"
+  ARGS="--full --variant $variant --batch $b --dtype $dt --no-cpu-baseline --no-extra"
   python "$R/bench.py" $ARGS --layers "$OUT/classes_$cfg.txt" > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err"
   rocprofv3 --kernel-trace --stats -d "$OUT/trace_$cfg" -o t -- python "$R/bench.py" $ARGS --steps 40 --warmup 5 > "$OUT/trace_$cfg.log" 2>&1
   pmc() { local name=$1; shift

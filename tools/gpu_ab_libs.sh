@@ -2,7 +2,7 @@
 # A-B-A-B of two prebuilt libraries (livespeechportraits_amd/_ab/liblspf2f_{old,new}.so) swapped in place; the new one stays.  Usage: tools/gpu_ab_libs.sh <tag> [kernel-class prefix]
 cd $GRAFT_REPO_ROOT; OUT=gpurun_out/$1; mkdir -p $OUT; PFX=${2:-wino}
 L=livespeechportraits_amd
-run() { python bench.py --no-cpu-baseline --no-extra --steps 100 --batch $2 2>/dev/null | python -c "
+run() { python bench.py --full --no-cpu-baseline --no-extra --steps 100 --batch $2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 pc={c['kernel']:c for c in d['roofline']['per_class']}

@@ -1,6 +1,8 @@
 #!/bin/bash
 # PMC passes (separate rocprofv3 runs per counter group, as MI355X_MICROARCH.md prescribes;
 # never combined with sys/hip/hsa traces).  Usage: tools/pmc.sh <outdir> [bench args...]
+# The bench runs are plain: 1 warm-up + 2 timed forwards per pass.  Add --full to the bench args for the composition of runs taken before
+# --full existed (they also held the clock probe's second loop and the roofline's eager forward and class replays); raw totals compare only with the same composition.
 set -u
 OUT=$1; shift
 mkdir -p "$OUT"

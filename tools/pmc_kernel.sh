@@ -1,5 +1,7 @@
 #!/bin/bash
 # PMC counters of the kernels whose name contains <pattern> inside bench.py (GPU box).  Usage: tools/pmc_kernel.sh <outdir> <pattern> [bench args]
+# The bench runs are plain: 1 warm-up + 2 timed forwards per pass.  Add --full to the bench args for the composition of runs taken before
+# --full existed (they also held the clock probe's second loop and the roofline's eager forward and class replays); raw totals compare only with the same composition.
 set -u
 OUT=$(realpath -m "$1"); PAT=$2; shift 2
 mkdir -p "$OUT"

@@ -1,6 +1,8 @@
 #!/bin/bash
 # FETCH_SIZE / L2 hit per LSP_HIP_XCD mode (separate rocprofv3 --pmc passes, no trace domains).
 # Usage: tools/xcd_fetch.sh <outdir> [bench args...]
+# The bench runs are plain: 1 warm-up + 2 timed forwards per pass.  Add --full to the bench args for the composition of runs taken before
+# --full existed (they also held the clock probe's second loop and the roofline's eager forward and class replays); raw totals compare only with the same composition.
 set -u
 OUT=$(realpath -m "$1"); shift
 mkdir -p "$OUT"
