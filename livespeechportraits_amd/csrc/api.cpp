@@ -202,6 +202,16 @@ int lspf2f_create_tuned(const lspf2f_config *cfg, const char *tune, lspf2f_handl
                                   (cfg->flags & LSPF2F_FLAG_KEEP_INTERMEDIATES) != 0, cfg->dtype,
                                   (cfg->flags & LSPF2F_FLAG_INSTANCE_NORM) ? 1 : 0, cfg->max_batch);
     if (!e.empty()) { delete h; return fail(LSPF2F_ERR_UNSUPPORTED, e); }
+    int largest = -1;
+    const int frames = P.max_frames(&largest);
+    if (cfg->max_batch > frames) {
+        const TensorDesc &t = P.tensors[largest];
+        const std::string msg = "max_batch " + std::to_string(cfg->max_batch) + " exceeds the limit of " + std::to_string(frames) + " frames: " + t.name + " (" +
+                                std::to_string(t.h) + "x" + std::to_string(t.h) + "x" + std::to_string(t.c) + ", " + std::to_string((size_t)t.c * t.h * t.h * P.elt()) +
+                                " bytes per frame) must stay within the kernels' 2 GiB tensor limit (32-bit buffer offsets)";
+        delete h;
+        return fail(LSPF2F_ERR_UNSUPPORTED, msg);
+    }
     P.plan_batch(cfg->max_batch);
     *out = h;
     return LSPF2F_OK;

@@ -568,11 +568,19 @@ BatchLayout layout_for(const Plan &p, int batch, std::vector<size_t> *offsets, s
                                              : batch >= p.bandconv_min_frames_small);
             if (bandconv) { bm = l.ho == 16 ? 64 : 32; bn = 32; splits = 1; group = 1; }
             int pbn = 0;
-            const int patch16 = (p.use_patch16 && !smallm && !fullk && !rowconv && !bandconv)
-                                    ? patch16_choice(batch, l.ho, l.c0, l.c1, l.cout, l.stride, l.up, l.up4, p.dtype, l.inorm, p.patch16_min_blocks, &pbn) : 0;
+            int patch16 = (p.use_patch16 && !smallm && !fullk && !rowconv && !bandconv)
+                              ? patch16_choice(batch, l.ho, l.c0, l.c1, l.cout, l.stride, l.up, l.up4, p.dtype, l.inorm, p.patch16_min_blocks, &pbn) : 0;
             int patchup16 = 0;
             if (!patch16 && p.use_patch16 && p.use_patchup16 && !smallm && !fullk && !rowup && !winoup)
                 patchup16 = patchup16_choice(batch, l.hs, l.c0, l.c1, l.cout, l.up4, p.dtype, l.inorm, p.patch16_min_blocks, &pbn);
+            if (patch16 || patchup16) {
+                // the launchers' own limits (32-bit buffer offsets: 2 GiB per tensor) decide too, like wino_choice(): a shape the launch would
+                // refuse keeps the implicit GEMM instead of failing during graph capture
+                PatchConvParams q{};
+                q.B = batch; q.H = q.W = patch16 ? l.ho : l.hs; q.C = l.c0; q.C1 = l.c1; q.Cout = l.cout; q.dtype = p.dtype;
+                q.src1 = l.c1 ? &q : nullptr;        // (only tested for presence)
+                if (patch16 ? !patch16_supported(q, patch16, pbn) : !patchup16_supported(q, patchup16, pbn)) patch16 = patchup16 = 0;
+            }
             if (patch16 || patchup16) { bm = 256; bn = pbn; splits = 1; group = 1; }
             int route = kInNone;
             if (l.inorm) {
@@ -631,6 +639,18 @@ void Plan::plan_batch(int batch)
     stats_offset = partial_offset + partial_bytes;
     stats_groups_max = bl.groups_max;
     planned_batch = batch;
+}
+
+int Plan::max_frames(int *largest) const
+{
+    size_t most = 0;
+    int arg = -1;
+    for (size_t i = 0; i < tensors.size(); ++i) {
+        const size_t b = (size_t)tensors[i].c * tensors[i].h * tensors[i].h * elt();
+        if (b > most) { most = b; arg = (int)i; }
+    }
+    if (largest) *largest = arg;
+    return most ? (int)std::min<size_t>(0x7fffffffull / most, 0x7fffffff) : 0x7fffffff;
 }
 
 size_t Plan::workspace_bytes(int batch) const

@@ -166,6 +166,10 @@ struct Plan {
     int blob_pad_kb = 0;           // tune key `blob_pad_kb` (tools): empty KB in front of the first layer's weights
     bool keep_all_forms = false;   // tune key `all_forms=1`: every form whatever the batch range (tests that look at forms other batches would use)
     void plan_batch(int batch);
+    // the most frames one forward can run: every kernel addresses a tensor through 32-bit buffer offsets (top bit = out-of-range marker),
+    // so the largest activation tensor of the plan must stay within 2 GiB - 1 at the batch (the implicit GEMM refuses its source past it,
+    // igemm.hip launch_igemm; 8 MiB per frame at 512x512 in 16 bits: 255 frames).  `largest` (optional) receives that tensor's index.
+    int max_frames(int *largest = nullptr) const;
     size_t workspace_bytes(int batch) const;   // without mutating the current plan
     std::string pack(void *blob, size_t bytes) const;   // "" or error
     int64_t layer_flops(const LayerDesc &l) const;
