@@ -1,4 +1,4 @@
-"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h).
+"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h).
 
 There is deliberately no fallback: if the shared library is missing or does not
 load, importing the hot path raises -- a GPU box must never silently run
@@ -270,6 +270,17 @@ UNET_SIGNATURES = {
     "lspunet_launch_info": (c_int, [c_void_p, c_int, c_int, POINTER(c_char_p), POINTER(c_char_p), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
 }
 
+# every symbol include/lspjpeg.h declares
+JPEG_SIGNATURES = {
+    "lspjpeg_create": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "lspjpeg_destroy": (c_int, [c_void_p]),
+    "lspjpeg_last_error": (c_char_p, []),
+    "lspjpeg_header": (c_int64, [c_void_p, c_void_p, c_size_t]),
+    "lspjpeg_capacity_bytes": (c_size_t, [c_void_p]),
+    "lspjpeg_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "lspjpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 _lib = None
 
 
@@ -287,7 +298,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise NativeLibraryError("failed to load %s: %s" % (LIB_PATH, e)) from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -382,3 +393,15 @@ def check_unet(rc: int) -> None:
     if rc != OK:
         msg = load().lspunet_last_error()
         raise LspunetError(rc, msg.decode() if msg else "")
+
+
+class LspjpegError(RuntimeError):
+    def __init__(self, code: int, msg: str):
+        super().__init__("lspjpeg error %d: %s" % (code, msg))
+        self.code = code
+
+
+def check_jpeg(rc: int) -> None:
+    if rc != OK:
+        msg = load().lspjpeg_last_error()
+        raise LspjpegError(rc, msg.decode() if msg else "")

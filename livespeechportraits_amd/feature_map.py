@@ -54,17 +54,19 @@ class FeatureMapRasteriser:
 
     # -- batched entry point ---------------------------------------------------------------------------------------
     def rasterise(self, landmarks, shoulders=None, pad: Optional[Sequence[float]] = None, out: Optional[torch.Tensor] = None,
-                  as_uint8: bool = False) -> torch.Tensor:
+                  as_uint8: bool = False, out_u8: Optional[torch.Tensor] = None) -> torch.Tensor:
         """landmarks [B, 73, 2] (x, y), shoulders [B, n_shoulder, 2] or None (numpy or torch, any float type / int32, host or
         device) -> float32 [B, 1, H, W] in {0, 1} on the device (uint8 [B, H, W] in {0, 255} when ``as_uint8``).
         ``pad`` = (top, bottom, left, right) shifts the shoulders by (right - left, top - bottom) as get_feature_image does
         (face_dataset.py:287-292; applied to a copy, the reference shifts its argument in place)."""
-        return self.rasterise_points(self._points(landmarks, shoulders, pad), out, as_uint8)
+        return self.rasterise_points(self._points(landmarks, shoulders, pad), out, as_uint8, out_u8)
 
-    def rasterise_points(self, pts: torch.Tensor, out: Optional[torch.Tensor] = None, as_uint8: bool = False) -> torch.Tensor:
+    def rasterise_points(self, pts: torch.Tensor, out: Optional[torch.Tensor] = None, as_uint8: bool = False,
+                         out_u8: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The same with the points already laid out as the kernel wants them: ONE device tensor [B, 73 + n_shoulder, 2] (landmarks
         then shoulder points, pad shift applied), int32 / float32 / float64 -- a render loop that keeps such a buffer moves one
-        ~1.5 KB H2D copy per frame and launches nothing else."""
+        ~1.5 KB H2D copy per frame and launches nothing else.  ``out_u8`` (with the float map only): a uint8 [B, H, W] tensor that receives
+        the {0, 255} map of the same launch as well (demo.py:270's ``np.uint8(map * 255)``, the input_<n>.jpg of save_input)."""
         if pts.device != self.device or pts.dim() != 3 or pts.shape[1] != N_LANDMARKS + self.n_shoulder or pts.shape[2] != 2 \
                 or not pts.is_contiguous() or pts.dtype not in (torch.int32, torch.float32, torch.float64):
             raise ValueError("points must be a contiguous [B, %d, 2] int32/float32/float64 tensor on %s" % (N_LANDMARKS + self.n_shoulder, self.device))
@@ -79,6 +81,12 @@ class FeatureMapRasteriser:
         want = ((b, s, s), torch.uint8) if as_uint8 else ((b, 1, s, s), torch.float32)
         if res.device != self.device or not res.is_contiguous() or tuple(res.shape) != want[0] or res.dtype != want[1]:
             raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (want[1], list(want[0]), self.device))
+        if out_u8 is not None:
+            if as_uint8:
+                raise ValueError("out_u8 goes with the float map: use out with as_uint8=True for the uint8 map alone")
+            if out_u8.device != self.device or not out_u8.is_contiguous() or tuple(out_u8.shape) != (b, s, s) or out_u8.dtype != torch.uint8:
+                raise ValueError("out_u8 must be a contiguous torch.uint8 tensor of shape %s on %s" % ([b, s, s], self.device))
+            u8 = out_u8
         p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         with torch.cuda.device(self.device):
             N.check_raster(self.lib.lspraster_edge_maps(p(pts), N.RASTER_POINT_DTYPES[str(pts.dtype).replace("torch.", "")], b,

@@ -27,7 +27,8 @@ def batched(it: Iterable, n: int) -> Iterator[List]:
 
 def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch.Tensor, batch: int = 8,
                   device: Optional[torch.device] = None,
-                  on_frame: Optional[Callable[[int, np.ndarray], None]] = None, streams: int = 2) -> List[np.ndarray]:
+                  on_frame: Optional[Callable[[int, np.ndarray], None]] = None, streams: int = 2,
+                  jpeg_quality: Optional[int] = None) -> List[np.ndarray]:
     """``feature_maps`` yields [1,H,W] (or [C,H,W]) CPU/GPU tensors as
     ``facedataset.dataset.get_data_test_mode`` does (demo.py:262); ``cand_image`` is demo.py's
     ``img_candidates`` ([1,12,H,W], already on the device).  Returns (or streams to ``on_frame``) uint8 HWC
@@ -41,11 +42,17 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
     Measured, round 5 (tools/render_loop_profile.py, tools/host_probe.py): the loop of rounds 2-4 ran at 70-290 frames/s on a generator that renders 665-1019 -- because of the
     host-side copy described at the gather below, not because of how it waited or allocated (a hipGraph cache miss costs nothing next to a forward; the late event waits seen in the
     first measurements were not separated from that throttling).
-    A model that cannot give a second handle (the `small` U-Net, several gpu_ids, stand-ins) gets one lane on the current stream: enqueue, wait, hand out."""
+    A model that cannot give a second handle (the `small` U-Net, several gpu_ids, stand-ins) gets one lane on the current stream: enqueue, wait, hand out.
+
+    ``jpeg_quality`` (1..100, Pillow's default is 75): every lane encodes its frames on its own stream right behind the generator (jpeg.JpegEncoder,
+    include/lspjpeg.h) and the frames are handed out as complete JPEG files (``bytes``, what demo.py:271's save_images writes as pred_<n>.jpg); only the
+    compressed bytes cross PCIe.  There is no host encoder: a model on the host with ``jpeg_quality`` raises."""
     device = device or cand_image.device
     frames: List[np.ndarray] = []
     idx = 0
     on_gpu = device.type == "cuda"
+    if jpeg_quality is not None and not on_gpu:
+        raise ValueError("jpeg_quality: the JPEG encoder runs on the device only, and this model renders on the host")
     nlane = max(1, int(streams)) if on_gpu and getattr(model, "supports_replicas", lambda: False)() else 1
     try:
         takes_out = "out" in inspect.signature(model.inference_image).parameters      # (stand-in models of the tests do not)
@@ -53,26 +60,29 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
         takes_out = False
     lanes: List[dict] = []              # made at the first batch (shapes come from the data)
 
-    def emit(i0, host, n):
-        for k in range(n):
-            arr = host[k].numpy().copy()
+    def emit(i0, items):
+        for k, item in enumerate(items):
             if on_frame is not None:
-                on_frame(i0 + k, arr)
+                on_frame(i0 + k, item)
             else:
-                frames.append(arr)
+                frames.append(item)
 
     def drain(lane):
         if lane["busy"] is not None:
             i0, n = lane["busy"]
-            (lane["stream"] if lane["stream"] is not None else torch.cuda.current_stream(device)).synchronize()
-            emit(i0, lane["host"], n)
+            if lane["jpeg"] is not None:
+                emit(i0, lane["jpeg"].collect())                # waits for the lane's stream, then copies the compressed bytes only
+            else:
+                (lane["stream"] if lane["stream"] is not None else torch.cuda.current_stream(device)).synchronize()
+                emit(i0, [lane["host"][k].numpy().copy() for k in range(n)])
             lane["busy"] = None
 
     for n, chunk in enumerate(batched(feature_maps, batch)):
         chunk = [m if m.dim() == 3 else m.unsqueeze(0) for m in chunk]
         b = len(chunk)
         if not on_gpu:                                          # (stand-in models on the host: tests)
-            emit(idx, model.inference_image(torch.stack(chunk).to(device, torch.float32), cand_image), b)
+            host = model.inference_image(torch.stack(chunk).to(device, torch.float32), cand_image)
+            emit(idx, [host[k].numpy().copy() for k in range(b)])
             idx += b
             continue
         if not lanes:
@@ -82,7 +92,7 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
                 st = torch.cuda.Stream(device) if nlane > 1 else None
                 if st is not None:
                     st.wait_stream(cur)                          # cand_image was produced there
-                lanes.append({"stream": st, "busy": None, "host": None, "u8": None,
+                lanes.append({"stream": st, "busy": None, "host": None, "u8": None, "jpeg": None,
                               "stage": torch.empty(shape, dtype=torch.float32, pin_memory=True), "dev": torch.empty(shape, dtype=torch.float32, device=device)})
                 lanes[-1]["stage_np"] = lanes[-1]["stage"].numpy()
         lane = lanes[n % nlane]
@@ -114,9 +124,15 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
                     lane["u8"] = torch.empty((batch, H, H, 3), dtype=torch.uint8, device=device)
                 kw["out"] = lane["u8"][:b]
             u8 = model.inference_image(lane["dev"][:b], cand_image, **kw)
-            if lane["host"] is None:
-                lane["host"] = torch.empty((batch,) + tuple(u8.shape[1:]), dtype=torch.uint8, pin_memory=True)
-            lane["host"][:b].copy_(u8, non_blocking=True)
+            if jpeg_quality is not None:
+                if lane["jpeg"] is None:
+                    from .jpeg import JpegEncoder
+                    lane["jpeg"] = JpegEncoder(tuple(u8.shape[1:3]), 3, jpeg_quality, device, max_batch=batch)
+                lane["jpeg"].submit(u8)                         # on the lane's stream, behind the generator
+            else:
+                if lane["host"] is None:
+                    lane["host"] = torch.empty((batch,) + tuple(u8.shape[1:]), dtype=torch.uint8, pin_memory=True)
+                lane["host"][:b].copy_(u8, non_blocking=True)
         lane["busy"] = (idx, b)
         idx += b
         if nlane == 1:
@@ -137,35 +153,66 @@ class _null:
 
 def render_frames_from_landmarks(model, landmarks: Iterable, shoulders: Iterable, cand_image: torch.Tensor,
                                  pad=None, load_size: int = 512, batch: int = 8,
-                                 on_frame: Optional[Callable[[int, np.ndarray], None]] = None) -> List[np.ndarray]:
+                                 on_frame: Optional[Callable[[int, np.ndarray], None]] = None,
+                                 jpeg_quality: Optional[int] = None, save_input: bool = False) -> List[np.ndarray]:
     """demo.py:260-272 with the edge map drawn on the device: per frame the loop moves the 73 landmarks and the shoulder
     points (~1.5 KB) instead of a host-rasterised 1 MiB feature map.  ``landmarks`` yields [73, 2] arrays (``pred_landmarks[i]``
-    of demo.py:262), ``shoulders`` yields [n, 2] arrays (``pred_shoulders[i]``); ``pad`` as ``facedataset.dataset.image_pad``."""
+    of demo.py:262), ``shoulders`` yields [n, 2] arrays (``pred_shoulders[i]``); ``pad`` as ``facedataset.dataset.image_pad``.
+
+    ``jpeg_quality``: frames are encoded on the device behind the generator and handed out as JPEG files (``bytes``, see render_frames).
+    ``save_input`` (``Image2Image.save_input``, demo.py:269-270): every frame is a ``(pred, input)`` pair, ``input`` the uint8 edge map
+    ``np.uint8(map * 255)`` -- written by the rasteriser in the same launch as the float map, and JPEG-encoded (grayscale) with ``jpeg_quality``."""
     from .feature_map import FeatureMapRasteriser
     device = cand_image.device
+    if jpeg_quality is not None and device.type != "cuda":
+        raise ValueError("jpeg_quality: the JPEG encoder runs on the device only")
     rast = None
-    maps_buf = None
+    maps_buf = edge_buf = None
+    enc = enc_in = None
 
     def chunks():
-        nonlocal rast, maps_buf
+        nonlocal rast, maps_buf, edge_buf
         for lm, sh in zip(batched(landmarks, batch), batched(shoulders, batch)):
             lm_a, sh_a = np.stack([np.asarray(x) for x in lm]), np.stack([np.asarray(x) for x in sh])
+            b = lm_a.shape[0]
             if rast is None:
                 rast = FeatureMapRasteriser(load_size, sh_a.shape[1], device)
                 maps_buf = torch.empty((batch, 1, load_size, load_size), dtype=torch.float32, device=device)
-            yield rast.rasterise(lm_a, sh_a, pad, out=maps_buf[:lm_a.shape[0]])
+                if save_input:
+                    edge_buf = torch.empty((batch, load_size, load_size), dtype=torch.uint8, device=device)
+            edges = edge_buf[:b] if save_input else None
+            yield rast.rasterise(lm_a, sh_a, pad, out=maps_buf[:b], out_u8=edges), edges
 
     frames: List[np.ndarray] = []
     idx = 0
-    host = None                                                 # one pinned result tensor, reused
-    for maps in chunks():
+    host = host_in = None                                       # pinned result tensors, reused
+    for maps, edges in chunks():
         u8 = model.inference_image(maps, cand_image)
-        if host is None:
-            host = torch.empty((batch,) + tuple(u8.shape[1:]), dtype=torch.uint8, pin_memory=True)
-        host[:u8.shape[0]].copy_(u8, non_blocking=True)
-        # one batch at a time: the rasteriser's output tensor is reused, and the wait is on the stream's own tail
-        torch.cuda.current_stream(device).synchronize()
-        for k in range(u8.shape[0]):
-            (on_frame(idx + k, host[k].numpy().copy()) if on_frame else frames.append(host[k].numpy().copy()))
-        idx += u8.shape[0]
+        b = u8.shape[0]
+        if jpeg_quality is not None:
+            from .jpeg import JpegEncoder
+            if enc is None:
+                enc = JpegEncoder(tuple(u8.shape[1:3]), 3, jpeg_quality, device, max_batch=batch)
+                enc_in = JpegEncoder(load_size, 1, jpeg_quality, device, max_batch=batch) if save_input else None
+            enc.submit(u8)
+            if save_input:
+                enc_in.submit(edges)
+            # one batch at a time: the rasteriser's output tensors are reused, and collect() waits on the stream's own tail
+            preds = enc.collect()
+            items = list(zip(preds, enc_in.collect())) if save_input else preds
+        else:
+            if host is None:
+                host = torch.empty((batch,) + tuple(u8.shape[1:]), dtype=torch.uint8, pin_memory=True)
+                host_in = torch.empty((batch, load_size, load_size), dtype=torch.uint8, pin_memory=True) if save_input else None
+            host[:b].copy_(u8, non_blocking=True)
+            if save_input:
+                host_in[:b].copy_(edges, non_blocking=True)
+            # one batch at a time: the rasteriser's output tensor is reused, and the wait is on the stream's own tail
+            torch.cuda.current_stream(device).synchronize()
+            items = [host[k].numpy().copy() for k in range(b)]
+            if save_input:
+                items = [(items[k], host_in[k].numpy().copy()) for k in range(b)]
+        for k, item in enumerate(items):
+            (on_frame(idx + k, item) if on_frame else frames.append(item))
+        idx += b
     return frames

@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""Cost of the device JPEG encoder (include/lspjpeg.h) in one session on the GPU, recorded to profiles/<name>.json (+ .txt):
+  (a) device time of lspjpeg_encode for 8 frames of 512^2 at q75: the `normal` bf16 generator's own uint8 frames (colour) and the rasteriser's
+      uint8 edge maps (grayscale), with the bf16 batch-8 forward timed the same way for the 10 % bar;
+  (b) Pillow (Image.fromarray(img).save(f, "JPEG", quality=75)) on the same frames with 1 and 16 threads, on this host, if Pillow is installed;
+  (c) render_frames frames/s, `normal` bf16, batch 8, without and with jpeg_quality=75, run A-B-A-B.
+    python tools/jpeg_time.py [name] [output directory, default profiles/]"""
+import argparse
+import ctypes
+import io
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import livespeechportraits_amd as L  # noqa: E402
+from livespeechportraits_amd import _native as N, synth  # noqa: E402
+from livespeechportraits_amd.engine import Engine  # noqa: E402
+from livespeechportraits_amd.feature_map import FeatureMapRasteriser  # noqa: E402
+from livespeechportraits_amd.jpeg import JpegEncoder  # noqa: E402
+from livespeechportraits_amd.render_loop import render_frames  # noqa: E402
+from livespeechportraits_amd.topology import build_topology  # noqa: E402
+
+name = sys.argv[1] if len(sys.argv) > 1 else "jpeg_time"
+out_dir = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles")
+dev = torch.device("cuda:0")
+B, S, Q = 8, 512, 75
+rec = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "batch": B, "size": S, "quality": Q}
+lines = []
+
+
+def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+
+def device_us(fn, reps=50, warm=5):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / reps
+
+
+# ---- the frames: the normal bf16 generator's own output and the rasteriser's edge maps ------------------------------------------
+topo = build_topology("normal")
+sd = synth.make_state_dict(topo, 1234)
+eng = Engine("normal", size=S, max_batch=B, dtype="bf16")
+eng.load_state_dict(sd)
+eng.bind(eng.pack(), dev)
+feats, cand = synth.make_inputs(B, S, seed=5, cand_batch=1)
+fd, cd = torch.from_numpy(feats).to(dev), torch.from_numpy(cand).to(dev)
+u8 = torch.empty((B, S, S, 3), dtype=torch.uint8, device=dev)
+eng.forward_image(fd, cd, out_u8=u8)
+rng = np.random.default_rng(5)
+lm = 256 + rng.normal(0, 60, (B, 73, 2))
+sh = np.stack([np.linspace(0, 512, 18), np.full(18, 470.0)], 1)[None].repeat(B, 0)
+edges = FeatureMapRasteriser(S, 18, dev).rasterise(lm, sh, as_uint8=True)
+torch.cuda.synchronize()
+
+encs = {"colour": (JpegEncoder(S, 3, Q, dev, max_batch=B), u8), "gray": (JpegEncoder(S, 1, Q, dev, max_batch=B), edges)}
+st = torch.cuda.current_stream(dev)
+
+
+def launch(enc, x):
+    N.check_jpeg(enc.lib.lspjpeg_encode(enc._h, ctypes.c_void_p(x.data_ptr()), B, ctypes.c_void_p(enc._dst.data_ptr()), ctypes.c_void_p(enc._sizes.data_ptr()),
+                                        ctypes.c_void_p(enc._ws.data_ptr()), enc._ws_bytes, ctypes.c_void_p(st.cuda_stream)))
+
+
+rec["a"] = {}
+fwd = []
+for rep in range(2):                                       # A-B: forward, colour, gray, both
+    fwd.append(device_us(lambda: eng.forward_image(fd, cd, out_u8=u8)))
+    for k, (enc, x) in encs.items():
+        rec["a"].setdefault(k + "_us", []).append(round(device_us(lambda: launch(enc, x)), 2))
+    rec["a"].setdefault("colour_plus_gray_us", []).append(round(device_us(lambda: (launch(*encs["colour"]), launch(*encs["gray"]))), 2))
+rec["a"]["bf16_forward_b8_us"] = [round(v, 1) for v in fwd]
+files = {k: enc.encode(x) for k, (enc, x) in encs.items()}
+rec["a"]["bytes_per_frame"] = {k: int(np.mean([len(f) for f in v])) for k, v in files.items()}
+both, f = min(rec["a"]["colour_plus_gray_us"]), min(fwd)
+rec["a"]["encode_over_forward"] = round(both / f, 4)
+say("(a) device, %d frames %d^2 q%d: colour %s us, gray %s us, colour+gray %s us; bf16 forward_image batch %d: %s us -> encode / forward = %.1f %% (bar 10 %%); "
+    "mean file: colour %d B, gray %d B" % (B, S, Q, rec["a"]["colour_us"], rec["a"]["gray_us"], rec["a"]["colour_plus_gray_us"], B, rec["a"]["bf16_forward_b8_us"],
+                                           100 * both / f, rec["a"]["bytes_per_frame"]["colour"], rec["a"]["bytes_per_frame"]["gray"]))
+# with the copy of the compressed bytes to pinned host memory (what render_frames pays per batch)
+rec["a"]["encode_and_fetch_ms"] = {}
+for k, (enc, x) in encs.items():
+    enc.encode(x)
+    t0 = time.perf_counter()
+    for _ in range(20):
+        enc.encode(x)
+    rec["a"]["encode_and_fetch_ms"][k] = round((time.perf_counter() - t0) / 20 * 1e3, 3)
+say("(a') encode + sizes + bytes to pinned host memory, host clock: %s ms per batch of %d" % (rec["a"]["encode_and_fetch_ms"], B))
+
+# ---- (b) Pillow on this host -------------------------------------------------------------------------------------------------
+host = {"colour": u8.cpu().numpy(), "gray": edges.cpu().numpy()}
+try:
+    from PIL import Image, features
+    from concurrent.futures import ThreadPoolExecutor
+
+    def pil(img):
+        b = io.BytesIO()
+        Image.fromarray(img).save(b, "JPEG", quality=Q)
+        return b.getvalue()
+    rec["b"] = {"where": "the host CPU of the machine that holds the GPU", "pillow": Image.__version__,
+                "libjpeg_turbo": features.version("libjpeg_turbo")}
+    for k, frames in host.items():
+        same = [pil(frames[i]) for i in range(B)] == files[k]
+        t0 = time.perf_counter()
+        for _ in range(5):
+            for i in range(B):
+                pil(frames[i])
+        one = (time.perf_counter() - t0) / 5
+        with ThreadPoolExecutor(16) as ex:
+            list(ex.map(pil, list(frames)))
+            t0 = time.perf_counter()
+            for _ in range(5):
+                list(ex.map(pil, list(frames)))
+            sixteen = (time.perf_counter() - t0) / 5
+        rec["b"][k] = {"1_thread_ms_per_batch": round(one * 1e3, 3), "16_threads_ms_per_batch": round(sixteen * 1e3, 3), "device_bytes_equal_pillow": same}
+    say("(b) Pillow %s (libjpeg-turbo %s) on the GPU host, %d frames: %s" % (rec["b"]["pillow"], rec["b"]["libjpeg_turbo"], B,
+                                                                          {k: rec["b"][k] for k in host}))
+except ImportError:
+    rec["b"] = {"where": "not installed on the GPU host: see the build-machine figures in README"}
+    say("(b) Pillow is not installed on this host")
+
+# ---- (c) render_frames frames/s, normal bf16, batch 8, A-B-A-B ------------------------------------------------------------------
+opt = argparse.Namespace(model="feature2face", gpu_ids=[0], isTrain=False, size="normal", ngf=64, n_downsample_G=8, fp16=0, checkpoints_dir=tempfile.mkdtemp(), name="t",
+                         load_epoch="none", verbose=False)
+model = L.create_model(opt)
+model._g().netG.dtype = "bf16"                             # the bf16 storage plan (bench.py's configs[2]) before the first engine is built
+model._g().load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()})
+model.eval()
+nframes = 256
+maps = [torch.from_numpy(feats[i % B]).pin_memory() for i in range(nframes)]
+rec["c"] = {"plain_fps": [], "jpeg75_fps": []}
+for arm in ("plain", "jpeg75", "plain", "jpeg75", "plain", "jpeg75"):
+    kw = {"jpeg_quality": 75} if arm == "jpeg75" else {}
+    render_frames(model, iter(maps[:4 * B]), cd, batch=B, **kw)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = render_frames(model, iter(maps), cd, batch=B, **kw)
+    dt = time.perf_counter() - t0
+    rec["c"][arm + "_fps"].append(round(nframes / dt, 1))
+    say("(c) render_frames normal bf16 batch %d, %s: %.1f frames/s (%d frames in %.3f s)" % (B, arm, nframes / dt, nframes, dt))
+eng.close()
+os.makedirs(out_dir, exist_ok=True)
+with open(os.path.join(out_dir, name + ".json"), "w") as fh:
+    json.dump(rec, fh, indent=1)
+with open(os.path.join(out_dir, name + ".txt"), "w") as fh:
+    fh.write("\n".join(lines) + "\n")
