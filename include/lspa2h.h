@@ -100,6 +100,23 @@ int lspa2h_bind_workspace(lspa2h_handle *h, void *workspace_dev, size_t bytes);
 int lspa2h_generate(lspa2h_handle *h, const float *audio_dev, int n_audio, const float *pre_dev, const float *noise_dev,
                     const float *expq_dev, float sigma_scale, int frame_future, float *out_dev, int nframe, void *stream);
 
+/* Resumable generation for a stream whose audio rows arrive in pieces (the single-workgroup kernel).  The carried state -- every layer's
+ * dilation queue, the 12-float WaveNet input and the step counter (which also fixes each queue's ring slot) -- is read from state_in at
+ * the start and written to state_out at the end: lspa2h_state_bytes() bytes of device memory each, two SEPARATE buffers (a call whose
+ * status is not 0 is run again from the same state_in).
+ *   audio_dev [n_new][2*hidden_size]  audio rows row0 .. row0+n_new-1 of the stream, each passed exactly once (n_new may be 0);
+ *                                     their cond projections go to a ring of max_audio_frames rows in the workspace
+ *   frame0, nframe                     this call generates frames [frame0, frame0 + nframe), nframe >= 1
+ *   state_in                           NULL: start of the clip (frame0 == 0, queues zero, input = pre_dev, priming steps included);
+ *                                      else the state_out of the call that ended at frame0 (checked on the device: status 0x5000000)
+ *   noise_dev / expq_dev / out_dev     rows of THIS call's frames, as in lspa2h_generate
+ * Frame f reads audio row f + frame_future (the priming steps rows 0..frame_future-1): every row a call reads must lie in
+ * [row0 + n_new - max_audio_frames, row0 + n_new).  Chained calls give the bits of one lspa2h_generate call over the whole clip. */
+size_t lspa2h_state_bytes(const lspa2h_handle *h);
+int lspa2h_generate_resume(lspa2h_handle *h, const float *audio_dev, int row0, int n_new, const float *pre_dev, const float *noise_dev,
+                           const float *expq_dev, float sigma_scale, int frame_future, int frame0, int nframe, const void *state_in,
+                           void *state_out, float *out_dev, void *stream);
+
 /* Waits for `stream` and reports whether the last lspa2h_generate completed: *code == 0, or the identifier of the
  * first inter-workgroup hand-off that timed out (the kernel never spins unbounded; output rows are then undefined). */
 int lspa2h_status(lspa2h_handle *h, void *stream, uint32_t *code);

@@ -52,6 +52,17 @@ size_t lspmel_workspace_bytes(int nwindows);
 int lspmel_compute(const float *audio_dev, int64_t nsamples, const float *basis_dev, int nwindows, float *mel_dev,
                    void *workspace_dev, size_t workspace_bytes, void *hip_stream);
 
+/* Start sample of window i: int(i * (16000 * (0.5 / 60))), the same double product as compute_mel_one_sequence (utils.py:74). */
+int64_t lspmel_window_start(int64_t window);
+
+/* Windows [win0, win0 + nwin) of a stream, for a caller that receives the audio in pieces.  audio_dev holds stream samples
+ * [first_sample, first_sample + navail); window win0 must start at or after first_sample.  `ended` != 0 says the clip ends after those
+ * samples: only then may a window's 266-sample clip reach past them, and it is zero padded as utils.py:76-79 does; the windows must then
+ * lie below lspmel_num_windows(first_sample + navail).  Without `ended` such a window is refused (LSPMEL_ERR_SHAPE).  Row r of mel_dev is
+ * bit for bit row win0 + r of lspmel_compute over the whole clip; workspace >= lspmel_workspace_bytes(nwin). */
+int lspmel_compute_range(const float *audio_dev, int64_t first_sample, int64_t navail, int ended, int64_t win0, int nwin,
+                         const float *basis_dev, float *mel_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream);
+
 const char *lspmel_last_error(void);
 
 #pragma GCC visibility pop

@@ -11,7 +11,7 @@
  *   GRU : r = s(W_ir x + b_ir + W_hr h + b_hr), z likewise, n = tanh(W_in x + b_in + r * (W_hn h + b_hn)),
  *         h' = (1 - z) * n + z * h
  *   LSTM: i, f, g, o = W_i x + b_i + W_h h + b_h; c' = s(f) c + s(i) tanh(g); h' = s(o) tanh(c')
- * Zero initial state, batch 1, fp32.  Conventions as lspf2f.h (0 / negative status, lsprnn_last_error(), no device
+ * Zero initial state (lsprnn_forward) or a carried one (lsprnn_forward_state), batch 1, fp32.  Conventions as lspf2f.h (0 / negative status, lsprnn_last_error(), no device
  * allocation, asynchronous on `stream`).
  */
 #ifndef LSPRNN_H
@@ -74,6 +74,15 @@ int lsprnn_bind_workspace(lsprnn_handle *h, void *workspace_dev, size_t bytes);
 
 /* output, _ = rnn(x) for x [1][T][input_size]: out_dev [T][hidden_size] = the last layer's hidden states. */
 int lsprnn_forward(lsprnn_handle *h, const float *x_dev, int T, float *out_dev, void *stream);
+
+/* The same with a carried state, in PyTorch's h_n / (h_n, c_n) layout: GRU h [num_layers][hidden_size]; LSTM h [num_layers][hidden_size]
+ * followed by c [num_layers][hidden_size] -- lsprnn_state_floats() floats, device fp32.  state_in_dev == NULL starts from zeros (exactly
+ * lsprnn_forward); state_out_dev == NULL does not write the final state.  The two must be separate buffers: a call whose hand-off timed out
+ * (lsprnn_status) is run again from the same state_in.  Splitting a sequence into calls that chain state_out -> state_in gives the bits of
+ * one call: every step's arithmetic and summation order is the same whatever T is. */
+size_t lsprnn_state_floats(const lsprnn_handle *h);
+int lsprnn_forward_state(lsprnn_handle *h, const float *x_dev, int T, float *out_dev, const float *state_in_dev, float *state_out_dev,
+                         void *stream);
 
 /* Waits for `stream`; *code == 0 if the last forward completed, else the hand-off that timed out (bounded polls). */
 int lsprnn_status(lsprnn_handle *h, void *stream, uint32_t *code);

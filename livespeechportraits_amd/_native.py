@@ -182,6 +182,9 @@ A2H_SIGNATURES = {
     "lspa2h_generate_timed": (c_int, _GEN_ARGS + [POINTER(c_float), POINTER(c_float)]),
     "lspa2h_debug_cond": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int)]),
     "lspa2h_status": (c_int, [c_void_p, c_void_p, POINTER(c_uint32)]),
+    "lspa2h_state_bytes": (c_size_t, [c_void_p]),
+    "lspa2h_generate_resume": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "lspa2h_sample_gmm": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
 }
 
@@ -219,6 +222,8 @@ RNN_SIGNATURES = {
     "lsprnn_workspace_bytes": (c_size_t, [c_void_p]),
     "lsprnn_bind_workspace": (c_int, [c_void_p, c_void_p, c_size_t]),
     "lsprnn_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "lsprnn_state_floats": (c_size_t, [c_void_p]),
+    "lsprnn_forward_state": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsprnn_status": (c_int, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "lsprnn_linear": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
 }
@@ -238,6 +243,8 @@ MEL_SIGNATURES = {
     "lspmel_make_basis": (c_int, [c_void_p, c_size_t]),
     "lspmel_workspace_bytes": (c_size_t, [c_int]),
     "lspmel_compute": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "lspmel_window_start": (c_int64, [c_int64]),
+    "lspmel_compute_range": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

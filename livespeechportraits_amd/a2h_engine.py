@@ -132,6 +132,45 @@ class HeadposeEngine:
             N.check_a2h(self.lib.lspa2h_generate_timed(*args, ctypes.byref(pre_ms), ctypes.byref(loop_ms)))
         return out, pre_ms.value, loop_ms.value
 
+    def state_bytes(self) -> int:
+        """Bytes of a carried generation state (dilation queues, WaveNet input, step counter): lspa2h_state_bytes."""
+        return int(self.lib.lspa2h_state_bytes(self.h))
+
+    def generate_resume(self, audio: Optional[torch.Tensor], row0: int, pre: Optional[torch.Tensor], noise: Optional[torch.Tensor],
+                        expq: Optional[torch.Tensor], sigma_scale: float, frame_future: int, frame0: int, nframe: int,
+                        state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Frames [frame0, frame0 + nframe) of a stream (include/lspa2h.h lspa2h_generate_resume): ``audio`` holds the stream's audio rows
+        [row0, row0 + len) not passed before (or None), ``state_in`` None starts the clip from ``pre``.  Asynchronous on the current stream."""
+        if self.blob is None:
+            raise RuntimeError("HeadposeEngine.bind(device) first")
+        dev = self.blob.device
+        for name, t in (("audio", audio), ("pre", pre), ("noise", noise), ("expq", expq), ("out", out)):
+            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous float32 device tensor (there is no CPU path)" % name)
+        for name, t in (("state_in", state_in), ("state_out", state_out)):
+            if t is not None and (not t.is_cuda or not t.is_contiguous() or t.numel() * t.element_size() != self.state_bytes()):
+                raise ValueError("%s must be a contiguous device buffer of %d bytes" % (name, self.state_bytes()))
+        n_new = 0
+        if audio is not None:
+            if audio.dim() != 2 or audio.shape[1] != 2 * self.hidden_size:
+                raise ValueError("audio must be [n, %d]" % (2 * self.hidden_size))
+            n_new = audio.shape[0]
+        if noise is not None and tuple(noise.shape) != (nframe, self.ndim):
+            raise ValueError("noise must be [%d, %d]" % (nframe, self.ndim))
+        if expq is not None and tuple(expq.shape) != (nframe, self.ncenter):
+            raise ValueError("expq must be [%d, %d]" % (nframe, self.ncenter))
+        if out is None:
+            out = torch.empty(nframe, self.ndim, dtype=torch.float32, device=dev)
+        elif tuple(out.shape) != (nframe, self.ndim):
+            raise ValueError("out must be [%d, %d]" % (nframe, self.ndim))
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(dev):
+            N.check_a2h(self.lib.lspa2h_generate_resume(self.h, ptr(audio) if n_new else None, int(row0), n_new, ptr(pre), ptr(noise), ptr(expq),
+                                                        ctypes.c_float(sigma_scale), int(frame_future), int(frame0), int(nframe),
+                                                        ptr(state_in), ptr(state_out), ptr(out),
+                                                        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return out
+
     def status(self, device=None) -> int:
         """Synchronises the current stream; 0 if the last generate() completed, else the code of the hand-off that timed out."""
         code = ctypes.c_uint32()

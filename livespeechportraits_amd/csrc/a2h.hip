@@ -62,6 +62,11 @@ struct StreamParams {
     unsigned *status;                   // 0 ok, else the code of the first hand-off that timed out
     unsigned epoch;                     // tag of this call (never 0)
     int stride;                         // only blocks with blockIdx.x % stride == 0 work (8: all on one XCD, for speed only)
+    // stream kernel: resumable form (lspa2h_generate_resume); the whole-clip call has frame0 = 0, no states, ring = max_audio_frames
+    int frame0;                         // first frame of this call; out / noise / expq row 0 belongs to it
+    int ring;                           // proj holds audio row r at row r % ring
+    const float *state_in;              // null: start of the clip; else queues [qrows][128], inb [16], step counter (int bits)
+    float *state_out;                   // null, or where the state after the last step goes (same layout)
 };
 
 template <int CTRL> __device__ __forceinline__ float dpp_add(float v)
@@ -106,10 +111,21 @@ __global__ __launch_bounds__(NT) void a2h_stream(StreamParams p)
 
     int qrows = 0;
     for (int l = 0; l < p.layers; ++l) qrows += p.dil[l];
-    for (int i = tid; i < qrows * RC; i += NT) queue[i] = 0.f;
-    if (tid < 16) inb[tid] = tid < p.ndim ? p.pre[tid] : 0.f;
+    const int nsteps = p.field - 1 + p.frame0 + p.nframe;
+    int s0 = 0;                                      // start of a clip: every priming step, queues zero, input = pre
+    if (p.state_in) {                                // resumed: the state saved after step field - 1 + frame0 - 1
+        s0 = p.field - 1 + p.frame0;
+        if (__float_as_int(p.state_in[qrows * RC + 16]) != s0) {
+            if (tid == 0) atomicCAS(p.status, 0u, 0x5000000u);    // the state belongs to another frame: refuse, outputs untouched
+            return;
+        }
+        for (int i = tid; i < qrows * RC; i += NT) queue[i] = p.state_in[i];
+        if (tid < 16) inb[tid] = p.state_in[qrows * RC + tid];
+    } else {
+        for (int i = tid; i < qrows * RC; i += NT) queue[i] = 0.f;
+        if (tid < 16) inb[tid] = tid < p.ndim ? p.pre[tid] : 0.f;
+    }
 
-    const int nsteps = p.field - 1 + p.nframe;
     const int fu = tid >> 3, fpart = tid & 7;        // fg item: channels fu and fu+64, 32-column part
     const int rq = tid >> 2, rpart = tid & 3;        // rs item: rows rq, 128+rq, 256+rq, 32-column part
     const unsigned fg_stride = 32 * NT * 16, rs_stride = 24 * NT * 16;   // bytes per layer
@@ -124,10 +140,10 @@ __global__ __launch_bounds__(NT) void a2h_stream(StreamParams p)
     load_packed<0, 32>(F, blob, p.fg_w, voff);
     __syncthreads();
 
-    for (int s = 0; s < nsteps; ++s) {
+    for (int s = s0; s < nsteps; ++s) {
         int arow = s + p.frame_future - (p.field - 1);
         arow = arow < 0 ? 0 : arow;                  // the reference prepends field-1 copies of audio row 0
-        const float *projrow = p.proj + (size_t)arow * projN;
+        const float *projrow = p.proj + (size_t)(arow % p.ring) * projN;
         // ---- start convs (networks.py:198-199): 1x1, bias, LeakyReLU
         if (tid < RC) {
             float a = p.start1_b[tid];
@@ -236,19 +252,24 @@ __global__ __launch_bounds__(NT) void a2h_stream(StreamParams p)
                     for (int k = 0; k < p.ncenter; ++k) den += expf(r2[k] - mx);
                     float best = -1.f;
                     for (int k = 0; k < p.ncenter; ++k) {
-                        const float val = (expf(r2[k] - mx) / den) / p.expq[(size_t)frame * p.ncenter + k];
+                        const float val = (expf(r2[k] - mx) / den) / p.expq[(size_t)(frame - p.frame0) * p.ncenter + k];
                         if (val > best) { best = val; idx = k; }
                     }
                 }
                 const float mu = r2[p.ncenter + idx * p.ndim + tid];
                 const float sigma = expf(-r2[p.ncenter + p.ncenter * p.ndim + idx * p.ndim + tid]) * p.sigma_scale;
-                const float nz = p.noise ? p.noise[(size_t)frame * p.ndim + tid] : 0.f;
+                const float nz = p.noise ? p.noise[(size_t)(frame - p.frame0) * p.ndim + tid] : 0.f;
                 v = nz * sigma + mu;
             }
-            p.out[(size_t)frame * p.ndim + tid] = v;
+            p.out[(size_t)(frame - p.frame0) * p.ndim + tid] = v;
             inb[tid] = v;                                // history_headpose <- cat(history[1:], pred), :186
         }
         __syncthreads();
+    }
+    if (p.state_out) {                                   // every step ended on a barrier: the queues and inb are final
+        for (int i = tid; i < qrows * RC; i += NT) p.state_out[i] = queue[i];
+        if (tid < 16) p.state_out[qrows * RC + tid] = inb[tid];
+        if (tid == 0) p.state_out[qrows * RC + 16] = __int_as_float(nsteps);
     }
 }
 
@@ -839,6 +860,7 @@ static int generate_impl(lspa2h_handle *h, const float *audio_dev, int n_audio, 
     p.proj = proj; p.pre = pre_dev; p.noise = noise_dev; p.expq = expq_dev; p.out = out_dev;
     p.layers = L; p.ndim = h->cfg.ndim; p.ncenter = h->cfg.ncenter; p.nout = h->nout; p.loss = h->cfg.loss;
     p.field = h->field; p.nframe = nframe; p.frame_future = frame_future; p.sigma_scale = sigma_scale;
+    p.frame0 = 0; p.ring = (int)rows; p.state_in = nullptr; p.state_out = nullptr;
     for (int l = 0; l < L; ++l) { p.dil[l] = h->dil[l]; p.qoff[l] = h->qoff[l]; }
     const bool single = (h->cfg.flags & LSPA2H_FLAG_SINGLE_WORKGROUP) != 0;
     char *tail = reinterpret_cast<char *>(proj + align64(rows * (size_t)L * 256));
@@ -879,6 +901,69 @@ static int generate_impl(lspa2h_handle *h, const float *audio_dev, int n_audio, 
         return e == hipSuccess ? LSPA2H_OK : hipfail(e, "a2h_pipe launch");
     }
 single_workgroup:
+    const size_t lds = (size_t)(RC * 3 + SC + 2 * MAX_OUT + 16 + (size_t)h->qrows * RC) * sizeof(float);
+    if (!h->attr_done) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&a2h_stream),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return hipfail(e, "hipFuncSetAttribute(a2h_stream)");
+        h->attr_done = true;
+    }
+    hipLaunchKernelGGL(a2h_stream, dim3(1), dim3(NT), lds, s, p);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LSPA2H_OK : hipfail(e, "a2h_stream launch");
+}
+
+size_t lspa2h_state_bytes(const lspa2h_handle *h) { return h ? ((size_t)h->qrows * RC + 16 + 4) * sizeof(float) : 0; }
+
+int lspa2h_generate_resume(lspa2h_handle *h, const float *audio_dev, int row0, int n_new, const float *pre_dev, const float *noise_dev,
+                           const float *expq_dev, float sigma_scale, int frame_future, int frame0, int nframe, const void *state_in,
+                           void *state_out, float *out_dev, void *stream)
+{
+    if (!h || !out_dev || (n_new > 0 && !audio_dev) || (!state_in && !pre_dev)) return fail(LSPA2H_ERR_INVALID_ARGUMENT, "null argument");
+    if (!h->blob) return fail(LSPA2H_ERR_STATE, "weights not bound (lspa2h_bind_weights)");
+    if (!h->ws) return fail(LSPA2H_ERR_STATE, "workspace not bound (lspa2h_bind_workspace)");
+    if (state_in && state_in == state_out)
+        return fail(LSPA2H_ERR_INVALID_ARGUMENT, "state_in and state_out must be separate buffers (a retried call restarts from state_in)");
+    if (!state_in && frame0 != 0) return fail(LSPA2H_ERR_INVALID_ARGUMENT, "a call without state_in starts the clip: frame0 must be 0");
+    const int R = h->cfg.max_audio_frames;
+    if (row0 < 0 || n_new < 0 || n_new > R || frame0 < 0 || nframe < 1 || frame_future < 0)
+        return fail(LSPA2H_ERR_SHAPE, "need row0, frame0, frame_future >= 0, 0 <= n_new <= max_audio_frames, nframe >= 1");
+    const long long known = (long long)row0 + n_new;                        // audio rows of the stream projected so far
+    const long long lo = state_in ? (long long)frame0 + frame_future : 0, hi = (long long)frame0 + nframe - 1 + frame_future;
+    if (hi >= known) return fail(LSPA2H_ERR_SHAPE, "frame frame0+nframe-1 needs audio row frame0+nframe-1+frame_future: not passed yet");
+    if (lo < known - R) return fail(LSPA2H_ERR_SHAPE, "an audio row this call reads has left the projection ring (max_audio_frames rows)");
+    if (h->cfg.loss == LSPA2H_LOSS_GMM && h->cfg.ncenter > 1 && !expq_dev)
+        return fail(LSPA2H_ERR_INVALID_ARGUMENT, "expq_dev is required when ncenter > 1");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int H = h->cfg.hidden_size, L = h->layers;
+    const size_t rows = (size_t)R;
+    float *hid = h->ws, *cond = hid + align64(rows * H), *proj = cond + align64(rows * H);
+    const float *b = h->blob;
+    int rc;
+    if (n_new > 0) {   // the new rows only: downsample MLP, then the cond projections into ring rows row % R (split at the wrap)
+        if ((rc = launch_gemm(audio_dev, b + h->o_mlp0_w, b + h->o_mlp0_scale, b + h->o_mlp0_shift, hid, n_new, H, 2 * H, 1, s))) return rc;
+        if ((rc = launch_gemm(hid, b + h->o_mlp1_w, nullptr, b + h->o_mlp1_b, cond, n_new, H, H, 0, s))) return rc;
+        const int slot = row0 % R, first = n_new < R - slot ? n_new : R - slot;
+        if ((rc = launch_gemm(cond, b + h->o_proj_w, nullptr, b + h->o_proj_b, proj + (size_t)slot * L * 256, first, L * 256, H, 0, s))) return rc;
+        if (first < n_new &&
+            (rc = launch_gemm(cond + (size_t)first * H, b + h->o_proj_w, nullptr, b + h->o_proj_b, proj, n_new - first, L * 256, H, 0, s))) return rc;
+    }
+    StreamParams p{};
+    p.start1_w = b + h->o_start1_w; p.start1_b = b + h->o_start1_b;
+    p.blob = b; p.blob_bytes = (unsigned)(h->blob_floats * sizeof(float));
+    p.start2_w = (unsigned)(h->o_start2_w * 4); p.start2_b = b + h->o_start2_b;
+    p.fg_w = (unsigned)(h->o_fg_w * 4); p.rs_w = (unsigned)(h->o_rs_w * 4); p.rs_b = b + h->o_rs_b;
+    p.end1_w = (unsigned)(h->o_end1_w * 4); p.end1_b = b + h->o_end1_b;
+    p.end2_w = b + h->o_end2_w; p.end2_b = b + h->o_end2_b;
+    p.proj = proj; p.pre = pre_dev; p.noise = noise_dev; p.expq = expq_dev; p.out = out_dev;
+    p.layers = L; p.ndim = h->cfg.ndim; p.ncenter = h->cfg.ncenter; p.nout = h->nout; p.loss = h->cfg.loss;
+    p.field = h->field; p.nframe = nframe; p.frame_future = frame_future; p.sigma_scale = sigma_scale;
+    p.frame0 = frame0; p.ring = R;
+    p.state_in = static_cast<const float *>(state_in); p.state_out = static_cast<float *>(state_out);
+    for (int l = 0; l < L; ++l) { p.dil[l] = h->dil[l]; p.qoff[l] = h->qoff[l]; }
+    char *tail = reinterpret_cast<char *>(proj + align64(rows * (size_t)L * 256));
+    p.status = reinterpret_cast<unsigned *>(tail + h->xbox_bytes() + h->sbox_bytes());
+    if (hipMemsetAsync(p.status, 0, 64, s) != hipSuccess) return fail(LSPA2H_ERR_HIP, "hipMemsetAsync(status)");
     const size_t lds = (size_t)(RC * 3 + SC + 2 * MAX_OUT + 16 + (size_t)h->qrows * RC) * sizeof(float);
     if (!h->attr_done) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&a2h_stream),

@@ -23,17 +23,18 @@ constexpr int KM = 260;        // 257 bins, padded
 constexpr int PAD = 189;       // (n_fft - hop) / 2
 constexpr int OFF = 123;       // (n_fft - win_length) / 2: where torch.stft centres the window in the frame
 
-__global__ __launch_bounds__(256) void mel_gather(const float *audio, long long nsamples, int nwin, float *A)
+// windows win0 .. win0+nwin-1 of the stream; audio[j] is stream sample first + j, j < navail
+__global__ __launch_bounds__(256) void mel_gather(const float *audio, long long first, long long navail, long long win0, int nwin, float *A)
 {
     const int i = blockIdx.x, n = threadIdx.x + blockIdx.y * 256;
     if (i >= nwin || n >= KA) return;
     float v = 0.f;
     if (n < LSPMEL_WIN) {
-        const long long st = (long long)((double)i * (16000.0 * (0.5 / 60)));      // int(i * mel_frame_step), same double product
+        const long long st = (long long)((double)(win0 + i) * (16000.0 * (0.5 / 60)));   // int(i * mel_frame_step), same double product
         int k = n + OFF - PAD;                                                       // index into the 266-sample clip
         k = k < 0 ? -k : k;                                                          // reflect (no edge repeat); the right edge is never reached
-        const long long s = st + k;
-        v = s < nsamples ? audio[s] : 0.f;                                           // zero padding of a short last clip (utils.py:76-77)
+        const long long s = st + k - first;
+        v = s < navail ? audio[s] : 0.f;                                             // zero padding of a short last clip (utils.py:76-77)
     }
     A[(size_t)i * KA + n] = v;
 }
@@ -138,18 +139,19 @@ size_t lspmel_workspace_bytes(int nwindows)
     return align256((size_t)nwindows * KA * 4) + align256((size_t)nwindows * 2 * NB * 4) + align256((size_t)nwindows * KM * 4);
 }
 
-int lspmel_compute(const float *audio_dev, int64_t nsamples, const float *basis_dev, int nwindows, float *mel_dev,
-                   void *workspace_dev, size_t workspace_bytes, void *hip_stream)
+}  // extern "C"
+
+// windows [win0, win0 + nwindows) from stream samples [first, first + navail) in audio_dev
+static int compute(const float *audio_dev, long long first, long long navail, long long win0, const float *basis_dev, int nwindows,
+                   float *mel_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream)
 {
-    if (!audio_dev || !basis_dev || !mel_dev || !workspace_dev) return fail(LSPMEL_ERR_INVALID_ARGUMENT, "null argument");
-    if (nwindows < 1 || nwindows != lspmel_num_windows(nsamples)) return fail(LSPMEL_ERR_SHAPE, "nwindows must equal lspmel_num_windows(nsamples) and be >= 1");
     if (workspace_bytes < lspmel_workspace_bytes(nwindows)) return fail(LSPMEL_ERR_SHAPE, "workspace smaller than lspmel_workspace_bytes()");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     char *w = static_cast<char *>(workspace_dev);
     float *A = reinterpret_cast<float *>(w);
     float *C = reinterpret_cast<float *>(w + align256((size_t)nwindows * KA * 4));
     float *mag = reinterpret_cast<float *>(w + align256((size_t)nwindows * KA * 4) + align256((size_t)nwindows * 2 * NB * 4));
-    hipLaunchKernelGGL(mel_gather, dim3(nwindows, (KA + 255) / 256), dim3(256), 0, s, audio_dev, (long long)nsamples, nwindows, A);
+    hipLaunchKernelGGL(mel_gather, dim3(nwindows, (KA + 255) / 256), dim3(256), 0, s, audio_dev, first, navail, win0, nwindows, A);
     lspgemm::GemmParams g1{A, basis_dev, nullptr, nullptr, nullptr, C, nwindows, 2 * NB, KA, 1.0f, 0};
     hipError_t e = lspgemm::launch_gemm_f32(g1, s);
     if (e != hipSuccess) return fail(LSPMEL_ERR_HIP, std::string("DFT gemm launch: ") + hipGetErrorString(e));
@@ -160,6 +162,32 @@ int lspmel_compute(const float *audio_dev, int64_t nsamples, const float *basis_
     hipLaunchKernelGGL(mel_log, dim3((nwindows * LSPMEL_N_MELS + 255) / 256), dim3(256), 0, s, mel_dev, nwindows * LSPMEL_N_MELS);
     e = hipGetLastError();
     return e == hipSuccess ? LSPMEL_OK : fail(LSPMEL_ERR_HIP, std::string("mel kernels: ") + hipGetErrorString(e));
+}
+
+extern "C" {
+
+int lspmel_compute(const float *audio_dev, int64_t nsamples, const float *basis_dev, int nwindows, float *mel_dev,
+                   void *workspace_dev, size_t workspace_bytes, void *hip_stream)
+{
+    if (!audio_dev || !basis_dev || !mel_dev || !workspace_dev) return fail(LSPMEL_ERR_INVALID_ARGUMENT, "null argument");
+    if (nwindows < 1 || nwindows != lspmel_num_windows(nsamples)) return fail(LSPMEL_ERR_SHAPE, "nwindows must equal lspmel_num_windows(nsamples) and be >= 1");
+    return compute(audio_dev, 0, nsamples, 0, basis_dev, nwindows, mel_dev, workspace_dev, workspace_bytes, hip_stream);
+}
+
+int64_t lspmel_window_start(int64_t window) { return window < 0 ? -1 : (int64_t)((double)window * (16000.0 * (0.5 / 60))); }
+
+int lspmel_compute_range(const float *audio_dev, int64_t first_sample, int64_t navail, int ended, int64_t win0, int nwin,
+                         const float *basis_dev, float *mel_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream)
+{
+    if (!audio_dev || !basis_dev || !mel_dev || !workspace_dev) return fail(LSPMEL_ERR_INVALID_ARGUMENT, "null argument");
+    if (nwin < 1 || win0 < 0 || first_sample < 0 || navail < 0) return fail(LSPMEL_ERR_SHAPE, "need nwin >= 1 and win0, first_sample, navail >= 0");
+    if (lspmel_window_start(win0) < first_sample) return fail(LSPMEL_ERR_SHAPE, "window win0 starts before first_sample");
+    const int64_t end = lspmel_window_start(win0 + nwin - 1) + LSPMEL_WIN;            // one past the last sample of the last window's clip
+    if (!ended && end > first_sample + navail)
+        return fail(LSPMEL_ERR_SHAPE, "the last window reaches past the samples passed and the clip has not ended (no zero padding before the end)");
+    if (ended && win0 + nwin > lspmel_num_windows(first_sample + navail))
+        return fail(LSPMEL_ERR_SHAPE, "window past the last one of the clip (lspmel_num_windows of its length)");
+    return compute(audio_dev, first_sample, navail, win0, basis_dev, nwin, mel_dev, workspace_dev, workspace_bytes, hip_stream);
 }
 
 }  // extern "C"

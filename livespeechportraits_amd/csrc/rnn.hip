@@ -36,6 +36,8 @@ struct LayerParams {
     float *hseq;                   // [T][H] output of this layer
     unsigned long long *hbox;      // [T][H] granules
     unsigned *status;
+    const float *h0, *c0;          // this layer's initial h / c [H], or null (zeros)
+    float *hN, *cN;                // this layer's final h / c [H], or null (not written)
     unsigned epoch;
     int T, H, stride;
 };
@@ -79,6 +81,10 @@ template <int GATES, int P> __global__ __launch_bounds__(NT) void rnn_layer(Laye
             blob, tid * 16, (int)(p.whh + ((unsigned)wg * GATES * 8 + (unsigned)i) * NT * 16u), 0));
     const float bhn = (GATES == 3 && part == 0) ? p.bhn[unit] : 0.f;
     float hprev = 0.f, cprev = 0.f;                       // leader lanes: own unit's state
+    if (part == 0) {
+        if (p.h0) hprev = p.h0[unit];
+        if (GATES == 4 && p.c0) cprev = p.c0[unit];
+    }
     for (int t = 0; t < p.T; ++t) {
         float xg[GATES];
         if (part == 0) {
@@ -87,7 +93,7 @@ template <int GATES, int P> __global__ __launch_bounds__(NT) void rnn_layer(Laye
         }
         bool ok = true;
         if (t == 0) {
-            if (tid < H) hbuf[tid] = 0.f;                   // zero initial state
+            if (tid < H) hbuf[tid] = p.h0 ? p.h0[tid] : 0.f;   // initial state (zero unless carried in)
         } else if (tid < H) {
             const int slot = (int)((unsigned)(t - 1) * (unsigned)H * 8u);
             for (unsigned spins = 0;;) {
@@ -134,6 +140,10 @@ template <int GATES, int P> __global__ __launch_bounds__(NT) void rnn_layer(Laye
             if (t + 1 < p.T)
                 __builtin_amdgcn_raw_buffer_store_b64(gr, box, unit * 8, (int)((unsigned)t * (unsigned)H * 8u), AUX_SC1);
             p.hseq[(size_t)t * H + unit] = hn;
+            if (t + 1 == p.T) {
+                if (p.hN) p.hN[unit] = hn;
+                if (GATES == 4 && p.cN) p.cN[unit] = cprev;
+            }
         }
         __syncthreads();
     }
@@ -154,6 +164,8 @@ struct WaveParams {
     float *out;                    // [T][H] top layer
     unsigned long long *hbox;      // [layers][T][H] granules
     unsigned *status;
+    const float *state_in;         // null, or h [layers][H] (then, LSTM, c [layers][H]): the initial state
+    float *state_out;              // null, or the final state, same layout
     unsigned epoch;
     int T, H, layers, wgs_per_layer, stride;
 };
@@ -188,6 +200,11 @@ template <int GATES, int P, int CPP> __global__ __launch_bounds__(NT) void rnn_w
     const float bhn = (GATES == 3 && part == 0) ? p.bhn[l][unit] : 0.f;
     const bool top = l + 1 == p.layers;
     float hprev = 0.f, cprev = 0.f;
+    const float *h0 = p.state_in ? p.state_in + (size_t)l * H : nullptr;
+    if (part == 0 && p.state_in) {
+        hprev = h0[unit];
+        if (GATES == 4) cprev = p.state_in[(size_t)(p.layers + l) * H + unit];
+    }
     for (int t = 0; t < p.T; ++t) {
         float xg[GATES];
 #pragma unroll
@@ -200,7 +217,7 @@ template <int GATES, int P, int CPP> __global__ __launch_bounds__(NT) void rnn_w
         // two polls per thread at most: own layer's h_{t-1} (slot t-1), the layer below's h_t (slot t)
         for (int which = 0; which < 2 && ok; ++which) {
             float *dst = which ? hlow : hown;
-            if (which == 0 && t == 0) { if (tid < H) dst[tid] = 0.f; continue; }
+            if (which == 0 && t == 0) { if (tid < H) dst[tid] = h0 ? h0[tid] : 0.f; continue; }
             if (which == 1 && l == 0) continue;
             if (tid < H) {
                 const int slot = (int)((unsigned)(which ? l - 1 : l) * plane + (unsigned)(which ? t : t - 1) * (unsigned)H * 8u);
@@ -260,6 +277,10 @@ template <int GATES, int P, int CPP> __global__ __launch_bounds__(NT) void rnn_w
             if (t + 1 < p.T || !top)          // consumers: this layer's next step, and the layer above at this step
                 __builtin_amdgcn_raw_buffer_store_b64(gr, box, unit * 8, (int)((unsigned)l * plane + (unsigned)t * (unsigned)H * 8u), AUX_SC1);
             if (top) p.out[(size_t)t * H + unit] = hn;
+            if (t + 1 == p.T && p.state_out) {
+                p.state_out[(size_t)l * H + unit] = hn;
+                if (GATES == 4) p.state_out[(size_t)(p.layers + l) * H + unit] = cprev;
+            }
         }
         __syncthreads();
     }
@@ -446,9 +467,23 @@ int lsprnn_bind_workspace(lsprnn_handle *h, void *workspace_dev, size_t bytes)
     return LSPRNN_OK;
 }
 
+size_t lsprnn_state_floats(const lsprnn_handle *h)
+{
+    if (!h) return 0;
+    return (size_t)(h->gates == 4 ? 2 : 1) * h->cfg.num_layers * h->cfg.hidden_size;
+}
+
 int lsprnn_forward(lsprnn_handle *h, const float *x_dev, int T, float *out_dev, void *stream)
 {
+    return lsprnn_forward_state(h, x_dev, T, out_dev, nullptr, nullptr, stream);
+}
+
+int lsprnn_forward_state(lsprnn_handle *h, const float *x_dev, int T, float *out_dev, const float *state_in_dev, float *state_out_dev,
+                         void *stream)
+{
     if (!h || !x_dev || !out_dev) return fail(LSPRNN_ERR_INVALID_ARGUMENT, "null argument");
+    if (state_in_dev && state_in_dev == state_out_dev)
+        return fail(LSPRNN_ERR_INVALID_ARGUMENT, "state_in and state_out must be separate buffers (a retried call restarts from state_in)");
     if (!h->blob) return fail(LSPRNN_ERR_STATE, "weights not bound (lsprnn_bind_weights)");
     if (!h->ws) return fail(LSPRNN_ERR_STATE, "workspace not bound (lsprnn_bind_workspace)");
     if (T < 1 || T > h->cfg.max_steps) return fail(LSPRNN_ERR_SHAPE, "T out of range (max_steps)");
@@ -492,6 +527,7 @@ int lsprnn_forward(lsprnn_handle *h, const float *x_dev, int T, float *out_dev, 
             p.bias[l] = h->blob + h->o_bias[l]; p.bhn[l] = h->blob + h->o_bhn[l];
         }
         p.xproj = xproj; p.out = out_dev; p.hbox = box; p.status = status; p.epoch = h->epoch;
+        p.state_in = state_in_dev; p.state_out = state_out_dev;
         p.T = T; p.H = H; p.layers = L; p.wgs_per_layer = h->Gw;
         // workgroup b runs on XCD b % 8 (observed, speed only): keep the stack on as few XCDs as its size allows
         const int nwg = L * h->Gw;
@@ -513,6 +549,11 @@ int lsprnn_forward(lsprnn_handle *h, const float *x_dev, int T, float *out_dev, 
         p.blob = h->blob; p.blob_bytes = (unsigned)(h->blob_floats * sizeof(float));
         p.whh = (unsigned)(h->o_whh[l] * sizeof(float)); p.bhn = h->blob + h->o_bhn[l];
         p.xproj = xproj; p.hseq = hseq; p.hbox = box; p.status = status; p.epoch = h->epoch;
+        const size_t cplane = (size_t)L * H;            // LSTM: the c block follows the h block
+        p.h0 = state_in_dev ? state_in_dev + (size_t)l * H : nullptr;
+        p.c0 = state_in_dev && GT == 4 ? state_in_dev + cplane + (size_t)l * H : nullptr;
+        p.hN = state_out_dev ? state_out_dev + (size_t)l * H : nullptr;
+        p.cN = state_out_dev && GT == 4 ? state_out_dev + cplane + (size_t)l * H : nullptr;
         p.T = T; p.H = H;
         p.stride = 8;           // every 8th block: the whole all-gather sits behind one XCD's L2 (speed only, see csrc/a2h.hip)
         const dim3 grid(h->G * p.stride), block(NT);

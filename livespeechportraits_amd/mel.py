@@ -47,6 +47,27 @@ def compute_mel(audio: torch.Tensor, out: Optional[torch.Tensor] = None) -> torc
     return mel
 
 
+def compute_mel_range(samples: torch.Tensor, first_sample: int, win0: int, nwin: int, ended: bool,
+                      out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Windows [win0, win0 + nwin) of a stream whose samples [first_sample, first_sample + len(samples)) are in ``samples`` (float32,
+    1-d, on the device) -> [nwin, 80], bit for bit the matching rows of compute_mel over the whole clip.  ``ended``: the clip ends after
+    these samples (only then is a window zero padded past them); include/lspmel.h lspmel_compute_range."""
+    if samples.device.type != "cuda" or samples.dim() != 1 or samples.dtype != torch.float32 or not samples.is_contiguous():
+        raise ValueError("samples must be a contiguous 1-d float32 device tensor (there is no CPU path)")
+    lib = N.load()
+    dev = samples.device
+    mel = out if out is not None else torch.empty((nwin, 80), dtype=torch.float32, device=dev)
+    if tuple(mel.shape) != (nwin, 80) or not mel.is_contiguous() or mel.device != dev:
+        raise ValueError("out must be a contiguous [%d, 80] tensor on %s" % (nwin, dev))
+    need = int(lib.lspmel_workspace_bytes(nwin))
+    ws = workspace if workspace is not None and workspace.numel() >= need else torch.empty(need, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        N.check_mel(lib.lspmel_compute_range(samples.data_ptr(), int(first_sample), samples.shape[0], int(bool(ended)), int(win0), int(nwin),
+                                             _basis_on(dev).data_ptr(), mel.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return mel
+
+
 def compute_mel_one_sequence(audio, hop_length=int(16000 / 120), winlen=1 / 60, winstep=0.5 / 60, sr=16000, fps=60, device="cuda:0"):
     """Same signature and return type as the reference function: numpy float64 [mel_nframe, 80].  Only the parameter set the
     reference itself uses is supported (it hard-codes them into Audio2Mel as well)."""

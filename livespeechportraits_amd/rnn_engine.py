@@ -96,6 +96,31 @@ class RecurrentEngine:
             torch.cuda.synchronize(x.device)
         raise RuntimeError("recurrent kernel: inter-workgroup hand-off timed out %d times in a row (status %d)" % (retries + 1, code))
 
+    def state_floats(self) -> int:
+        """Floats of a carried state: GRU h [L][H]; LSTM h [L][H] then c [L][H] (PyTorch's h_n / (h_n, c_n))."""
+        return int(self.lib.lsprnn_state_floats(self.h))
+
+    def forward_state(self, x: torch.Tensor, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor],
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """forward() from ``state_in`` (None: zeros), writing the final state to ``state_out`` (None: not written).
+        The two must be separate buffers; asynchronous on the current stream."""
+        if self.blob is None:
+            raise RuntimeError("RecurrentEngine.bind(device) first")
+        _require("x", x)
+        if x.dim() != 2 or x.shape[1] != self.input_size:
+            raise ValueError("x must be [T, %d]" % self.input_size)
+        for name, t in (("state_in", state_in), ("state_out", state_out)):
+            if t is not None:
+                _require(name, t)
+                if t.numel() != self.state_floats():
+                    raise ValueError("%s must hold %d floats" % (name, self.state_floats()))
+        if out is None:
+            out = torch.empty((x.shape[0], self.hidden_size), dtype=torch.float32, device=x.device)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(x.device):
+            N.check_rnn(self.lib.lsprnn_forward_state(self.h, ptr(x), x.shape[0], ptr(out), ptr(state_in), ptr(state_out), _stream(x.device)))
+        return out
+
     def status(self) -> int:
         code = ctypes.c_uint32()
         dev = self.blob.device
