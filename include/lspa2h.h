@@ -117,6 +117,39 @@ int lspa2h_generate_resume(lspa2h_handle *h, const float *audio_dev, int row0, i
                            const float *expq_dev, float sigma_scale, int frame_future, int frame0, int nframe, const void *state_in,
                            void *state_out, float *out_dev, void *stream);
 
+/* The same for several streams per call (several live sessions advanced together), in STEP ranges: a stream's steps 0 .. field-2 (field =
+ * lspa2h_receptive_field) fill the first receptive field and emit nothing, step field-1+f emits frame f; step s reads audio row
+ * max(0, s + frame_future - (field-1)).  A call runs steps [step0, step1) of each stream, so the field-1 priming steps that
+ * lspa2h_generate_resume runs in one go before frame 0 can be spread over many calls.  The carried state is that of lspa2h_generate_resume
+ * (its counter = the next step; checked on the device against step0, status 0x5000000, that stream's outputs untouched), so a state written
+ * by either entry point continues under the other, bit for bit.
+ *   audio_dev                          the new audio rows of all streams, one stream after the other: [sum n_new][2*hidden_size]
+ *   row0, n_new                        this stream's rows row0 .. row0+n_new-1 (n_new may be 0); their cond projections go to the ring
+ *                                      (max_audio_frames rows) of workspace slot `slot`; a stream keeps its slot for its whole life
+ *   step0, step1                       step1 == step0: new rows only, no state is read or written
+ *   state_in                           NULL iff step0 == 0 (start of the clip: queues zero, input = pre_dev)
+ *   noise_dev / expq_dev / out_dev     rows of the frames THIS call emits, [max(step0-(field-1), 0), step1-(field-1)); may be NULL while
+ *                                      no frame is emitted (expq_dev: required iff ncenter > 1, noise_dev NULL = zeros)
+ * Every row a step range reads must lie in [row0 + n_new - max_audio_frames, row0 + n_new); no buffer may be one stream's state_out and any
+ * stream's state_in; refusals name the stream's index.  All streams' new rows go through each downsample / projection GEMM in one launch
+ * (the projections reach the rings through one copy launch), and ONE launch of one workgroup per stream runs the steps: the launch count
+ * does not depend on nstreams.  The several-streams workspace is separate from lspa2h_bind_workspace's and has a status word of its own. */
+#define LSPA2H_MAX_STREAMS 16
+typedef struct lspa2h_stream_call {
+    int32_t slot;
+    int32_t row0, n_new;
+    int32_t step0, step1;
+    const float *pre_dev, *noise_dev, *expq_dev;
+    const void *state_in;
+    void *state_out;
+    float *out_dev;
+} lspa2h_stream_call;
+size_t lspa2h_workspace_bytes_multi(const lspa2h_handle *h, int max_streams);
+int lspa2h_bind_workspace_multi(lspa2h_handle *h, void *workspace_dev, size_t bytes, int max_streams);
+int lspa2h_generate_resume_multi(lspa2h_handle *h, int nstreams, const lspa2h_stream_call *calls, const float *audio_dev, float sigma_scale,
+                                 int frame_future, void *stream);
+int lspa2h_status_multi(lspa2h_handle *h, void *stream, uint32_t *code);
+
 /* Waits for `stream` and reports whether the last lspa2h_generate completed: *code == 0, or the identifier of the
  * first inter-workgroup hand-off that timed out (the kernel never spins unbounded; output rows are then undefined). */
 int lspa2h_status(lspa2h_handle *h, void *stream, uint32_t *code);

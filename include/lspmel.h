@@ -63,6 +63,16 @@ int64_t lspmel_window_start(int64_t window);
 int lspmel_compute_range(const float *audio_dev, int64_t first_sample, int64_t navail, int ended, int64_t win0, int nwin,
                          const float *basis_dev, float *mel_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream);
 
+/* The same for windows of several buffers in one call (several live streams advanced together): segment k (0 <= k < nseg <=
+ * LSPMEL_MAX_SEGMENTS) is what lspmel_compute_range takes for one stream -- audio_dev[k] (device pointer; the arrays themselves are host
+ * memory), first_sample[k], navail[k], ended[k], win0[k], nwin[k] -- and the refusals of lspmel_compute_range apply per segment, with its
+ * index in the message.  mel_dev receives the rows of segment 0, then segment 1, ...: sum nwin rows, each bit for bit the row
+ * lspmel_compute_range gives for that window; workspace >= lspmel_workspace_bytes(sum nwin).  One gather launch, whatever nseg is. */
+#define LSPMEL_MAX_SEGMENTS 16
+int lspmel_compute_ranges(int nseg, const float *const *audio_dev, const int64_t *first_sample, const int64_t *navail, const int *ended,
+                          const int64_t *win0, const int *nwin, const float *basis_dev, float *mel_dev, void *workspace_dev,
+                          size_t workspace_bytes, void *hip_stream);
+
 const char *lspmel_last_error(void);
 
 #pragma GCC visibility pop

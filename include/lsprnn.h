@@ -84,6 +84,19 @@ size_t lsprnn_state_floats(const lsprnn_handle *h);
 int lsprnn_forward_state(lsprnn_handle *h, const float *x_dev, int T, float *out_dev, const float *state_in_dev, float *state_out_dev,
                          void *stream);
 
+/* Up to LSPRNN_MAX_SEQUENCES independent sequences in one call (several live streams advanced together): one input-projection GEMM over
+ * all rows and ONE recurrence launch (per layer on the per-layer route), whatever nseq is.  x_dev holds the sequences' inputs one after
+ * another, [sum T[s]][input_size], out_dev likewise [sum T[s]][hidden_size]; T (host array) may be ragged, T[s] == 0 leaves sequence s
+ * untouched, its state_out included.  state_in_dev / state_out_dev are host arrays of nseq device pointers in lsprnn_forward_state's layout
+ * (either array, or any entry, may be NULL: zeros / not written).  No buffer may be a state_out and any sequence's state_in at once, and
+ * no two sequences may share a state_out.  The sequences share the workspace: sum T[s] <= max_steps.  Each sequence's outputs and final
+ * state are bit for bit those of lsprnn_forward_state alone on the same input and state: the weights a thread holds serve one sequence
+ * after the other, with the products, their order and the reductions of the single-sequence kernels.  lsprnn_status covers the call (one
+ * word; bits 26..29 name the sequence whose hand-off timed out). */
+#define LSPRNN_MAX_SEQUENCES 16
+int lsprnn_forward_multi(lsprnn_handle *h, int nseq, const float *x_dev, const int *T, float *out_dev, const float *const *state_in_dev,
+                         float *const *state_out_dev, void *stream);
+
 /* Waits for `stream`; *code == 0 if the last forward completed, else the hand-off that timed out (bounded polls). */
 int lsprnn_status(lsprnn_handle *h, void *stream, uint32_t *code);
 

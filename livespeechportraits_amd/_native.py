@@ -150,6 +150,18 @@ SIGNATURES = {
 
 
 
+A2H_MAX_STREAMS = 16
+RNN_MAX_SEQUENCES = 16
+MEL_MAX_SEGMENTS = 16
+
+
+class A2HStreamCall(Structure):
+    """lspa2h_stream_call (include/lspa2h.h)"""
+    _fields_ = [("slot", c_int32), ("row0", c_int32), ("n_new", c_int32), ("step0", c_int32), ("step1", c_int32),
+                ("pre_dev", c_void_p), ("noise_dev", c_void_p), ("expq_dev", c_void_p), ("state_in", c_void_p), ("state_out", c_void_p),
+                ("out_dev", c_void_p)]
+
+
 class A2HConfig(Structure):
     """lspa2h_config (include/lspa2h.h)"""
     _fields_ = [(n, c_int32) for n in ("abi_version", "residual_layers", "residual_blocks", "residual_channels",
@@ -185,6 +197,10 @@ A2H_SIGNATURES = {
     "lspa2h_state_bytes": (c_size_t, [c_void_p]),
     "lspa2h_generate_resume": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lspa2h_workspace_bytes_multi": (c_size_t, [c_void_p, c_int]),
+    "lspa2h_bind_workspace_multi": (c_int, [c_void_p, c_void_p, c_size_t, c_int]),
+    "lspa2h_generate_resume_multi": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, c_int, c_void_p]),
+    "lspa2h_status_multi": (c_int, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "lspa2h_sample_gmm": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
 }
 
@@ -224,6 +240,7 @@ RNN_SIGNATURES = {
     "lsprnn_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "lsprnn_state_floats": (c_size_t, [c_void_p]),
     "lsprnn_forward_state": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsprnn_forward_multi": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
     "lsprnn_status": (c_int, [c_void_p, c_void_p, POINTER(c_uint32)]),
     "lsprnn_linear": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
 }
@@ -244,6 +261,8 @@ MEL_SIGNATURES = {
     "lspmel_workspace_bytes": (c_size_t, [c_int]),
     "lspmel_compute": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "lspmel_window_start": (c_int64, [c_int64]),
+    "lspmel_compute_ranges": (c_int, [c_int, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), POINTER(c_int), POINTER(c_int64), POINTER(c_int),
+                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "lspmel_compute_range": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 

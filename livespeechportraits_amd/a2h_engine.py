@@ -171,6 +171,81 @@ class HeadposeEngine:
                                                         ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return out
 
+    # ---- several streams per call -------------------------------------------------------------
+    def bind_multi(self, max_streams: int) -> None:
+        """The several-streams workspace (one projection ring of ``max_audio_frames`` rows per stream); after bind()."""
+        if self.blob is None:
+            raise RuntimeError("HeadposeEngine.bind(device) first")
+        nbytes = int(self.lib.lspa2h_workspace_bytes_multi(self.h, int(max_streams)))
+        if nbytes == 0:
+            raise ValueError("max_streams must be in 1..%d" % N.A2H_MAX_STREAMS)
+        self.mws = torch.empty(nbytes, dtype=torch.uint8, device=self.blob.device)
+        N.check_a2h(self.lib.lspa2h_bind_workspace_multi(self.h, ctypes.c_void_p(self.mws.data_ptr()), self.mws.numel(), int(max_streams)))
+        self.max_streams = int(max_streams)
+
+    def generate_resume_multi(self, streams, audio: Optional[torch.Tensor], sigma_scale: float, frame_future: int):
+        """Steps of several streams in one call (include/lspa2h.h lspa2h_generate_resume_multi).  ``streams``: 1..16 dicts with
+        slot, row0, n_new, step0, step1 and optionally pre, noise, expq, state_in, state_out, out; ``audio`` the new rows of all streams
+        one after another ([sum n_new, 2 * hidden_size], or None).  Step field - 1 + f emits frame f; a stream's ``out`` (allocated here
+        unless given) has one row per frame its range emits.  -> the list of the streams' out tensors.  Asynchronous."""
+        if getattr(self, "mws", None) is None:
+            raise RuntimeError("HeadposeEngine.bind_multi(max_streams) first")
+        dev = self.blob.device
+        streams = list(streams)
+        n = len(streams)
+        if not 1 <= n <= self.max_streams:
+            raise ValueError("need 1..%d streams, got %d" % (self.max_streams, n))
+        total = sum(int(st.get("n_new", 0)) for st in streams)
+        if audio is not None:
+            if not audio.is_cuda or audio.dtype != torch.float32 or not audio.is_contiguous() or audio.dim() != 2 or \
+                    audio.shape[1] != 2 * self.hidden_size:
+                raise ValueError("audio must be a contiguous float32 device tensor [n, %d]" % (2 * self.hidden_size))
+        if (audio.shape[0] if audio is not None else 0) != total:
+            raise ValueError("audio must hold the sum of the streams' n_new rows (%d)" % total)
+        calls = (N.A2HStreamCall * n)()
+        outs = []
+        F1 = self.receptive_field - 1
+        for k, st in enumerate(streams):
+            step0, step1 = int(st["step0"]), int(st["step1"])
+            nf = max(step1 - F1, 0) - max(step0 - F1, 0)
+            for name in ("pre", "noise", "expq", "out"):
+                t = st.get(name)
+                if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
+                    raise ValueError("stream %d: %s must be a contiguous float32 device tensor (there is no CPU path)" % (k, name))
+            for name in ("state_in", "state_out"):
+                t = st.get(name)
+                if t is not None and (not t.is_cuda or not t.is_contiguous() or t.numel() * t.element_size() != self.state_bytes()):
+                    raise ValueError("stream %d: %s must be a contiguous device buffer of %d bytes" % (k, name, self.state_bytes()))
+            for name, width in (("noise", self.ndim), ("expq", self.ncenter)):
+                t = st.get(name)
+                if t is not None and tuple(t.shape) != (nf, width):
+                    raise ValueError("stream %d: %s must be [%d, %d]" % (k, name, nf, width))
+            out = st.get("out")
+            if out is None:
+                out = torch.empty(nf, self.ndim, dtype=torch.float32, device=dev)
+            elif tuple(out.shape) != (nf, self.ndim):
+                raise ValueError("stream %d: out must be [%d, %d]" % (k, nf, self.ndim))
+            outs.append(out)
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+            c = calls[k]
+            c.slot, c.row0, c.n_new, c.step0, c.step1 = int(st["slot"]), int(st.get("row0", 0)), int(st.get("n_new", 0)), step0, step1
+            c.pre_dev, c.noise_dev, c.expq_dev = ptr(st.get("pre")), ptr(st.get("noise")), ptr(st.get("expq"))
+            c.state_in, c.state_out, c.out_dev = ptr(st.get("state_in")), ptr(st.get("state_out")), ptr(out)
+        with torch.cuda.device(dev):
+            N.check_a2h(self.lib.lspa2h_generate_resume_multi(self.h, n, calls, ctypes.c_void_p(audio.data_ptr()) if total else None,
+                                                              ctypes.c_float(sigma_scale), int(frame_future),
+                                                              ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return outs
+
+    def status_multi(self) -> int:
+        """Synchronises the current stream; 0 if the last generate_resume_multi() completed, else 0x5000000 (a carried state did not match
+        its stream's step0: that stream's outputs and state_out are untouched)."""
+        code = ctypes.c_uint32()
+        dev = self.blob.device
+        with torch.cuda.device(dev):
+            N.check_a2h(self.lib.lspa2h_status_multi(self.h, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), ctypes.byref(code)))
+        return code.value
+
     def status(self, device=None) -> int:
         """Synchronises the current stream; 0 if the last generate() completed, else the code of the hand-off that timed out."""
         code = ctypes.c_uint32()

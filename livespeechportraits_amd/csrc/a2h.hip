@@ -273,6 +273,226 @@ __global__ __launch_bounds__(NT) void a2h_stream(StreamParams p)
     }
 }
 
+// The loop of a2h_stream for steps [s0, s1) of one stream of a2h_stream_multi -- a separate instance: a2h_stream above stays the code it
+// was (sharing one body changed its register allocation).  Steps below field - 1 fill the first receptive field and emit nothing, step
+// field - 1 + f emits frame f into row f - fbase of out (noise / expq likewise); per step the instructions are a2h_stream's.
+__device__ __forceinline__ void stream_steps(const StreamParams &p, float *smem, const float *proj, const float *pre, const float *noise,
+                                             const float *expq, float *out, const float *state_in, float *state_out, int s0, const int nsteps,
+                                             const int fbase)
+{
+    float *xbuf = smem;                  // [128] current layer input
+    float *zbuf = xbuf + RC;             // [128] gated activation
+    float *tbuf = zbuf + RC;             // [128] start_conv1 output
+    float *sbuf = tbuf + RC;             // [256] lrelu(skip sum)
+    float *r1 = sbuf + SC;               // [64]  end_conv_1 output (lrelu applied)
+    float *r2 = r1 + MAX_OUT;            // [64]  end_conv_2 output
+    float *inb = r2 + MAX_OUT;           // [16]  WaveNet input of this step (head pose)
+    float *queue = inb + 16;             // [sum of dilations][128]
+    const int tid = threadIdx.x;
+
+    int qrows = 0;
+    for (int l = 0; l < p.layers; ++l) qrows += p.dil[l];
+    if (state_in) {                                  // resumed: the state saved after step s0 - 1
+        if (__float_as_int(state_in[qrows * RC + 16]) != s0) {
+            if (tid == 0) atomicCAS(p.status, 0u, 0x5000000u);    // the state belongs to another step: refuse, outputs untouched
+            return;
+        }
+        for (int i = tid; i < qrows * RC; i += NT) queue[i] = state_in[i];
+        if (tid < 16) inb[tid] = state_in[qrows * RC + tid];
+    } else {                                         // start of a clip: queues zero, input = pre
+        s0 = 0;
+        for (int i = tid; i < qrows * RC; i += NT) queue[i] = 0.f;
+        if (tid < 16) inb[tid] = tid < p.ndim ? pre[tid] : 0.f;
+    }
+
+    const int fu = tid >> 3, fpart = tid & 7;        // fg item: channels fu and fu+64, 32-column part
+    const int rq = tid >> 2, rpart = tid & 3;        // rs item: rows rq, 128+rq, 256+rq, 32-column part
+    const unsigned fg_stride = 32 * NT * 16, rs_stride = 24 * NT * 16;   // bytes per layer
+    const __amdgpu_buffer_rsrc_t blob = __builtin_amdgcn_make_buffer_rsrc((void *)p.blob, 0, (int)p.blob_bytes, 0x00020000);
+    const int voff = tid * 16;
+    const int projN = p.layers * 256;
+
+    // Weight registers.  F + R together are 87 % of the CU's register file, so the next mat-vec's weights
+    // cannot all be in flight while the current set is live: half of the next set is requested before a
+    // set is consumed, the other half as soon as its registers are free.
+    float4 F[32], R[24];
+    load_packed<0, 32>(F, blob, p.fg_w, voff);
+    __syncthreads();
+
+    for (int s = s0; s < nsteps; ++s) {
+        int arow = s + p.frame_future - (p.field - 1);
+        arow = arow < 0 ? 0 : arow;                  // the reference prepends field-1 copies of audio row 0
+        const float *projrow = proj + (size_t)(arow % p.ring) * projN;
+        // ---- start convs (networks.py:198-199): 1x1, bias, LeakyReLU
+        if (tid < RC) {
+            float a = p.start1_b[tid];
+            for (int k = 0; k < p.ndim; ++k) a = fmaf(p.start1_w[tid * p.ndim + k], inb[k], a);
+            tbuf[tid] = lrelu(a);
+        }
+        __syncthreads();
+        {
+            float4 w[8];
+            load_packed<0, 8>(w, blob, p.start2_w, voff);
+            const float4 *v = reinterpret_cast<const float4 *>(tbuf + rpart * 32);
+            float a = 0.f;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) a = dot4(w[q], v[q], a);
+            a = sum4(a);
+            if (rpart == 0) xbuf[rq] = lrelu(a + p.start2_b[rq]);
+        }
+        float skip0 = 0.f, skip1 = 0.f;              // skip rows rq and 128+rq (leader lanes)
+        __syncthreads();
+
+        for (int l = 0; l < p.layers; ++l) {
+            const int d = p.dil[l];
+            float *qslot = queue + (size_t)(p.qoff[l] + (s & (d - 1))) * RC;   // holds x[t-d]; overwritten with x[t]
+            const unsigned rsw = p.rs_w + (unsigned)l * rs_stride;
+            load_packed<0, 16>(R, blob, rsw, voff);                                    // in flight during the fg mat-vec
+            float4 pb = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (fpart == 0) pb = *reinterpret_cast<const float4 *>(projrow + l * 256 + fu * 4);
+            // ---- filter/gate dilated convs + cond (networks.py:303-314): 256 rows x [x[t-d] ; x[t]]
+            {
+                const float4 *v = reinterpret_cast<const float4 *>((fpart < 4 ? qslot + fpart * 32 : xbuf + (fpart - 4) * 32));
+                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const float4 x = v[q];
+                    a0 = dot4(F[q], x, a0); a1 = dot4(F[8 + q], x, a1); a2 = dot4(F[16 + q], x, a2); a3 = dot4(F[24 + q], x, a3);
+                }
+                asm volatile("" ::: "memory");                  // keep the late half late: its registers are not free earlier
+                load_packed<16, 24>(R, blob, rsw, voff);
+                a0 = sum8(a0); a1 = sum8(a1); a2 = sum8(a2); a3 = sum8(a3);
+                if (fpart == 0) {   // tanh(filter) * sigmoid(gate), networks.py:317-319
+                    zbuf[fu] = tanhf(a0 + pb.x) * (1.f / (1.f + expf(-(a1 + pb.y))));
+                    zbuf[fu + 64] = tanhf(a2 + pb.z) * (1.f / (1.f + expf(-(a3 + pb.w))));
+                }
+            }
+            __syncthreads();
+            // next fg weights (next layer, or layer 0 of the next step) stream in during the rs mat-vec
+            const unsigned fgw = p.fg_w + (unsigned)(l + 1 == p.layers ? 0 : l + 1) * fg_stride;
+            load_packed<0, 16>(F, blob, fgw, voff);
+            // ---- residual + skip 1x1 convs (networks.py:322-323)
+            {
+                const float4 *v = reinterpret_cast<const float4 *>(zbuf + rpart * 32);
+                float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const float4 z = v[q];
+                    a0 = dot4(R[q], z, a0); a1 = dot4(R[8 + q], z, a1); a2 = dot4(R[16 + q], z, a2);
+                }
+                asm volatile("" ::: "memory");
+                load_packed<16, 32>(F, blob, fgw, voff);
+                a0 = sum4(a0); a1 = sum4(a1); a2 = sum4(a2);
+                if (rpart == 0) {
+                    const float *b = p.rs_b + l * 384;
+                    const float x = xbuf[rq];
+                    qslot[rq] = x;                       // every reader of x[t-d] is past the barrier above
+                    xbuf[rq] = a0 + b[rq] + x;           // residual = residual_conv(x) + input
+                    skip0 += a1 + b[128 + rq];
+                    skip1 += a2 + b[256 + rq];
+                }
+            }
+            __syncthreads();
+        }
+
+        const int frame = s - (p.field - 1);
+        if (frame < 0) continue;                         // still filling the first receptive field
+        // ---- end convs (networks.py:207-208) on the summed skips
+        if (rpart == 0) { sbuf[rq] = lrelu(skip0); sbuf[128 + rq] = lrelu(skip1); }
+        __syncthreads();
+        {
+            float4 w[8];
+            load_packed<0, 8>(w, blob, p.end1_w, voff);
+            const float4 *v = reinterpret_cast<const float4 *>(sbuf + fpart * 32);
+            float a = 0.f;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) a = dot4(w[q], v[q], a);
+            a = sum8(a);
+            if (fpart == 0) r1[fu] = lrelu(a + p.end1_b[fu]);
+        }
+        __syncthreads();
+        if (tid < p.nout) {
+            float a = p.end2_b[tid];
+            for (int k = 0; k < p.nout; ++k) a = fmaf(p.end2_w[tid * p.nout + k], r1[k], a);
+            r2[tid] = a;
+        }
+        __syncthreads();
+        // ---- Sample_GMM (losses.py:68-112) / L2 passthrough
+        if (tid < p.ndim) {
+            float v;
+            if (p.loss == LSPA2H_LOSS_L2) {
+                v = r2[tid];
+            } else {
+                int idx = 0;
+                if (p.ncenter > 1) {   // softmax -> prob / Exp(1) draw -> argmax  (torch.multinomial, one sample)
+                    float mx = r2[0];
+                    for (int k = 1; k < p.ncenter; ++k) mx = fmaxf(mx, r2[k]);
+                    float den = 0.f;
+                    for (int k = 0; k < p.ncenter; ++k) den += expf(r2[k] - mx);
+                    float best = -1.f;
+                    for (int k = 0; k < p.ncenter; ++k) {
+                        const float val = (expf(r2[k] - mx) / den) / expq[(size_t)(frame - fbase) * p.ncenter + k];
+                        if (val > best) { best = val; idx = k; }
+                    }
+                }
+                const float mu = r2[p.ncenter + idx * p.ndim + tid];
+                const float sigma = expf(-r2[p.ncenter + p.ncenter * p.ndim + idx * p.ndim + tid]) * p.sigma_scale;
+                const float nz = noise ? noise[(size_t)(frame - fbase) * p.ndim + tid] : 0.f;
+                v = nz * sigma + mu;
+            }
+            out[(size_t)(frame - fbase) * p.ndim + tid] = v;
+            inb[tid] = v;                                // history_headpose <- cat(history[1:], pred), :186
+        }
+        __syncthreads();
+    }
+    if (state_out) {                                     // every step ended on a barrier: the queues and inb are final
+        for (int i = tid; i < qrows * RC; i += NT) state_out[i] = queue[i];
+        if (tid < 16) state_out[qrows * RC + tid] = inb[tid];
+        if (tid == 0) state_out[qrows * RC + 16] = __int_as_float(nsteps);
+    }
+}
+
+// Several streams per launch (lspa2h_generate_resume_multi): workgroup b runs entry b of the table.  A stream's dilation queues fill most of
+// a CU's LDS, so one workgroup per stream is forced; the workgroups share nothing but the weights (read-only) and the status word.
+struct StreamItem {
+    const float *proj;                  // this stream's projection ring
+    const float *pre, *noise, *expq;
+    float *out;
+    const float *state_in;
+    float *state_out;
+    int step0, step1;                   // steps [step0, step1) of the stream; out / noise / expq row 0 is the first frame they emit
+};
+struct StreamTable { StreamItem it[LSPA2H_MAX_STREAMS]; };
+
+__global__ __launch_bounds__(NT) void a2h_stream_multi(StreamParams p, StreamTable tb)
+{
+    extern __shared__ float smem[];
+    const StreamItem &it = tb.it[blockIdx.x];
+    if (it.step1 <= it.step0) return;                // only new audio rows for this stream
+    const int fb = it.step0 - (p.field - 1);
+    stream_steps(p, smem, it.proj, it.pre, it.noise, it.expq, it.out, it.state_in, it.state_out, it.step0, it.step1, fb < 0 ? 0 : fb);
+}
+
+// cond projections of the new rows of all streams, computed in one GEMM into a staging area, go to their streams' rings: source row r
+// belongs to the stream k with src0[k] <= r < src0[k + 1] and lands in ring row (row0[k] + r - src0[k]) % ring of that stream
+struct ScatterParams {
+    const float *src;
+    float *dst[LSPA2H_MAX_STREAMS];
+    int src0[LSPA2H_MAX_STREAMS + 1], row0[LSPA2H_MAX_STREAMS];
+    int n, ring, rowlen4;               // rowlen4: float4 per row
+};
+__global__ __launch_bounds__(256) void proj_scatter(ScatterParams sp)
+{
+    const int r = blockIdx.x;
+    if (r >= sp.src0[sp.n]) return;
+    int k = 0;
+    while (k + 1 < sp.n && r >= sp.src0[k + 1]) ++k;
+    const float4 *src = reinterpret_cast<const float4 *>(sp.src) + (size_t)r * sp.rowlen4;
+    float4 *dst = reinterpret_cast<float4 *>(sp.dst[k]) + (size_t)((sp.row0[k] + r - sp.src0[k]) % sp.ring) * sp.rowlen4;
+    for (int i = threadIdx.x; i < sp.rowlen4; i += 256) dst[i] = src[i];
+}
+
+
 // -------------------------------------------------------------------------------------------- pipeline
 // Layer-pipelined form of the same loop: block 0 is the head (start convs, end convs, sampling), block 1+l owns
 // residual layer l with ALL its weights resident on the CU (fg: 128 VGPRs, residual + first skip half: 64 VGPRs,
@@ -567,8 +787,10 @@ struct lspa2h_handle {
     size_t blob_bytes = 0;
     float *ws = nullptr;
     size_t ws_bytes = 0;
+    float *mws = nullptr;                // the several-streams workspace (lspa2h_bind_workspace_multi)
+    int mstreams = 0;
     bool packed = false;
-    bool attr_done = false, pipe_attr_done = false, pipe_fits = false, boxes_clean = false;
+    bool attr_done = false, mattr_done = false, pipe_attr_done = false, pipe_fits = false, boxes_clean = false;
     unsigned epoch = 0;
     int last_rows = 0;
     size_t xbox_bytes() const { return (size_t)(layers + 1) * (size_t)(field - 1 + cfg.max_audio_frames) * RC * 8; }
@@ -974,6 +1196,141 @@ int lspa2h_generate_resume(lspa2h_handle *h, const float *audio_dev, int row0, i
     hipLaunchKernelGGL(a2h_stream, dim3(1), dim3(NT), lds, s, p);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? LSPA2H_OK : hipfail(e, "a2h_stream launch");
+}
+
+// several-streams workspace: hid / cond / projection staging for max_streams * max_audio_frames new rows, one ring per stream, the status word
+static size_t multi_floats(const lspa2h_handle *h, int max_streams, size_t *o_cond, size_t *o_stage, size_t *o_rings)
+{
+    const size_t rows = (size_t)h->cfg.max_audio_frames * max_streams, H = h->cfg.hidden_size, N = (size_t)h->layers * 256;
+    size_t o = align64(rows * H);
+    if (o_cond) *o_cond = o;
+    o += align64(rows * H);
+    if (o_stage) *o_stage = o;
+    o += align64(rows * N);
+    if (o_rings) *o_rings = o;
+    o += align64(rows * N);
+    return o;
+}
+
+size_t lspa2h_workspace_bytes_multi(const lspa2h_handle *h, int max_streams)
+{
+    if (!h || max_streams < 1 || max_streams > LSPA2H_MAX_STREAMS) return 0;
+    return multi_floats(h, max_streams, nullptr, nullptr, nullptr) * sizeof(float) + 256;
+}
+
+int lspa2h_bind_workspace_multi(lspa2h_handle *h, void *workspace_dev, size_t bytes, int max_streams)
+{
+    if (!h || !workspace_dev) return fail(LSPA2H_ERR_INVALID_ARGUMENT, "null argument");
+    if (max_streams < 1 || max_streams > LSPA2H_MAX_STREAMS) return fail(LSPA2H_ERR_SHAPE, "max_streams must be in 1..LSPA2H_MAX_STREAMS");
+    if (bytes < lspa2h_workspace_bytes_multi(h, max_streams)) return fail(LSPA2H_ERR_SHAPE, "workspace smaller than lspa2h_workspace_bytes_multi()");
+    if ((uintptr_t)workspace_dev & 15) return fail(LSPA2H_ERR_INVALID_ARGUMENT, "workspace must be 16-byte aligned");
+    h->mws = static_cast<float *>(workspace_dev);
+    h->mstreams = max_streams;
+    return LSPA2H_OK;
+}
+
+int lspa2h_generate_resume_multi(lspa2h_handle *h, int nstreams, const lspa2h_stream_call *calls, const float *audio_dev, float sigma_scale,
+                                 int frame_future, void *stream)
+{
+    if (!h || !calls) return fail(LSPA2H_ERR_INVALID_ARGUMENT, "null argument");
+    if (!h->blob) return fail(LSPA2H_ERR_STATE, "weights not bound (lspa2h_bind_weights)");
+    if (!h->mws) return fail(LSPA2H_ERR_STATE, "several-streams workspace not bound (lspa2h_bind_workspace_multi)");
+    if (nstreams < 1 || nstreams > h->mstreams) return fail(LSPA2H_ERR_SHAPE, "nstreams must be in 1..max_streams of the bound workspace");
+    if (frame_future < 0) return fail(LSPA2H_ERR_SHAPE, "frame_future must be >= 0");
+    const int R = h->cfg.max_audio_frames, H = h->cfg.hidden_size, L = h->layers, F1 = h->field - 1;
+    size_t o_cond, o_stage, o_rings;
+    const size_t total = multi_floats(h, h->mstreams, &o_cond, &o_stage, &o_rings);
+    float *hid = h->mws, *cond = hid + o_cond, *stage = hid + o_stage, *rings = hid + o_rings;
+    unsigned *status = reinterpret_cast<unsigned *>(hid + total);
+    const size_t N = (size_t)L * 256;
+    StreamTable tb{};
+    ScatterParams sp{};
+    int n_new = 0;
+    bool steps = false;
+    for (int k = 0; k < nstreams; ++k) {
+        const lspa2h_stream_call &c = calls[k];
+        const std::string w = "stream " + std::to_string(k) + ": ";
+        if (c.slot < 0 || c.slot >= h->mstreams) return fail(LSPA2H_ERR_SHAPE, w + "slot outside the bound workspace (max_streams)");
+        for (int j = 0; j < k; ++j)
+            if (calls[j].slot == c.slot) return fail(LSPA2H_ERR_INVALID_ARGUMENT, w + "slot already used by stream " + std::to_string(j) + " of this call");
+        if (c.row0 < 0 || c.n_new < 0 || c.n_new > R || c.step0 < 0 || c.step1 < c.step0)
+            return fail(LSPA2H_ERR_SHAPE, w + "need row0, step0 >= 0, 0 <= n_new <= max_audio_frames, step1 >= step0");
+        const bool run = c.step1 > c.step0, emits = c.step1 > F1;
+        if (run) {
+            if (!c.state_in && c.step0 != 0) return fail(LSPA2H_ERR_INVALID_ARGUMENT, w + "a call without state_in starts the clip: step0 must be 0");
+            if (c.state_in && c.step0 == 0) return fail(LSPA2H_ERR_INVALID_ARGUMENT, w + "step 0 starts the clip: it takes no state_in");
+            if (!c.state_in && !c.pre_dev) return fail(LSPA2H_ERR_INVALID_ARGUMENT, w + "pre_dev is required at the start of the clip");
+            if (emits && !c.out_dev) return fail(LSPA2H_ERR_INVALID_ARGUMENT, w + "out_dev is required when the steps emit frames");
+            if (emits && h->cfg.loss == LSPA2H_LOSS_GMM && h->cfg.ncenter > 1 && !c.expq_dev)
+                return fail(LSPA2H_ERR_INVALID_ARGUMENT, w + "expq_dev is required when ncenter > 1");
+            for (int j = 0; j < nstreams; ++j) {
+                if (c.state_out && calls[j].step1 > calls[j].step0 && c.state_out == calls[j].state_in)
+                    return fail(LSPA2H_ERR_INVALID_ARGUMENT, w + "state_out is the state_in of stream " + std::to_string(j) +
+                                                             " (state_in and state_out must be separate buffers: a retried call restarts from state_in)");
+                if (j != k && c.state_out && calls[j].step1 > calls[j].step0 && c.state_out == calls[j].state_out)
+                    return fail(LSPA2H_ERR_INVALID_ARGUMENT, w + "state_out shared with stream " + std::to_string(j));
+            }
+            const long long known = (long long)c.row0 + c.n_new;         // audio rows of the stream projected so far
+            const long long lo = c.step0 + frame_future - F1 < 0 ? 0 : c.step0 + frame_future - F1;
+            const long long hi = c.step1 - 1 + frame_future - F1 < 0 ? 0 : c.step1 - 1 + frame_future - F1;
+            if (hi >= known) return fail(LSPA2H_ERR_SHAPE, w + "step step1-1 needs audio row max(0, step1-1+frame_future-(field-1)): not passed yet");
+            if (lo < known - R) return fail(LSPA2H_ERR_SHAPE, w + "an audio row this call reads has left the projection ring (max_audio_frames rows)");
+            steps = true;
+        }
+        float *ring = rings + (size_t)c.slot * R * N;
+        StreamItem &it = tb.it[k];
+        it.proj = ring; it.pre = c.pre_dev; it.noise = c.noise_dev; it.expq = c.expq_dev; it.out = c.out_dev;
+        it.state_in = static_cast<const float *>(c.state_in); it.state_out = static_cast<float *>(c.state_out);
+        it.step0 = c.step0; it.step1 = c.step1;
+        sp.dst[k] = ring; sp.src0[k] = n_new; sp.row0[k] = c.row0;
+        n_new += c.n_new;
+    }
+    sp.src0[nstreams] = n_new; sp.n = nstreams; sp.ring = R; sp.rowlen4 = (int)(N / 4); sp.src = stage;
+    if (n_new > 0 && !audio_dev) return fail(LSPA2H_ERR_INVALID_ARGUMENT, "audio_dev is required when a stream passes new rows");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const float *b = h->blob;
+    int rc;
+    if (hipMemsetAsync(status, 0, 64, s) != hipSuccess) return fail(LSPA2H_ERR_HIP, "hipMemsetAsync(status)");
+    if (n_new > 0) {   // the new rows of every stream: one launch per GEMM, then one copy launch into the rings
+        if ((rc = launch_gemm(audio_dev, b + h->o_mlp0_w, b + h->o_mlp0_scale, b + h->o_mlp0_shift, hid, n_new, H, 2 * H, 1, s))) return rc;
+        if ((rc = launch_gemm(hid, b + h->o_mlp1_w, nullptr, b + h->o_mlp1_b, cond, n_new, H, H, 0, s))) return rc;
+        if ((rc = launch_gemm(cond, b + h->o_proj_w, nullptr, b + h->o_proj_b, stage, n_new, L * 256, H, 0, s))) return rc;
+        hipLaunchKernelGGL(proj_scatter, dim3(n_new), dim3(256), 0, s, sp);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hipfail(e, "proj_scatter launch");
+    }
+    if (!steps) return LSPA2H_OK;
+    StreamParams p{};
+    p.start1_w = b + h->o_start1_w; p.start1_b = b + h->o_start1_b;
+    p.blob = b; p.blob_bytes = (unsigned)(h->blob_floats * sizeof(float));
+    p.start2_w = (unsigned)(h->o_start2_w * 4); p.start2_b = b + h->o_start2_b;
+    p.fg_w = (unsigned)(h->o_fg_w * 4); p.rs_w = (unsigned)(h->o_rs_w * 4); p.rs_b = b + h->o_rs_b;
+    p.end1_w = (unsigned)(h->o_end1_w * 4); p.end1_b = b + h->o_end1_b;
+    p.end2_w = b + h->o_end2_w; p.end2_b = b + h->o_end2_b;
+    p.layers = L; p.ndim = h->cfg.ndim; p.ncenter = h->cfg.ncenter; p.nout = h->nout; p.loss = h->cfg.loss;
+    p.field = h->field; p.frame_future = frame_future; p.sigma_scale = sigma_scale; p.ring = R;
+    for (int l = 0; l < L; ++l) { p.dil[l] = h->dil[l]; p.qoff[l] = h->qoff[l]; }
+    p.status = status;
+    const size_t lds = (size_t)(RC * 3 + SC + 2 * MAX_OUT + 16 + (size_t)h->qrows * RC) * sizeof(float);
+    if (!h->mattr_done) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&a2h_stream_multi),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return hipfail(e, "hipFuncSetAttribute(a2h_stream_multi)");
+        h->mattr_done = true;
+    }
+    hipLaunchKernelGGL(a2h_stream_multi, dim3(nstreams), dim3(NT), lds, s, p, tb);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LSPA2H_OK : hipfail(e, "a2h_stream_multi launch");
+}
+
+int lspa2h_status_multi(lspa2h_handle *h, void *stream, uint32_t *code)
+{
+    if (!h || !code) return fail(LSPA2H_ERR_INVALID_ARGUMENT, "null argument");
+    if (!h->mws) return fail(LSPA2H_ERR_STATE, "several-streams workspace not bound");
+    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "hipStreamSynchronize");
+    e = hipMemcpy(code, h->mws + multi_floats(h, h->mstreams, nullptr, nullptr, nullptr), sizeof(uint32_t), hipMemcpyDeviceToHost);
+    return e == hipSuccess ? LSPA2H_OK : hipfail(e, "hipMemcpy(status)");
 }
 
 int lspa2h_generate(lspa2h_handle *h, const float *audio_dev, int n_audio, const float *pre_dev, const float *noise_dev,

@@ -39,6 +39,32 @@ __global__ __launch_bounds__(256) void mel_gather(const float *audio, long long 
     A[(size_t)i * KA + n] = v;
 }
 
+// The same gather for windows of several buffers (lspmel_compute_ranges): row r belongs to the segment whose [row0, row0 + nwin) holds it; the
+// segment table rides in the kernarg (at most LSPMEL_MAX_SEGMENTS entries, scanned per thread: uniform scalar loads).
+struct Segments {
+    const float *audio[LSPMEL_MAX_SEGMENTS];
+    long long first[LSPMEL_MAX_SEGMENTS], navail[LSPMEL_MAX_SEGMENTS], win0[LSPMEL_MAX_SEGMENTS];
+    int row0[LSPMEL_MAX_SEGMENTS + 1];           // first output row of segment k; row0[nseg] = rows in all
+    int nseg;
+};
+
+__global__ __launch_bounds__(256) void mel_gather_segments(Segments sg, float *A)
+{
+    const int r = blockIdx.x, n = threadIdx.x + blockIdx.y * 256;
+    if (r >= sg.row0[sg.nseg] || n >= KA) return;
+    int k = 0;
+    while (k + 1 < sg.nseg && r >= sg.row0[k + 1]) ++k;
+    float v = 0.f;
+    if (n < LSPMEL_WIN) {
+        const long long st = (long long)((double)(sg.win0[k] + (r - sg.row0[k])) * (16000.0 * (0.5 / 60)));   // as mel_gather
+        int j = n + OFF - PAD;
+        j = j < 0 ? -j : j;
+        const long long s = st + j - sg.first[k];
+        v = s < sg.navail[k] ? sg.audio[k][s] : 0.f;
+    }
+    A[(size_t)r * KA + n] = v;
+}
+
 __global__ __launch_bounds__(256) void mel_magnitude(const float *C, int nwin, float *mag)
 {
     const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -142,8 +168,9 @@ size_t lspmel_workspace_bytes(int nwindows)
 }  // extern "C"
 
 // windows [win0, win0 + nwindows) from stream samples [first, first + navail) in audio_dev
+// (sg != null: the rows of several buffers, gathered by mel_gather_segments; everything after the gather works on a row count)
 static int compute(const float *audio_dev, long long first, long long navail, long long win0, const float *basis_dev, int nwindows,
-                   float *mel_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream)
+                   float *mel_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream, const Segments *sg = nullptr)
 {
     if (workspace_bytes < lspmel_workspace_bytes(nwindows)) return fail(LSPMEL_ERR_SHAPE, "workspace smaller than lspmel_workspace_bytes()");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
@@ -151,7 +178,8 @@ static int compute(const float *audio_dev, long long first, long long navail, lo
     float *A = reinterpret_cast<float *>(w);
     float *C = reinterpret_cast<float *>(w + align256((size_t)nwindows * KA * 4));
     float *mag = reinterpret_cast<float *>(w + align256((size_t)nwindows * KA * 4) + align256((size_t)nwindows * 2 * NB * 4));
-    hipLaunchKernelGGL(mel_gather, dim3(nwindows, (KA + 255) / 256), dim3(256), 0, s, audio_dev, first, navail, win0, nwindows, A);
+    if (sg) hipLaunchKernelGGL(mel_gather_segments, dim3(nwindows, (KA + 255) / 256), dim3(256), 0, s, *sg, A);
+    else hipLaunchKernelGGL(mel_gather, dim3(nwindows, (KA + 255) / 256), dim3(256), 0, s, audio_dev, first, navail, win0, nwindows, A);
     lspgemm::GemmParams g1{A, basis_dev, nullptr, nullptr, nullptr, C, nwindows, 2 * NB, KA, 1.0f, 0};
     hipError_t e = lspgemm::launch_gemm_f32(g1, s);
     if (e != hipSuccess) return fail(LSPMEL_ERR_HIP, std::string("DFT gemm launch: ") + hipGetErrorString(e));
@@ -176,17 +204,47 @@ int lspmel_compute(const float *audio_dev, int64_t nsamples, const float *basis_
 
 int64_t lspmel_window_start(int64_t window) { return window < 0 ? -1 : (int64_t)((double)window * (16000.0 * (0.5 / 60))); }
 
+// the refusals of a window range; `where` prefixes the message (the segment of lspmel_compute_ranges)
+static int check_range(int64_t first_sample, int64_t navail, int ended, int64_t win0, int nwin, const std::string &where)
+{
+    if (nwin < 1 || win0 < 0 || first_sample < 0 || navail < 0) return fail(LSPMEL_ERR_SHAPE, where + "need nwin >= 1 and win0, first_sample, navail >= 0");
+    if (lspmel_window_start(win0) < first_sample) return fail(LSPMEL_ERR_SHAPE, where + "window win0 starts before first_sample");
+    const int64_t end = lspmel_window_start(win0 + nwin - 1) + LSPMEL_WIN;            // one past the last sample of the last window's clip
+    if (!ended && end > first_sample + navail)
+        return fail(LSPMEL_ERR_SHAPE, where + "the last window reaches past the samples passed and the clip has not ended (no zero padding before the end)");
+    if (ended && win0 + nwin > lspmel_num_windows(first_sample + navail))
+        return fail(LSPMEL_ERR_SHAPE, where + "window past the last one of the clip (lspmel_num_windows of its length)");
+    return LSPMEL_OK;
+}
+
+int lspmel_compute_ranges(int nseg, const float *const *audio_dev, const int64_t *first_sample, const int64_t *navail, const int *ended,
+                          const int64_t *win0, const int *nwin, const float *basis_dev, float *mel_dev, void *workspace_dev,
+                          size_t workspace_bytes, void *hip_stream)
+{
+    if (!audio_dev || !first_sample || !navail || !ended || !win0 || !nwin || !basis_dev || !mel_dev || !workspace_dev)
+        return fail(LSPMEL_ERR_INVALID_ARGUMENT, "null argument");
+    if (nseg < 1 || nseg > LSPMEL_MAX_SEGMENTS) return fail(LSPMEL_ERR_SHAPE, "need 1 <= nseg <= LSPMEL_MAX_SEGMENTS");
+    Segments sg{};
+    int rows = 0;
+    for (int k = 0; k < nseg; ++k) {
+        const std::string where = "segment " + std::to_string(k) + ": ";
+        if (!audio_dev[k]) return fail(LSPMEL_ERR_INVALID_ARGUMENT, where + "null sample buffer");
+        if (int rc = check_range(first_sample[k], navail[k], ended[k], win0[k], nwin[k], where)) return rc;
+        if (nwin[k] > (1 << 24) - rows) return fail(LSPMEL_ERR_SHAPE, where + "too many windows in one call");
+        sg.audio[k] = audio_dev[k]; sg.first[k] = first_sample[k]; sg.navail[k] = navail[k]; sg.win0[k] = win0[k];
+        sg.row0[k] = rows;
+        rows += nwin[k];
+    }
+    sg.row0[nseg] = rows;
+    sg.nseg = nseg;
+    return compute(nullptr, 0, 0, 0, basis_dev, rows, mel_dev, workspace_dev, workspace_bytes, hip_stream, &sg);
+}
+
 int lspmel_compute_range(const float *audio_dev, int64_t first_sample, int64_t navail, int ended, int64_t win0, int nwin,
                          const float *basis_dev, float *mel_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream)
 {
     if (!audio_dev || !basis_dev || !mel_dev || !workspace_dev) return fail(LSPMEL_ERR_INVALID_ARGUMENT, "null argument");
-    if (nwin < 1 || win0 < 0 || first_sample < 0 || navail < 0) return fail(LSPMEL_ERR_SHAPE, "need nwin >= 1 and win0, first_sample, navail >= 0");
-    if (lspmel_window_start(win0) < first_sample) return fail(LSPMEL_ERR_SHAPE, "window win0 starts before first_sample");
-    const int64_t end = lspmel_window_start(win0 + nwin - 1) + LSPMEL_WIN;            // one past the last sample of the last window's clip
-    if (!ended && end > first_sample + navail)
-        return fail(LSPMEL_ERR_SHAPE, "the last window reaches past the samples passed and the clip has not ended (no zero padding before the end)");
-    if (ended && win0 + nwin > lspmel_num_windows(first_sample + navail))
-        return fail(LSPMEL_ERR_SHAPE, "window past the last one of the clip (lspmel_num_windows of its length)");
+    if (int rc = check_range(first_sample, navail, ended, win0, nwin, "")) return rc;
     return compute(audio_dev, first_sample, navail, win0, basis_dev, nwin, mel_dev, workspace_dev, workspace_bytes, hip_stream);
 }
 

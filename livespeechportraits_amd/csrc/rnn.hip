@@ -286,6 +286,275 @@ template <int GATES, int P, int CPP> __global__ __launch_bounds__(NT) void rnn_w
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------ several sequences per launch
+// lsprnn_forward_multi: the two kernels above for up to LSPRNN_MAX_SEQUENCES independent sequences in ONE launch.  The weights a thread
+// holds in registers serve every sequence of a step; what is per sequence lives in LDS: the gathered h vectors ([S][H]), the leaders' cell
+// state ([S][U]) and the step's input projections ([S][GATES][U], staged while the polls are in flight).  Per sequence the products, their
+// order, the sum_p reduction and the gate arithmetic are those of the single-sequence kernels, one sequence at a time (no more accumulators
+// are live than there), so each sequence gets the bits of lsprnn_forward_state alone.  Sequence s owns rows [off[s], off[s] + T[s]) of
+// x / xproj / out and of every mailbox plane; a sequence shorter than the longest stops taking part once its steps are done.
+struct SeqTable {
+    const float *state_in[LSPRNN_MAX_SEQUENCES];   // null: zeros
+    float *state_out[LSPRNN_MAX_SEQUENCES];        // null: not written
+    int off[LSPRNN_MAX_SEQUENCES], T[LSPRNN_MAX_SEQUENCES];
+    int S, Tmax, rows;                             // rows = sum T
+};
+
+// the poll of one H-vector of sequence s (threads tid < H), exactly the single-sequence loop
+__device__ __forceinline__ bool poll_vector(__amdgpu_buffer_rsrc_t box, int slot, int tid, int H, unsigned epoch, unsigned *status, float *dst)
+{
+    bool ok = true;
+    if (tid < H) {
+        for (unsigned spins = 0;;) {
+            const u32x2 g = __builtin_amdgcn_raw_buffer_load_b64(box, tid * 8, slot, AUX_SC1);
+            asm volatile("" ::: "memory");
+            if (g.y == epoch) { dst[tid] = __uint_as_float(g.x); break; }
+            if (++spins > SPIN_LIMIT || ((spins & 1023) == 0 && __hip_atomic_load(status, RLX_AGENT) != 0)) { ok = false; break; }
+            __builtin_amdgcn_s_sleep(1);
+        }
+    }
+    return ok;
+}
+
+struct LayerMultiParams {
+    const float *blob; unsigned blob_bytes;
+    unsigned whh;
+    const float *bhn;
+    const float *xproj;            // [rows][GATES*H]
+    float *hseq;                   // [rows][H]
+    unsigned long long *hbox;      // [rows][H] granules
+    unsigned *status;
+    unsigned epoch;
+    int H, stride, layer, layers;  // the state of layer l sits at l * H (h) and (layers + l) * H (c) of a sequence's state
+    SeqTable q;
+};
+
+template <int GATES, int P> __global__ __launch_bounds__(NT) void rnn_layer_multi(LayerMultiParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    if (blockIdx.x % p.stride) return;
+    const int wg = blockIdx.x / p.stride;
+    constexpr int U = NT / P;
+    const int tid = threadIdx.x, part = tid % P, ul = tid / P;
+    const int unit = wg * U + ul;
+    const int H = p.H, S = p.q.S;
+    float *hbuf = lds;                             // [S][H]
+    float *cst = hbuf + S * H;                     // [S][U]          leaders: c of the own unit
+    float *xs = cst + S * U;                       // [S][GATES][U]   this step's input projections of the own units
+    const __amdgpu_buffer_rsrc_t blob = __builtin_amdgcn_make_buffer_rsrc((void *)p.blob, 0, (int)p.blob_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t box = __builtin_amdgcn_make_buffer_rsrc((void *)p.hbox, 0, (int)((unsigned)p.q.rows * (unsigned)H * 8u), 0x00020000);
+    float4 W[GATES * 8];
+#pragma unroll
+    for (int i = 0; i < GATES * 8; ++i)
+        W[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
+            blob, tid * 16, (int)(p.whh + ((unsigned)wg * GATES * 8 + (unsigned)i) * NT * 16u), 0));
+    const float bhn = (GATES == 3 && part == 0) ? p.bhn[unit] : 0.f;
+    if (GATES == 4 && part == 0)
+        for (int s = 0; s < S; ++s) cst[s * U + ul] = p.q.state_in[s] ? p.q.state_in[s][(size_t)(p.layers + p.layer) * H + unit] : 0.f;
+    for (int t = 0; t < p.q.Tmax; ++t) {
+        for (int i = tid; i < S * GATES * U; i += NT) {
+            const int s = i / (GATES * U), r = i - s * (GATES * U), g = r / U, u = r - g * U;
+            if (t < p.q.T[s]) xs[i] = p.xproj[((size_t)(p.q.off[s] + t) * GATES + g) * H + wg * U + u];
+        }
+        bool ok = true;
+        for (int s = 0; s < S && ok; ++s) {
+            if (t >= p.q.T[s]) continue;
+            float *dst = hbuf + s * H;
+            if (t == 0) {
+                const float *h0 = p.q.state_in[s] ? p.q.state_in[s] + (size_t)p.layer * H : nullptr;
+                if (tid < H) dst[tid] = h0 ? h0[tid] : 0.f;
+                continue;
+            }
+            ok = poll_vector(box, (int)((unsigned)(p.q.off[s] + t - 1) * (unsigned)H * 8u), tid, H, p.epoch, p.status, dst);
+            if (!ok) atomicCAS(p.status, 0u, 0x1000000u + ((unsigned)s << 26) + (unsigned)t);
+        }
+        if (!__syncthreads_and(ok)) return;
+        for (int s = 0; s < S; ++s) {
+            if (t >= p.q.T[s]) continue;
+            float a[GATES];
+            {
+                const float4 *v = reinterpret_cast<const float4 *>(hbuf + s * H + part * 32);
+#pragma unroll
+                for (int g = 0; g < GATES; ++g) a[g] = 0.f;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const float4 x = v[q];
+#pragma unroll
+                    for (int g = 0; g < GATES; ++g) a[g] = dot4(W[g * 8 + q], x, a[g]);
+                }
+#pragma unroll
+                for (int g = 0; g < GATES; ++g) a[g] = sum_p<P>(a[g]);
+            }
+            if (part == 0) {
+                float xg[GATES];
+#pragma unroll
+                for (int g = 0; g < GATES; ++g) xg[g] = xs[(s * GATES + g) * U + ul];
+                const float hprev = hbuf[s * H + unit];          // h_{t-1} of the own unit: the value the single-sequence leader keeps in a register
+                float cprev = GATES == 4 ? cst[s * U + ul] : 0.f;
+                float hn;
+                if (GATES == 3) {
+                    const float r = sigmoidf(xg[0] + a[0]);
+                    const float z = sigmoidf(xg[1] + a[1]);
+                    const float n = tanhf(xg[2] + r * (a[2] + bhn));
+                    hn = (1.f - z) * n + z * hprev;
+                } else {
+                    const float i = sigmoidf(xg[0] + a[0]);
+                    const float f = sigmoidf(xg[1] + a[1]);
+                    const float g = tanhf(xg[2] + a[2]);
+                    const float o = sigmoidf(xg[GATES - 1] + a[GATES - 1]);
+                    cprev = f * cprev + i * g;
+                    hn = o * tanhf(cprev);
+                    cst[s * U + ul] = cprev;
+                }
+                const int row = p.q.off[s] + t;
+                u32x2 gr; gr.x = __float_as_uint(hn); gr.y = p.epoch;
+                if (t + 1 < p.q.T[s])
+                    __builtin_amdgcn_raw_buffer_store_b64(gr, box, unit * 8, (int)((unsigned)row * (unsigned)H * 8u), AUX_SC1);
+                p.hseq[(size_t)row * H + unit] = hn;
+                if (t + 1 == p.q.T[s] && p.q.state_out[s]) {
+                    p.q.state_out[s][(size_t)p.layer * H + unit] = hn;
+                    if (GATES == 4) p.q.state_out[s][(size_t)(p.layers + p.layer) * H + unit] = cprev;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+struct WaveMultiParams {
+    const float *blob; unsigned blob_bytes;
+    unsigned whh[8], wih[8];
+    const float *bias[8];
+    const float *bhn[8];
+    const float *xproj;            // layer 0: [rows][GATES*H]
+    float *out;                    // [rows][H] top layer
+    unsigned long long *hbox;      // [layers][rows][H] granules
+    unsigned *status;
+    unsigned epoch;
+    int H, layers, wgs_per_layer, stride;
+    SeqTable q;
+};
+
+template <int GATES, int P, int CPP> __global__ __launch_bounds__(NT) void rnn_wave_multi(WaveMultiParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    if (blockIdx.x % p.stride) return;
+    const int b = blockIdx.x / p.stride;
+    const int l = b / p.wgs_per_layer, wg = b % p.wgs_per_layer;
+    constexpr int U = NT / P, Q = CPP / 4;
+    const int tid = threadIdx.x, part = tid % P, ul = tid / P;
+    const int unit = wg * U + ul;
+    const int H = p.H, S = p.q.S;
+    float *hown = lds;                             // [S][H] own layer's h_{t-1}
+    float *hlow = hown + S * H;                    // [S][H] the layer below's h_t
+    float *cst = hlow + S * H;                     // [S][U]
+    float *xs = cst + S * U;                       // [S][GATES][U] (layer 0)
+    const __amdgpu_buffer_rsrc_t blob = __builtin_amdgcn_make_buffer_rsrc((void *)p.blob, 0, (int)p.blob_bytes, 0x00020000);
+    const unsigned plane = (unsigned)p.q.rows * (unsigned)H * 8u;
+    const __amdgpu_buffer_rsrc_t box = __builtin_amdgcn_make_buffer_rsrc((void *)p.hbox, 0, (int)(plane * (unsigned)p.layers), 0x00020000);
+    float4 W[GATES * Q], V[GATES * Q];
+#pragma unroll
+    for (int i = 0; i < GATES * Q; ++i) {
+        W[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
+            blob, tid * 16, (int)(p.whh[l] + ((unsigned)wg * GATES * Q + (unsigned)i) * NT * 16u), 0));
+        V[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (l > 0)
+            V[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
+                blob, tid * 16, (int)(p.wih[l] + ((unsigned)wg * GATES * Q + (unsigned)i) * NT * 16u), 0));
+    }
+    float bg[GATES];
+#pragma unroll
+    for (int g = 0; g < GATES; ++g) bg[g] = (l > 0 && part == 0) ? p.bias[l][g * H + unit] : 0.f;
+    const float bhn = (GATES == 3 && part == 0) ? p.bhn[l][unit] : 0.f;
+    const bool top = l + 1 == p.layers;
+    if (GATES == 4 && part == 0)
+        for (int s = 0; s < S; ++s) cst[s * U + ul] = p.q.state_in[s] ? p.q.state_in[s][(size_t)(p.layers + l) * H + unit] : 0.f;
+    for (int t = 0; t < p.q.Tmax; ++t) {
+        if (l == 0)
+            for (int i = tid; i < S * GATES * U; i += NT) {
+                const int s = i / (GATES * U), r = i - s * (GATES * U), g = r / U, u = r - g * U;
+                if (t < p.q.T[s]) xs[i] = p.xproj[((size_t)(p.q.off[s] + t) * GATES + g) * H + wg * U + u];
+            }
+        bool ok = true;
+        // per sequence two polls per thread at most: own layer's h_{t-1} (row t-1), the layer below's h_t (row t)
+        for (int s = 0; s < S && ok; ++s) {
+            if (t >= p.q.T[s]) continue;
+            const int row = p.q.off[s] + t;
+            if (t == 0) {
+                const float *h0 = p.q.state_in[s] ? p.q.state_in[s] + (size_t)l * H : nullptr;
+                if (tid < H) hown[s * H + tid] = h0 ? h0[tid] : 0.f;
+            } else {
+                ok = poll_vector(box, (int)((unsigned)l * plane + (unsigned)(row - 1) * (unsigned)H * 8u), tid, H, p.epoch, p.status, hown + s * H);
+            }
+            if (ok && l > 0)
+                ok = poll_vector(box, (int)((unsigned)(l - 1) * plane + (unsigned)row * (unsigned)H * 8u), tid, H, p.epoch, p.status, hlow + s * H);
+            if (!ok) atomicCAS(p.status, 0u, 0x2000000u + ((unsigned)s << 26) + ((unsigned)l << 20) + (unsigned)t);
+        }
+        if (!__syncthreads_and(ok)) return;
+        for (int s = 0; s < S; ++s) {
+            if (t >= p.q.T[s]) continue;
+            float a[GATES], c[GATES];
+            {
+                const float4 *v = reinterpret_cast<const float4 *>(hown + s * H + part * CPP);
+                const float4 *u = reinterpret_cast<const float4 *>(hlow + s * H + part * CPP);
+#pragma unroll
+                for (int g = 0; g < GATES; ++g) { a[g] = 0.f; c[g] = 0.f; }
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    const float4 x = v[q];
+#pragma unroll
+                    for (int g = 0; g < GATES; ++g) a[g] = dot4(W[g * Q + q], x, a[g]);
+                }
+                if (l > 0) {
+#pragma unroll
+                    for (int q = 0; q < Q; ++q) {
+                        const float4 x = u[q];
+#pragma unroll
+                        for (int g = 0; g < GATES; ++g) c[g] = dot4(V[g * Q + q], x, c[g]);
+                    }
+                }
+#pragma unroll
+                for (int g = 0; g < GATES; ++g) { a[g] = sum_p<P>(a[g]); c[g] = sum_p<P>(c[g]); }
+            }
+            if (part == 0) {
+                float xg[GATES];
+#pragma unroll
+                for (int g = 0; g < GATES; ++g) xg[g] = l == 0 ? xs[(s * GATES + g) * U + ul] : bg[g];
+#pragma unroll
+                for (int g = 0; g < GATES; ++g) xg[g] += c[g];       // input side: W_ih h_below + biases (layer 0: from the gemm)
+                const float hprev = hown[s * H + unit];
+                float cprev = GATES == 4 ? cst[s * U + ul] : 0.f;
+                float hn;
+                if (GATES == 3) {
+                    const float r = sigmoidf(xg[0] + a[0]);
+                    const float z = sigmoidf(xg[1] + a[1]);
+                    const float n = tanhf(xg[2] + r * (a[2] + bhn));
+                    hn = (1.f - z) * n + z * hprev;
+                } else {
+                    const float i = sigmoidf(xg[0] + a[0]);
+                    const float f = sigmoidf(xg[1] + a[1]);
+                    const float g = tanhf(xg[2] + a[2]);
+                    const float o = sigmoidf(xg[GATES - 1] + a[GATES - 1]);
+                    cprev = f * cprev + i * g;
+                    hn = o * tanhf(cprev);
+                    cst[s * U + ul] = cprev;
+                }
+                const int row = p.q.off[s] + t;
+                u32x2 gr; gr.x = __float_as_uint(hn); gr.y = p.epoch;
+                if (t + 1 < p.q.T[s] || !top)     // consumers: this layer's next step, and the layer above at this step
+                    __builtin_amdgcn_raw_buffer_store_b64(gr, box, unit * 8, (int)((unsigned)l * plane + (unsigned)row * (unsigned)H * 8u), AUX_SC1);
+                if (top) p.out[(size_t)row * H + unit] = hn;
+                if (t + 1 == p.q.T[s] && p.q.state_out[s]) {
+                    p.q.state_out[s][(size_t)l * H + unit] = hn;
+                    if (GATES == 4) p.q.state_out[s][(size_t)(p.layers + l) * H + unit] = cprev;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 static int hipfail(hipError_t e, const char *what) { return fail(LSPRNN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
@@ -314,6 +583,7 @@ struct lsprnn_handle {
     const float *blob = nullptr;
     float *ws = nullptr;
     bool boxes_clean = false, wave_fit_checked = false, wave_fits = false, layer_fit_checked = false;
+    bool mwave_fit_checked = false, mwave_fits = false, mlayer_fit_checked = false;      // the multi-sequence instances (their LDS differs)
     int fit_device = -1;         // the device the cached residency answers belong to
     unsigned epoch = 0;
     void add(const std::string &k, size_t n) { Slot s; s.key = k; s.numel = n; index[k] = (int)tensors.size(); tensors.push_back(std::move(s)); }
@@ -504,7 +774,11 @@ int lsprnn_forward_state(lsprnn_handle *h, const float *x_dev, int T, float *out
     // per-layer route is taken silently.  The residency answers are cached per handle AND device.
     int dev = -1;
     (void)hipGetDevice(&dev);
-    if (dev != h->fit_device) { h->fit_device = dev; h->wave_fit_checked = h->layer_fit_checked = false; h->wave_fits = false; }
+    if (dev != h->fit_device) {
+        h->fit_device = dev;
+        h->wave_fit_checked = h->layer_fit_checked = h->mwave_fit_checked = h->mlayer_fit_checked = false;
+        h->wave_fits = h->mwave_fits = false;
+    }
     bool wave = (h->cfg.flags & LSPRNN_FLAG_PER_LAYER) ? false : L > 1;
     if (wave && !h->wave_fit_checked) {
         void (*kern0)(WaveParams) = GT == 3 ? (h->Pw == 32 ? rnn_wave<3, 32, 16> : rnn_wave<3, 16, 16>) : (h->Pw == 32 ? rnn_wave<4, 32, 16> : rnn_wave<4, 16, 16>);
@@ -569,6 +843,122 @@ int lsprnn_forward_state(lsprnn_handle *h, const float *x_dev, int T, float *out
         hipLaunchKernelGGL(kern, grid, block, 0, s, p);
         e = hipGetLastError();
         if (e != hipSuccess) return hipfail(e, "rnn_layer launch");
+        in = hseq;
+    }
+    return LSPRNN_OK;
+}
+
+int lsprnn_forward_multi(lsprnn_handle *h, int nseq, const float *x_dev, const int *T, float *out_dev, const float *const *state_in_dev,
+                         float *const *state_out_dev, void *stream)
+{
+    if (!h || !x_dev || !out_dev || !T) return fail(LSPRNN_ERR_INVALID_ARGUMENT, "null argument");
+    if (nseq < 1 || nseq > LSPRNN_MAX_SEQUENCES) return fail(LSPRNN_ERR_SHAPE, "need 1 <= nseq <= LSPRNN_MAX_SEQUENCES");
+    if (!h->blob) return fail(LSPRNN_ERR_STATE, "weights not bound (lsprnn_bind_weights)");
+    if (!h->ws) return fail(LSPRNN_ERR_STATE, "workspace not bound (lsprnn_bind_workspace)");
+    SeqTable q{};
+    long long rows = 0;
+    for (int s = 0; s < nseq; ++s) {
+        if (T[s] < 0) return fail(LSPRNN_ERR_SHAPE, "sequence " + std::to_string(s) + ": T < 0");
+        q.off[s] = (int)rows; q.T[s] = T[s];
+        rows += T[s];
+        if (rows > h->cfg.max_steps) return fail(LSPRNN_ERR_SHAPE, "the steps of all sequences together exceed max_steps (the sequences share the workspace)");
+        q.state_in[s] = state_in_dev ? state_in_dev[s] : nullptr;
+        q.state_out[s] = state_out_dev ? state_out_dev[s] : nullptr;
+        if (T[s] > q.Tmax) q.Tmax = T[s];
+    }
+    // a state-out buffer is written while other sequences may still read their state-in: no buffer may be both, in any pairing
+    for (int s = 0; s < nseq; ++s)
+        for (int r = 0; r < nseq; ++r) {
+            if (q.state_out[s] && q.state_out[s] == q.state_in[r])
+                return fail(LSPRNN_ERR_INVALID_ARGUMENT, "sequence " + std::to_string(s) + ": state_out is the state_in of sequence " + std::to_string(r) +
+                                                         " (state_in and state_out must be separate buffers: a retried call restarts from state_in)");
+            if (r != s && q.state_out[s] && q.state_out[s] == q.state_out[r])
+                return fail(LSPRNN_ERR_INVALID_ARGUMENT, "sequences " + std::to_string(s) + " and " + std::to_string(r) + " share a state_out buffer");
+        }
+    q.S = nseq; q.rows = (int)rows;
+    if (rows == 0) return LSPRNN_OK;                          // nothing to do: no sequence is touched
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int H = h->cfg.hidden_size, GT = h->gates, L = h->cfg.num_layers, R = (int)rows;
+    float *xproj = h->ws, *hs0 = xproj + h->xproj_floats(), *hs1 = hs0 + h->hseq_floats();
+    char *tail = reinterpret_cast<char *>(hs1 + h->hseq_floats());
+    unsigned long long *box = reinterpret_cast<unsigned long long *>(tail);
+    unsigned *status = reinterpret_cast<unsigned *>(tail + h->box_bytes());
+    if (hipMemsetAsync(status, 0, 64, s) != hipSuccess) return fail(LSPRNN_ERR_HIP, "hipMemsetAsync(status)");
+    if (!h->boxes_clean) {
+        const hipError_t e = hipMemsetAsync(box, 0, h->box_bytes(), s);
+        if (e != hipSuccess) return hipfail(e, "hipMemsetAsync(mailboxes)");
+        h->boxes_clean = true;
+    }
+    int dev = -1;
+    (void)hipGetDevice(&dev);
+    if (dev != h->fit_device) {
+        h->fit_device = dev;
+        h->wave_fit_checked = h->layer_fit_checked = h->mwave_fit_checked = h->mlayer_fit_checked = false;
+        h->wave_fits = h->mwave_fits = false;
+    }
+    // residency is asked for the LDS of a full call (LSPRNN_MAX_SEQUENCES sequences), so the route does not depend on nseq
+    const size_t lds_wave_max = ((size_t)LSPRNN_MAX_SEQUENCES * (2 * H + (GT + 1) * h->Uw)) * sizeof(float);
+    const size_t lds_layer_max = ((size_t)LSPRNN_MAX_SEQUENCES * (H + (GT + 1) * h->U)) * sizeof(float);
+    bool wave = (h->cfg.flags & LSPRNN_FLAG_PER_LAYER) ? false : L > 1;
+    void (*wkern)(WaveMultiParams) = GT == 3 ? (h->Pw == 32 ? rnn_wave_multi<3, 32, 16> : rnn_wave_multi<3, 16, 16>)
+                                             : (h->Pw == 32 ? rnn_wave_multi<4, 32, 16> : rnn_wave_multi<4, 16, 16>);
+    if (wave && !h->mwave_fit_checked) {
+        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(wkern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wave_max);
+        if (e0 != hipSuccess) return hipfail(e0, "hipFuncSetAttribute(rnn_wave_multi)");
+        bool ok = false;
+        e0 = lspgemm::fits_resident(reinterpret_cast<const void *>(wkern), NT, lds_wave_max, L * h->Gw, &ok);
+        if (e0 != hipSuccess) return hipfail(e0, "occupancy query (rnn_wave_multi)");
+        h->mwave_fits = ok;
+        h->mwave_fit_checked = true;
+    }
+    if (wave && !h->mwave_fits) wave = false;
+    if (wave) {
+        lspgemm::GemmParams g{x_dev, h->blob + h->o_wih[0], nullptr, h->blob + h->o_bias[0], nullptr, xproj, R, GT * H, h->in_size(0), 1.0f, 0};
+        hipError_t e = lspgemm::launch_gemm_f32(g, s);
+        if (e != hipSuccess) return hipfail(e, "input projection gemm launch");
+        if (++h->epoch == 0) h->epoch = 1;
+        WaveMultiParams p{};
+        p.blob = h->blob; p.blob_bytes = (unsigned)(h->blob_floats * sizeof(float));
+        for (int l = 0; l < L; ++l) {
+            p.whh[l] = (unsigned)(h->o_whh_w[l] * sizeof(float)); p.wih[l] = (unsigned)(h->o_wih_w[l] * sizeof(float));
+            p.bias[l] = h->blob + h->o_bias[l]; p.bhn[l] = h->blob + h->o_bhn[l];
+        }
+        p.xproj = xproj; p.out = out_dev; p.hbox = box; p.status = status; p.epoch = h->epoch;
+        p.H = H; p.layers = L; p.wgs_per_layer = h->Gw; p.q = q;
+        const int nwg = L * h->Gw;
+        p.stride = nwg <= 32 ? 8 : (nwg <= 64 ? 4 : (nwg <= 128 ? 2 : 1));
+        const size_t lds = ((size_t)nseq * (2 * H + (GT + 1) * h->Uw)) * sizeof(float);
+        hipLaunchKernelGGL(wkern, dim3(nwg * p.stride), dim3(NT), lds, s, p);
+        e = hipGetLastError();
+        return e == hipSuccess ? LSPRNN_OK : hipfail(e, "rnn_wave_multi launch");
+    }
+    void (*lkern)(LayerMultiParams) = GT == 3 ? (h->P == 16 ? rnn_layer_multi<3, 16> : rnn_layer_multi<3, 8>)
+                                              : (h->P == 16 ? rnn_layer_multi<4, 16> : rnn_layer_multi<4, 8>);
+    if (!h->mlayer_fit_checked) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(lkern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layer_max);
+        if (e != hipSuccess) return hipfail(e, "hipFuncSetAttribute(rnn_layer_multi)");
+        bool ok = false;
+        e = lspgemm::fits_resident(reinterpret_cast<const void *>(lkern), NT, lds_layer_max, h->G, &ok);
+        if (e != hipSuccess) return hipfail(e, "occupancy query (rnn_layer_multi)");
+        if (!ok) return fail(LSPRNN_ERR_UNSUPPORTED, "rnn_layer_multi: the G = H / P polling workgroups of a layer (16..64) do not fit this device at once");
+        h->mlayer_fit_checked = true;
+    }
+    const float *in = x_dev;
+    for (int l = 0; l < L; ++l) {
+        lspgemm::GemmParams g{in, h->blob + h->o_wih[l], nullptr, h->blob + h->o_bias[l], nullptr, xproj, R, GT * H, h->in_size(l), 1.0f, 0};
+        hipError_t e = lspgemm::launch_gemm_f32(g, s);
+        if (e != hipSuccess) return hipfail(e, "input projection gemm launch");
+        float *hseq = l + 1 == L ? out_dev : (l & 1 ? hs1 : hs0);
+        if (++h->epoch == 0) h->epoch = 1;
+        LayerMultiParams p{};
+        p.blob = h->blob; p.blob_bytes = (unsigned)(h->blob_floats * sizeof(float));
+        p.whh = (unsigned)(h->o_whh[l] * sizeof(float)); p.bhn = h->blob + h->o_bhn[l];
+        p.xproj = xproj; p.hseq = hseq; p.hbox = box; p.status = status; p.epoch = h->epoch;
+        p.H = H; p.stride = 8; p.layer = l; p.layers = L; p.q = q;
+        const size_t lds = ((size_t)nseq * (H + (GT + 1) * h->U)) * sizeof(float);
+        hipLaunchKernelGGL(lkern, dim3(h->G * p.stride), dim3(NT), lds, s, p);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hipfail(e, "rnn_layer_multi launch");
         in = hseq;
     }
     return LSPRNN_OK;

@@ -117,6 +117,52 @@ class LiveScheduler:
         return self._step(0, True)
 
 
+class PrimingPlanner:
+    """Which steps of the head-pose WaveNet a session runs in each step of work, when the field - 1 priming steps before pose 0 are
+    spread over the ticks instead of run in one go (LiveSessionPool; lspa2h_generate_resume_multi takes step ranges).
+
+    Step s < field - 1 primes and emits nothing, step field - 1 + i emits pose i; step s reads pair row max(0, s + ff_head - (field - 1)).
+    Rules: a step runs only once the row it reads exists; while no pose is due a session runs at most ``prime_steps_per_tick`` priming
+    steps per tick (``begin_tick`` refills the budget); when poses are due, every step up to the last of them runs at once, whatever
+    is left of the priming included (a whole clip pushed at once primes in one go).  Pair rows are handed to the generator when steps
+    run, all that exist: until pose 0 the rows 0..ff_head must stay in the generator's ring, which therefore holds at least
+    ff_head + (pair rows one step of work can add) rows -- ``ring_rows_needed``; LiveAudioFrontEnd's ring is one row longer."""
+
+    def __init__(self, field: int, ff_head: int, prime_steps_per_tick: int = 16):
+        if field < 1 or ff_head < 0 or prime_steps_per_tick < 1:
+            raise ValueError("need field >= 1, frame_future >= 0 and prime_steps_per_tick >= 1")
+        self.f1, self.ff, self.per_tick = field - 1, ff_head, prime_steps_per_tick
+        self.step = 0          # the next step
+        self.rows = 0          # pair rows handed to the generator
+        self.budget = prime_steps_per_tick
+
+    @staticmethod
+    def ring_rows_needed(ff_head: int, max_pairs_per_step: int) -> int:
+        return ff_head + max_pairs_per_step
+
+    def begin_tick(self) -> None:
+        self.budget = self.per_tick
+
+    def plan(self, npairs: int, poses) -> tuple:
+        """One step of work: ``npairs`` pair rows exist, ``poses`` = (h0, h1) are due (LivePlan.poses).  -> ((r0, r1), (s0, s1)): pair rows
+        to hand over and steps to run; r1 > r0 only when s1 > s0."""
+        h0, h1 = poses
+        s0 = self.step
+        if h1 > h0:
+            if s0 > self.f1 + h0 or (s0 < self.f1 + h0 and h0 > 0):
+                raise RuntimeError("internal: head-pose steps out of step with the poses due")
+            s1 = self.f1 + h1
+        elif s0 < self.f1 and npairs > 0:
+            s1 = max(s0, min(self.f1, s0 + self.budget, npairs + self.f1 - self.ff))
+            self.budget -= s1 - s0
+        else:
+            s1 = s0
+        r0 = self.rows
+        r1 = npairs if s1 > s0 else r0
+        self.step, self.rows = s1, r1
+        return (r0, r1), (s0, s1)
+
+
 def run_plan(backend, plan: LivePlan, samples) -> None:
     """The order every step runs in; ``backend`` provides the stages (LiveAudioFrontEnd, or a test double):
     feed(samples, first_sample, keep_from)  append the new samples; samples before `keep_from` are no longer read

@@ -68,6 +68,39 @@ def compute_mel_range(samples: torch.Tensor, first_sample: int, win0: int, nwin:
     return mel
 
 
+def compute_mel_ranges(segments, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Windows of several buffers in one call (include/lspmel.h lspmel_compute_ranges).  ``segments``: 1..16 tuples
+    (samples, first_sample, win0, nwin, ended), each what compute_mel_range takes for one stream -> [sum nwin, 80], the rows of segment 0,
+    then segment 1, ...; every row bit for bit what compute_mel_range gives for that window.  The refusals apply per segment."""
+    segments = list(segments)
+    if not 1 <= len(segments) <= N.MEL_MAX_SEGMENTS:
+        raise ValueError("need 1..%d segments, got %d" % (N.MEL_MAX_SEGMENTS, len(segments)))
+    dev = segments[0][0].device
+    for k, (samples, *_rest) in enumerate(segments):
+        if samples.device.type != "cuda" or samples.dim() != 1 or samples.dtype != torch.float32 or not samples.is_contiguous():
+            raise ValueError("segment %d: samples must be a contiguous 1-d float32 device tensor (there is no CPU path)" % k)
+        if samples.device != dev:
+            raise ValueError("segment %d: all sample buffers must be on one device" % k)
+    lib = N.load()
+    n = len(segments)
+    total = sum(int(sg[3]) for sg in segments)
+    mel = out if out is not None else torch.empty((max(total, 0), 80), dtype=torch.float32, device=dev)
+    if tuple(mel.shape) != (total, 80) or not mel.is_contiguous() or mel.device != dev:
+        raise ValueError("out must be a contiguous [%d, 80] tensor on %s" % (total, dev))
+    need = int(lib.lspmel_workspace_bytes(max(total, 1)))
+    ws = workspace if workspace is not None and workspace.numel() >= need else torch.empty(need, dtype=torch.uint8, device=dev)
+    ptrs = (ctypes.c_void_p * n)(*[sg[0].data_ptr() for sg in segments])
+    first = (ctypes.c_int64 * n)(*[int(sg[1]) for sg in segments])
+    navail = (ctypes.c_int64 * n)(*[sg[0].shape[0] for sg in segments])
+    win0 = (ctypes.c_int64 * n)(*[int(sg[2]) for sg in segments])
+    nwin = (ctypes.c_int * n)(*[int(sg[3]) for sg in segments])
+    ended = (ctypes.c_int * n)(*[int(bool(sg[4])) for sg in segments])
+    with torch.cuda.device(dev):
+        N.check_mel(lib.lspmel_compute_ranges(n, ptrs, first, navail, ended, win0, nwin, _basis_on(dev).data_ptr(), mel.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return mel
+
+
 def compute_mel_one_sequence(audio, hop_length=int(16000 / 120), winlen=1 / 60, winstep=0.5 / 60, sr=16000, fps=60, device="cuda:0"):
     """Same signature and return type as the reference function: numpy float64 [mel_nframe, 80].  Only the parameter set the
     reference itself uses is supported (it hard-codes them into Audio2Mel as well)."""

@@ -121,6 +121,42 @@ class RecurrentEngine:
             N.check_rnn(self.lib.lsprnn_forward_state(self.h, ptr(x), x.shape[0], ptr(out), ptr(state_in), ptr(state_out), _stream(x.device)))
         return out
 
+    def forward_multi(self, x: torch.Tensor, lengths, states_in=None, states_out=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Up to 16 independent sequences in one call (include/lsprnn.h lsprnn_forward_multi): ``x`` [sum T_s, input_size] holds them one
+        after another, ``lengths`` the T_s (ragged; 0 leaves a sequence untouched, state included), ``states_in`` / ``states_out`` one
+        buffer (or None: zeros / not written) per sequence in forward_state's layout.  -> [sum T_s, hidden_size]; each sequence's rows
+        and final state are bit for bit forward_state's on that sequence alone.  Asynchronous on the current stream."""
+        if self.blob is None:
+            raise RuntimeError("RecurrentEngine.bind(device) first")
+        lengths = [int(t) for t in lengths]
+        n = len(lengths)
+        if not 1 <= n <= N.RNN_MAX_SEQUENCES:
+            raise ValueError("need 1..%d sequences, got %d" % (N.RNN_MAX_SEQUENCES, n))
+        _require("x", x)
+        if x.dim() != 2 or x.shape[1] != self.input_size or x.shape[0] != sum(lengths) or min(lengths) < 0:
+            raise ValueError("x must be [sum(lengths) = %d, %d] and every length >= 0" % (sum(lengths), self.input_size))
+        tables = []
+        for name, states in (("states_in", states_in), ("states_out", states_out)):
+            states = [None] * n if states is None else list(states)
+            if len(states) != n:
+                raise ValueError("%s must have one entry per sequence" % name)
+            for t in states:
+                if t is not None:
+                    _require(name, t)
+                    if t.numel() != self.state_floats():
+                        raise ValueError("%s entries must hold %d floats" % (name, self.state_floats()))
+            tables.append((ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in states]))
+        if out is None:
+            out = torch.empty((x.shape[0], self.hidden_size), dtype=torch.float32, device=x.device)
+        elif tuple(out.shape) != (x.shape[0], self.hidden_size) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [%d, %d] tensor" % (x.shape[0], self.hidden_size))
+        if x.shape[0] == 0:                   # every sequence is empty: nothing is launched, no state is touched
+            return out
+        with torch.cuda.device(x.device):
+            N.check_rnn(self.lib.lsprnn_forward_multi(self.h, n, ctypes.c_void_p(x.data_ptr()), (ctypes.c_int * n)(*lengths),
+                                                      ctypes.c_void_p(out.data_ptr()), tables[0], tables[1], _stream(x.device)))
+        return out
+
     def status(self) -> int:
         code = ctypes.c_uint32()
         dev = self.blob.device
