@@ -6,7 +6,7 @@
 
 namespace lspgemm {
 
-// Hand-off kernels (a2h_pipe, rnn_wave, rnn_layer: the workgroups of ONE launch poll each other's mailboxes) only make progress when all
+// Hand-off kernels (a2h_pipe, rnn_wave, rnn_wave_multi: the workgroups of ONE launch poll each other's mailboxes) only make progress when all
 // their working blocks are resident at once.  A launch-time check against the occupancy query is what hipLaunchCooperativeKernel buys
 // (MI355X_MICROARCH.md, coop-launch row: +15-19 us per launch and the same residency as a plain launch), so it is done here once per kernel
 // instead: working blocks <= resident capacity of the device, with one block per CU of margin where several fit (the API answer can be one

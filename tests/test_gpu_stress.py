@@ -1,4 +1,4 @@
-"""Hand-off robustness of the multi-workgroup kernels (csrc/a2h.hip a2h_pipe, csrc/rnn.hip rnn_layer): the protocols must
+"""Hand-off robustness of the multi-workgroup kernels (csrc/a2h.hip a2h_pipe, csrc/rnn.hip rnn_wave): the protocols must
 not depend on timing, placement or an idle GPU.  Every repetition must be bit-identical to a quiet run and report no
 timeout while the renderer saturates the device on another stream (cdna_hip_programming.md Guideline 16, pitfall 3:
 a test on an idle, L1-cold GPU cannot see a missing acquire)."""
