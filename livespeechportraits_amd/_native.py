@@ -1,4 +1,4 @@
-"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h).
+"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h, include/lsplmk.h).
 
 There is deliberately no fallback: if the shared library is missing or does not
 load, importing the hot path raises -- a GPU box must never silently run
@@ -307,6 +307,45 @@ JPEG_SIGNATURES = {
     "lspjpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+
+
+class LmkConfig(Structure):
+    """lsplmk_config (include/lsplmk.h)"""
+    _fields_ = [(n, c_int32) for n in ("abi_version", "amp_method", "proj_f64", "n_candidates", "max_sessions", "ring_rows", "radius_mouth",
+                                       "radius_rot", "radius_trans", "future_mouth", "future_rot", "future_trans")] + \
+               [(n, ctypes.c_double) for n in ("sigma_mouth", "sigma_rot", "sigma_trans")] + [("amp", ctypes.c_double * 6), ("scale", ctypes.c_double)] + \
+               [(n, c_float) for n in ("rot_amp", "trans_amp", "shoulder_amp", "pad_dx", "pad_dy")] + \
+               [(n, c_void_p) for n in ("taps_mouth", "taps_rot", "taps_trans", "mean_mouth", "base_pts", "brow", "brow_indices", "mean_translation",
+                                        "camera_intrinsic", "view_rotation", "view_translation", "shoulder3d", "ref_trans")]
+
+
+class LmkSessionCall(Structure):
+    """lsplmk_session_call (include/lsplmk.h)"""
+    _fields_ = [(n, c_int32) for n in ("slot", "mouth_have", "mouth_fresh", "pose_have", "pose_fresh", "pose_stride", "emit0", "n_emit", "nframe",
+                                       "reserved")] + [("mouth_dev", c_void_p), ("poses_dev", c_void_p), ("out_dev", c_void_p)]
+
+
+LMK_ABI_VERSION = 1
+LMK_MAX_SESSIONS = 16
+LMK_MAX_RADIUS = 128
+LMK_AMP_IDS = {"XY": 0, "XYZ": 1, "LowerMore": 2, "delta": 3, "CloseSmall": 4}
+# every symbol include/lsplmk.h declares
+LMK_SIGNATURES = {
+    "lsplmk_create": (c_int, [POINTER(LmkConfig), POINTER(c_void_p)]),
+    "lsplmk_destroy": (c_int, [c_void_p]),
+    "lsplmk_last_error": (c_char_p, []),
+    "lsplmk_abi_version": (c_int, []),
+    "lsplmk_params_bytes": (c_size_t, [c_void_p]),
+    "lsplmk_pack_params": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "lsplmk_bind_params": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "lsplmk_state_bytes": (c_size_t, [c_void_p]),
+    "lsplmk_bind_state": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "lsplmk_clip_workspace_bytes": (c_size_t, [c_int]),
+    "lsplmk_clip": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "lsplmk_tick": (c_int, [c_void_p, c_int, POINTER(LmkSessionCall), c_void_p]),
+    "lsplmk_check_tick": (c_int, [c_void_p, c_int, POINTER(LmkSessionCall)]),
+}
+
 _lib = None
 
 
@@ -324,7 +363,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise NativeLibraryError("failed to load %s: %s" % (LIB_PATH, e)) from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(LMK_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -339,6 +378,8 @@ def load() -> ctypes.CDLL:
                                  % (lib.lspa2h_abi_version(), A2H_ABI_VERSION))
     if lib.lspunet_abi_version() != UNET_ABI_VERSION:
         raise NativeLibraryError("lspunet ABI version mismatch: library %d, binding %d" % (lib.lspunet_abi_version(), UNET_ABI_VERSION))
+    if lib.lsplmk_abi_version() != LMK_ABI_VERSION:
+        raise NativeLibraryError("lsplmk ABI version mismatch: library %d, binding %d" % (lib.lsplmk_abi_version(), LMK_ABI_VERSION))
     _lib = lib
     return lib
 
@@ -431,3 +472,15 @@ def check_jpeg(rc: int) -> None:
     if rc != OK:
         msg = load().lspjpeg_last_error()
         raise LspjpegError(rc, msg.decode() if msg else "")
+
+
+class LsplmkError(RuntimeError):
+    def __init__(self, code: int, msg: str):
+        super().__init__("lsplmk error %d: %s" % (code, msg))
+        self.code = code
+
+
+def check_lmk(rc: int) -> None:
+    if rc != OK:
+        msg = load().lsplmk_last_error()
+        raise LsplmkError(rc, msg.decode() if msg else "")

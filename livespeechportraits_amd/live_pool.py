@@ -102,6 +102,22 @@ class PoolPlanner:
         return [[per[sid][r] for sid in sorted(per) if r < len(per[sid])] for r in range(nrounds)]
 
 
+    def preview(self, lengths: Dict[int, int], finish) -> Dict[int, tuple]:
+        """What ``rounds(lengths, finish)`` would hand out, without advancing anything: {sid: (mouth rows, head poses)} that the tick makes
+        final.  Runs ``rounds`` on deep copies of the named sessions' schedulers."""
+        import copy
+        named = sorted(set(lengths) | set(finish))
+        twin = copy.copy(self)
+        twin.sched = {sid: copy.deepcopy(self.sched[sid]) for sid in named}
+        twin.prime = {sid: copy.deepcopy(self.prime[sid]) for sid in named}
+        out = {sid: [0, 0] for sid in named}
+        for work in twin.rounds(lengths, finish):
+            for sid, p, _, _, _ in work:
+                out[sid][0] += p.mouth[1] - p.mouth[0]
+                out[sid][1] += p.poses[1] - p.poses[0]
+        return {sid: tuple(v) for sid, v in out.items()}
+
+
 class _Slot:
     """Host-side book-keeping of one open session (the device memory is the pool's slot arrays)."""
 
