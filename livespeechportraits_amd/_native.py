@@ -1,4 +1,4 @@
-"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h, include/lsplmk.h).
+"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h, include/lsplmk.h, include/lspavi.h).
 
 There is deliberately no fallback: if the shared library is missing or does not
 load, importing the hot path raises -- a GPU box must never silently run
@@ -346,6 +346,17 @@ LMK_SIGNATURES = {
     "lsplmk_check_tick": (c_int, [c_void_p, c_int, POINTER(LmkSessionCall)]),
 }
 
+# every symbol include/lspavi.h declares
+AVI_MAX_BATCH = 64
+AVI_AUDIO_FORMATS = {None: 0, "s16": 1, "f32": 3}               # the WAVEFORMATEX wFormatTag
+AVI_SIGNATURES = {
+    "lspavi_last_error": (c_char_p, []),
+    "lspavi_capacity_bytes": (c_size_t, [c_int, c_size_t, c_int, c_int, c_int, c_int]),
+    "lspavi_workspace_bytes": (c_size_t, [c_int]),
+    "lspavi_pack": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int,
+                            c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 _lib = None
 
 
@@ -363,7 +374,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise NativeLibraryError("failed to load %s: %s" % (LIB_PATH, e)) from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(LMK_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(LMK_SIGNATURES.items()) + list(AVI_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -472,6 +483,18 @@ def check_jpeg(rc: int) -> None:
     if rc != OK:
         msg = load().lspjpeg_last_error()
         raise LspjpegError(rc, msg.decode() if msg else "")
+
+
+class LspaviError(RuntimeError):
+    def __init__(self, code: int, msg: str):
+        super().__init__("lspavi error %d: %s" % (code, msg))
+        self.code = code
+
+
+def check_avi(rc: int) -> None:
+    if rc != OK:
+        msg = load().lspavi_last_error()
+        raise LspaviError(rc, msg.decode() if msg else "")
 
 
 class LsplmkError(RuntimeError):

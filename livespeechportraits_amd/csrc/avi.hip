@@ -1,0 +1,294 @@
+// avi.hip -- the 'movi' fragment of a Motion-JPEG AVI, assembled on the device (include/lspavi.h).
+//
+// Two launches per batch, whatever the content:
+//   avi_layout  one wavefront: lane k owns frame k.  Chunk lengths (audio span of the frame, header + the encoder's byte count), their
+//               padded sizes scanned across the wavefront, then the table of chunk offsets / lengths / first samples (workspace), the index
+//               entries and the status block.
+//   avi_gather  gather form: one lane owns an aligned 16-byte piece of the OUTPUT.  It binary-searches the offset table (a copy in LDS) for
+//               the chunk the piece starts in.  A piece that lies inside one source segment (JPEG header, entropy-coded bytes, audio) is read
+//               as aligned dwords and funnel-shifted into place; a piece that touches a seam (chunk header, pad byte, header -> scan, the
+//               fragment's end) is selected byte by byte.  One 16-byte store per piece; the last, partial piece is stored as its dwords and an
+//               even byte tail, so nothing at or above the fragment's length is written.
+// Every output byte has exactly one writer, so the result does not depend on what the buffer held, and there is nothing to zero and no atomic.
+// The kernel moves ~150 KB per batch of 8 frames of 512 x 512: it is latency-bound, and what is being bought is the single copy to the host.
+#include "../../include/lspavi.h"
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+namespace lspavi {
+
+constexpr int TAB = 2 * LSPAVI_MAX_BATCH + 4;       // table stride: 2 * 64 chunks + the end offset, rounded up
+constexpr int NT = 256;                             // lanes per workgroup of avi_gather
+constexpr int MAX_BLOCKS = 256;                     // avi_gather strides over the pieces: 1 MiB per pass
+constexpr uint32_t FCC_VIDEO = 0x63643030u;         // '00dc'
+constexpr uint32_t FCC_AUDIO = 0x62773130u;         // '01wb'
+
+struct Params {
+    const unsigned char *hdr;       // JPEG header, hlen bytes
+    const unsigned char *slab;      // [batch][cap]
+    const uint32_t *sizes;          // [batch]
+    const float *wave;
+    unsigned char *out;
+    uint32_t *index;                // [nch][4]
+    uint32_t *status;               // [4]
+    uint32_t *tab;                  // [3][TAB]: chunk offsets (nch + 1), chunk lengths (nch), first sample of frame k (batch)
+    unsigned long long cap;
+    long long frame0;
+    int hlen, batch, rate, fps, fmt;
+};
+
+__device__ inline uint32_t sample_of(const Params &p, long long frame)
+{
+    return static_cast<uint32_t>(static_cast<unsigned long long>(frame) * static_cast<unsigned long long>(p.rate) /
+                                 static_cast<unsigned long long>(p.fps));
+}
+
+__global__ __launch_bounds__(64) void avi_layout(Params p)
+{
+    const int k = threadIdx.x;
+    const bool on = k < p.batch, au = p.fmt != LSPAVI_AUDIO_NONE;
+    const uint32_t bps = p.fmt == LSPAVI_AUDIO_F32 ? 4u : 2u;
+    uint32_t s0 = 0, alen = 0, vlen = 0;
+    if (on) {
+        if (au) {
+            s0 = sample_of(p, p.frame0 + k);
+            alen = (sample_of(p, p.frame0 + k + 1) - s0) * bps;
+        }
+        uint32_t sz = p.sizes[k];
+        if (sz > p.cap) sz = static_cast<uint32_t>(p.cap);      // never true for what lspjpeg_encode wrote: keeps every read inside the slab
+        vlen = static_cast<uint32_t>(p.hlen) + sz;
+    }
+    const uint32_t apad = on && au ? 8u + alen : 0u;            // 2 or 4 bytes per sample: always even
+    const uint32_t vpad = on ? 8u + vlen + (vlen & 1u) : 0u;
+    const uint32_t mine = apad + vpad;
+    uint32_t inc = mine, vmax = vlen, amax = alen;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d, 64);
+        if (k >= d) inc += t;
+        vmax = max(vmax, static_cast<uint32_t>(__shfl_xor(vmax, d, 64)));
+        amax = max(amax, static_cast<uint32_t>(__shfl_xor(amax, d, 64)));
+    }
+    if (!on) return;
+    const uint32_t start = inc - mine;
+    uint32_t c = au ? 2 * k : k;
+    p.tab[2 * TAB + k] = s0;
+    if (au) {
+        p.tab[c] = start;
+        p.tab[TAB + c] = alen;
+        *reinterpret_cast<uint4 *>(p.index + 4 * c) = make_uint4(FCC_AUDIO, 0x10u, start, alen);
+        ++c;
+    }
+    p.tab[c] = start + apad;
+    p.tab[TAB + c] = vlen;
+    *reinterpret_cast<uint4 *>(p.index + 4 * c) = make_uint4(FCC_VIDEO, 0x10u, start + apad, vlen);
+    if (k == p.batch - 1) {
+        p.tab[c + 1] = inc;
+        *reinterpret_cast<uint4 *>(p.status) = make_uint4(inc, c + 1, vmax, amax);
+    }
+}
+
+__device__ inline uint32_t pcm16(float x)
+{
+    float v = rintf(x * 32767.0f);
+    if (!(v == v)) return 0u;
+    v = fminf(fmaxf(v, -32767.0f), 32767.0f);
+    return static_cast<uint32_t>(static_cast<int>(v)) & 0xFFFFu;
+}
+
+// 16 bytes from base + off, base 4-byte aligned: aligned dwords, funnel-shifted.  Every dword read holds at least one byte of the 16.
+__device__ inline uint4 load16(const unsigned char *base, size_t off)
+{
+    const uint32_t *a = reinterpret_cast<const uint32_t *>(base + (off & ~static_cast<size_t>(3)));
+    const unsigned sh = static_cast<unsigned>(off & 3) * 8;
+    const uint32_t w0 = a[0], w1 = a[1], w2 = a[2], w3 = a[3];
+    if (sh == 0) return make_uint4(w0, w1, w2, w3);
+    const uint32_t w4 = a[4];
+    const unsigned up = 32 - sh;
+    return make_uint4((w0 >> sh) | (w1 << up), (w1 >> sh) | (w2 << up), (w2 >> sh) | (w3 << up), (w3 >> sh) | (w4 << up));
+}
+
+__global__ __launch_bounds__(NT) void avi_gather(Params p)
+{
+    __shared__ uint32_t s_off[TAB], s_len[TAB], s_smp[LSPAVI_MAX_BATCH];
+    const bool au = p.fmt != LSPAVI_AUDIO_NONE;
+    const int nch = au ? 2 * p.batch : p.batch;
+    for (int i = threadIdx.x; i <= nch; i += NT) {
+        s_off[i] = p.tab[i];
+        if (i < nch) s_len[i] = p.tab[TAB + i];
+        if (i < p.batch) s_smp[i] = p.tab[2 * TAB + i];
+    }
+    __syncthreads();
+    const uint32_t total = s_off[nch];
+    const uint32_t npiece = (total + 15u) >> 4;
+    const uint32_t hlen = static_cast<uint32_t>(p.hlen);
+
+    // one byte of chunk c at offset o of the chunk (header included)
+    auto byte_at = [&](int c, uint32_t o) -> uint32_t {
+        const bool video = !au || (c & 1);
+        const int k = au ? c >> 1 : c;
+        const uint32_t len = s_len[c];
+        if (o < 4) return ((video ? FCC_VIDEO : FCC_AUDIO) >> (8 * o)) & 0xFFu;
+        if (o < 8) return (len >> (8 * (o - 4))) & 0xFFu;
+        const uint32_t q = o - 8;
+        if (q >= len) return 0u;                                                        // the pad byte
+        if (video) return q < hlen ? p.hdr[q] : p.slab[static_cast<size_t>(k) * p.cap + (q - hlen)];
+        if (p.fmt == LSPAVI_AUDIO_F32) return reinterpret_cast<const unsigned char *>(p.wave)[static_cast<size_t>(s_smp[k]) * 4 + q];
+        return (pcm16(p.wave[static_cast<size_t>(s_smp[k]) + (q >> 1)]) >> (8 * (q & 1))) & 0xFFu;
+    };
+
+    for (uint32_t piece = blockIdx.x * NT + threadIdx.x; piece < npiece; piece += gridDim.x * NT) {
+        const uint32_t pos = piece << 4;
+        int lo = 0, hi = nch - 1;
+        while (lo < hi) {                                                               // the last chunk that starts at or before pos
+            const int mid = (lo + hi + 1) >> 1;
+            if (s_off[mid] <= pos) lo = mid; else hi = mid - 1;
+        }
+        const int c = lo;
+        const uint32_t o = pos - s_off[c], len = s_len[c];
+        const bool video = !au || (c & 1);
+        const int k = au ? c >> 1 : c;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        bool done = false;
+        if (o >= 8 && o + 16 <= 8 + len) {                                              // all 16 bytes are payload of this chunk
+            const uint32_t q = o - 8;
+            if (video) {
+                if (q + 16 <= hlen) {
+                    v = load16(p.hdr, q);
+                    done = true;
+                } else if (q >= hlen) {
+                    v = load16(p.slab, static_cast<size_t>(k) * p.cap + (q - hlen));
+                    done = true;
+                }
+            } else if (p.fmt == LSPAVI_AUDIO_F32) {
+                v = load16(reinterpret_cast<const unsigned char *>(p.wave), static_cast<size_t>(s_smp[k]) * 4 + q);
+                done = true;
+            } else {                                                                    // chunk starts are even, so q is: 8 whole samples
+                const float *w = p.wave + static_cast<size_t>(s_smp[k]) + (q >> 1);
+                v = make_uint4(pcm16(w[0]) | (pcm16(w[1]) << 16), pcm16(w[2]) | (pcm16(w[3]) << 16),
+                               pcm16(w[4]) | (pcm16(w[5]) << 16), pcm16(w[6]) | (pcm16(w[7]) << 16));
+                done = true;
+            }
+        }
+        if (!done) {                                                                    // a seam: byte by byte, over at most two chunks
+            uint32_t w[4] = {0u, 0u, 0u, 0u};
+            int cc = c;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const uint32_t b = pos + j;
+                if (b < total) {
+                    while (b >= s_off[cc + 1]) ++cc;
+                    w[j >> 2] |= byte_at(cc, b - s_off[cc]) << (8 * (j & 3));
+                }
+            }
+            v = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        if (pos + 16 <= total) {
+            *reinterpret_cast<uint4 *>(p.out + pos) = v;
+        } else {                                                                        // the fragment's end: total is even, so 2..14 bytes
+            const uint32_t r = total - pos;
+            uint32_t *o32 = reinterpret_cast<uint32_t *>(p.out + pos);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            const uint32_t nd = r >> 2;
+            for (uint32_t j = 0; j < nd; ++j) o32[j] = w[j];
+            if (r & 2u) *reinterpret_cast<unsigned short *>(p.out + pos + 4 * nd) = static_cast<unsigned short>(w[nd] & 0xFFFFu);
+        }
+    }
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------
+static thread_local std::string g_err;
+static int fail(int code, const std::string &msg)
+{
+    g_err = msg;
+    return code;
+}
+
+static bool format_ok(int f) { return f == LSPAVI_AUDIO_NONE || f == LSPAVI_AUDIO_S16 || f == LSPAVI_AUDIO_F32; }
+
+}  // namespace lspavi
+
+using namespace lspavi;
+
+extern "C" {
+
+const char *lspavi_last_error(void) { return g_err.c_str(); }
+
+size_t lspavi_capacity_bytes(int jpeg_header_len, size_t jpeg_capacity, int batch, int audio_format, int rate, int fps)
+{
+    if (jpeg_header_len < 2 || jpeg_header_len > 65536 || jpeg_capacity < 2 || jpeg_capacity > (size_t)1 << 31 || batch < 1 ||
+        batch > LSPAVI_MAX_BATCH || !format_ok(audio_format) || rate < 1 || fps < 1 || rate > 1 << 24 || fps > 1 << 16)
+        return 0;
+    size_t n = static_cast<size_t>(batch) * (8 + static_cast<size_t>(jpeg_header_len) + jpeg_capacity + 1);
+    if (audio_format != LSPAVI_AUDIO_NONE)
+        n += static_cast<size_t>(batch) * 8 +
+             (static_cast<size_t>(batch) * rate / fps + 1) * (audio_format == LSPAVI_AUDIO_F32 ? 4 : 2);
+    return (n + 15) & ~static_cast<size_t>(15);
+}
+
+size_t lspavi_workspace_bytes(int batch)
+{
+    return batch >= 1 && batch <= LSPAVI_MAX_BATCH ? 3 * TAB * sizeof(uint32_t) : 0;
+}
+
+int lspavi_pack(const unsigned char *jpeg_header_dev, int jpeg_header_len, const unsigned char *jpeg_dev, size_t jpeg_capacity,
+                const uint32_t *sizes_dev, int batch, const float *wave_dev, int64_t wave_samples, int64_t frame0, int rate, int fps,
+                int audio_format, unsigned char *out_dev, size_t out_capacity, uint32_t *index_dev, uint32_t *status_dev,
+                void *workspace_dev, size_t workspace_bytes, void *hip_stream)
+{
+    if (!jpeg_header_dev || !jpeg_dev || !sizes_dev || !out_dev || !index_dev || !status_dev || !workspace_dev)
+        return fail(LSPAVI_ERR_INVALID_ARGUMENT, "null argument");
+    if (batch < 1 || batch > LSPAVI_MAX_BATCH) return fail(LSPAVI_ERR_INVALID_ARGUMENT, "batch must be in 1..64");
+    if (!format_ok(audio_format)) return fail(LSPAVI_ERR_INVALID_ARGUMENT, "audio_format must be 0 (none), 1 (s16) or 3 (f32)");
+    if ((wave_dev != nullptr) != (audio_format != LSPAVI_AUDIO_NONE))
+        return fail(LSPAVI_ERR_INVALID_ARGUMENT, "a waveform needs an audio format, and an audio format a waveform");
+    const size_t need = lspavi_capacity_bytes(jpeg_header_len, jpeg_capacity, batch, audio_format, rate, fps);
+    if (need == 0) return fail(LSPAVI_ERR_INVALID_ARGUMENT, "jpeg_header_len, jpeg_capacity, rate or fps out of range");
+    if (need > 0xFFFFFFF0u) return fail(LSPAVI_ERR_UNSUPPORTED, "a fragment of " + std::to_string(need) + " bytes passes 32-bit offsets");
+    if (out_capacity < need) return fail(LSPAVI_ERR_INVALID_ARGUMENT, "out_dev needs " + std::to_string(need) + " bytes");
+    if (workspace_bytes < lspavi_workspace_bytes(batch))
+        return fail(LSPAVI_ERR_INVALID_ARGUMENT, "workspace needs " + std::to_string(lspavi_workspace_bytes(batch)) + " bytes");
+    if (reinterpret_cast<uintptr_t>(out_dev) % 16 || reinterpret_cast<uintptr_t>(index_dev) % 16 ||
+        reinterpret_cast<uintptr_t>(status_dev) % 16 || reinterpret_cast<uintptr_t>(workspace_dev) % 16)
+        return fail(LSPAVI_ERR_INVALID_ARGUMENT, "out_dev, index_dev, status_dev and workspace_dev must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(jpeg_header_dev) % 4 || reinterpret_cast<uintptr_t>(jpeg_dev) % 4 ||
+        reinterpret_cast<uintptr_t>(wave_dev) % 4)
+        return fail(LSPAVI_ERR_INVALID_ARGUMENT, "jpeg_header_dev, jpeg_dev and wave_dev must be 4-byte aligned");
+    if (frame0 < 0 || frame0 > ((int64_t)1 << 31)) return fail(LSPAVI_ERR_INVALID_ARGUMENT, "frame0 must be in 0..2^31");
+    if (wave_dev) {
+        const int64_t last = (frame0 + batch) * rate / fps;
+        if (wave_samples < 0 || wave_samples > ((int64_t)1 << 31))
+            return fail(LSPAVI_ERR_INVALID_ARGUMENT, "wave_samples must be in 0..2^31");
+        if (last > wave_samples)
+            return fail(LSPAVI_ERR_INVALID_ARGUMENT, "frames " + std::to_string(frame0) + ".." + std::to_string(frame0 + batch - 1) +
+                                                         " need " + std::to_string(last) + " samples, the waveform has " +
+                                                         std::to_string(wave_samples));
+    }
+    Params p{};
+    p.hdr = jpeg_header_dev;
+    p.slab = jpeg_dev;
+    p.sizes = sizes_dev;
+    p.wave = wave_dev;
+    p.out = out_dev;
+    p.index = index_dev;
+    p.status = status_dev;
+    p.tab = static_cast<uint32_t *>(workspace_dev);
+    p.cap = jpeg_capacity;
+    p.frame0 = frame0;
+    p.hlen = jpeg_header_len;
+    p.batch = batch;
+    p.rate = rate;
+    p.fps = fps;
+    p.fmt = audio_format;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    size_t blocks = (need / 16 + NT - 1) / NT;
+    if (blocks > MAX_BLOCKS) blocks = MAX_BLOCKS;
+    hipLaunchKernelGGL(avi_layout, dim3(1), dim3(64), 0, st, p);
+    hipLaunchKernelGGL(avi_gather, dim3(static_cast<unsigned>(blocks)), dim3(NT), 0, st, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(LSPAVI_ERR_HIP, std::string("avi launch: ") + hipGetErrorString(e));
+    return LSPAVI_OK;
+}
+
+}  // extern "C"

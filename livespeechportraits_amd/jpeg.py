@@ -105,6 +105,24 @@ class JpegEncoder:
             self._sizes_host[:b].copy_(self._sizes[:b], non_blocking=True)
         self._pending = (b, stream)
 
+    @property
+    def slab(self):
+        """(output ``[max_batch, capacity]`` uint8, byte counts ``[max_batch]`` int32): what lspjpeg_encode leaves on the device, for a
+        consumer that stays there (video.DeviceMuxer).  Read-only: the encoder writes them."""
+        return self._dst, self._sizes
+
+    def enqueue(self, frames: torch.Tensor) -> int:
+        """The encode alone on the current stream, into ``slab``: no copy to the host, nothing for collect() to hand out.  Returns the batch."""
+        if self._pending is not None:
+            raise RuntimeError("collect() the previous batch first: the encoder's buffers are still in use")
+        b = self._check(frames)
+        stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            N.check_jpeg(self.lib.lspjpeg_encode(self._h, ctypes.c_void_p(frames.data_ptr()), b, ctypes.c_void_p(self._dst.data_ptr()),
+                                                 ctypes.c_void_p(self._sizes.data_ptr()), ctypes.c_void_p(self._ws.data_ptr()), self._ws_bytes,
+                                                 ctypes.c_void_p(stream.cuda_stream)))
+        return b
+
     def collect(self) -> List[bytes]:
         """Wait for the submitted batch, copy exactly its compressed bytes to pinned memory, return one file per frame."""
         if self._pending is None:

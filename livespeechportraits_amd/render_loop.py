@@ -28,7 +28,7 @@ def batched(it: Iterable, n: int) -> Iterator[List]:
 def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch.Tensor, batch: int = 8,
                   device: Optional[torch.device] = None,
                   on_frame: Optional[Callable[[int, np.ndarray], None]] = None, streams: int = 2,
-                  jpeg_quality: Optional[int] = None) -> List[np.ndarray]:
+                  jpeg_quality: Optional[int] = None, video=None, audio=None, video_route: Optional[str] = None) -> List[np.ndarray]:
     """``feature_maps`` yields [1,H,W] (or [C,H,W]) CPU/GPU tensors as
     ``facedataset.dataset.get_data_test_mode`` does (demo.py:262); ``cand_image`` is demo.py's
     ``img_candidates`` ([1,12,H,W], already on the device).  Returns (or streams to ``on_frame``) uint8 HWC
@@ -46,13 +46,27 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
 
     ``jpeg_quality`` (1..100, Pillow's default is 75): every lane encodes its frames on its own stream right behind the generator (jpeg.JpegEncoder,
     include/lspjpeg.h) and the frames are handed out as complete JPEG files (``bytes``, what demo.py:271's save_images writes as pred_<n>.jpg); only the
-    compressed bytes cross PCIe.  There is no host encoder: a model on the host with ``jpeg_quality`` raises."""
+    compressed bytes cross PCIe.  There is no host encoder: a model on the host with ``jpeg_quality`` raises.
+
+    ``video`` (a video.AviWriter; demo.py:275-285): the encoded frames go into that Motion-JPEG AVI instead of being handed out -- each lane muxes its batch
+    on the device behind the encoder (video.DeviceMuxer, include/lspavi.h) and the fragments are appended in frame order; ``jpeg_quality`` defaults to 75,
+    the function returns [] (``on_frame(i, None)`` is still called per frame).  ``audio``: the CLIP's float32 waveform at the writer's rate (tensor or
+    array), required exactly when the writer has an audio stream; frame k of the file carries its samples [k * rate // fps, (k + 1) * rate // fps).
+    ``video_route`` "device" / "host" (JpegEncoder.collect + AviWriter.append_jpegs) overrides video.DEFAULT_VIDEO_ROUTE; both write the same file."""
     device = device or cand_image.device
     frames: List[np.ndarray] = []
     idx = 0
     on_gpu = device.type == "cuda"
+    if video is not None and jpeg_quality is None:
+        jpeg_quality = 75
     if jpeg_quality is not None and not on_gpu:
         raise ValueError("jpeg_quality: the JPEG encoder runs on the device only, and this model renders on the host")
+    if video is not None:
+        from .video import VideoSink, clip_audio
+        audio_dev, audio_host = clip_audio(video, audio, device)
+        frame_base = video.nframes
+    elif audio is not None:
+        raise ValueError("audio is the sound track of ``video``: pass an AviWriter")
     nlane = max(1, int(streams)) if on_gpu and getattr(model, "supports_replicas", lambda: False)() else 1
     try:
         takes_out = "out" in inspect.signature(model.inference_image).parameters      # (stand-in models of the tests do not)
@@ -70,7 +84,11 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
     def drain(lane):
         if lane["busy"] is not None:
             i0, n = lane["busy"]
-            if lane["jpeg"] is not None:
+            if lane["sink"] is not None:
+                lane["sink"].collect()                          # waits for the lane's stream; one copy, appended to the file
+                if on_frame is not None:
+                    emit(i0, [None] * n)
+            elif lane["jpeg"] is not None:
                 emit(i0, lane["jpeg"].collect())                # waits for the lane's stream, then copies the compressed bytes only
             else:
                 (lane["stream"] if lane["stream"] is not None else torch.cuda.current_stream(device)).synchronize()
@@ -92,7 +110,7 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
                 st = torch.cuda.Stream(device) if nlane > 1 else None
                 if st is not None:
                     st.wait_stream(cur)                          # cand_image was produced there
-                lanes.append({"stream": st, "busy": None, "host": None, "u8": None, "jpeg": None,
+                lanes.append({"stream": st, "busy": None, "host": None, "u8": None, "jpeg": None, "sink": None,
                               "stage": torch.empty(shape, dtype=torch.float32, pin_memory=True), "dev": torch.empty(shape, dtype=torch.float32, device=device)})
                 lanes[-1]["stage_np"] = lanes[-1]["stage"].numpy()
         lane = lanes[n % nlane]
@@ -124,7 +142,11 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
                     lane["u8"] = torch.empty((batch, H, H, 3), dtype=torch.uint8, device=device)
                 kw["out"] = lane["u8"][:b]
             u8 = model.inference_image(lane["dev"][:b], cand_image, **kw)
-            if jpeg_quality is not None:
+            if video is not None:
+                if lane["sink"] is None:
+                    lane["sink"] = VideoSink(video, tuple(u8.shape[1:3]), jpeg_quality, device, batch, audio_dev, audio_host, video_route)
+                lane["sink"].submit(u8, frame_base + idx)       # on the lane's stream, behind the generator
+            elif jpeg_quality is not None:
                 if lane["jpeg"] is None:
                     from .jpeg import JpegEncoder
                     lane["jpeg"] = JpegEncoder(tuple(u8.shape[1:3]), 3, jpeg_quality, device, max_batch=batch)
@@ -154,21 +176,37 @@ class _null:
 def render_frames_from_landmarks(model, landmarks: Iterable, shoulders: Iterable, cand_image: torch.Tensor,
                                  pad=None, load_size: int = 512, batch: int = 8,
                                  on_frame: Optional[Callable[[int, np.ndarray], None]] = None,
-                                 jpeg_quality: Optional[int] = None, save_input: bool = False) -> List[np.ndarray]:
+                                 jpeg_quality: Optional[int] = None, save_input: bool = False, video=None, audio=None, video_input=None,
+                                 video_route: Optional[str] = None) -> List[np.ndarray]:
     """demo.py:260-272 with the edge map drawn on the device: per frame the loop moves the 73 landmarks and the shoulder
     points (~1.5 KB) instead of a host-rasterised 1 MiB feature map.  ``landmarks`` yields [73, 2] arrays (``pred_landmarks[i]``
     of demo.py:262), ``shoulders`` yields [n, 2] arrays (``pred_shoulders[i]``); ``pad`` as ``facedataset.dataset.image_pad``.
 
     ``jpeg_quality``: frames are encoded on the device behind the generator and handed out as JPEG files (``bytes``, see render_frames).
     ``save_input`` (``Image2Image.save_input``, demo.py:269-270): every frame is a ``(pred, input)`` pair, ``input`` the uint8 edge map
-    ``np.uint8(map * 255)`` -- written by the rasteriser in the same launch as the float map, and JPEG-encoded (grayscale) with ``jpeg_quality``."""
+    ``np.uint8(map * 255)`` -- written by the rasteriser in the same launch as the float map, and JPEG-encoded (grayscale) with ``jpeg_quality``.
+
+    ``video`` / ``audio`` / ``video_route`` as render_frames: the frames go into that AviWriter (``jpeg_quality`` defaults to 75) and the function returns [];
+    with ``save_input`` a second, grayscale writer for the edge maps may be passed as ``video_input`` (it gets the same ``audio`` if it has an audio stream)."""
     from .feature_map import FeatureMapRasteriser
     device = cand_image.device
+    if video is not None and jpeg_quality is None:
+        jpeg_quality = 75
+    if video_input is not None and not (save_input and video is not None):
+        raise ValueError("video_input is the edge maps' file: it needs save_input=True and video")
+    if video is None and audio is not None:
+        raise ValueError("audio is the sound track of ``video``: pass an AviWriter")
     if jpeg_quality is not None and device.type != "cuda":
         raise ValueError("jpeg_quality: the JPEG encoder runs on the device only")
     rast = None
     maps_buf = edge_buf = None
     enc = enc_in = None
+    sink = sink_in = None
+    if video is not None:
+        from .video import VideoSink, clip_audio
+        tracks = clip_audio(video, audio, device)
+        tracks_in = clip_audio(video_input, audio if video_input.has_audio else None, device) if video_input is not None else None
+        bases = (video.nframes, video_input.nframes if video_input is not None else 0)
 
     def chunks():
         nonlocal rast, maps_buf, edge_buf
@@ -189,6 +227,23 @@ def render_frames_from_landmarks(model, landmarks: Iterable, shoulders: Iterable
     for maps, edges in chunks():
         u8 = model.inference_image(maps, cand_image)
         b = u8.shape[0]
+        if video is not None:
+            if sink is None:
+                sink = VideoSink(video, tuple(u8.shape[1:3]), jpeg_quality, device, batch, tracks[0], tracks[1], video_route)
+                if video_input is not None:
+                    sink_in = VideoSink(video_input, load_size, jpeg_quality, device, batch, tracks_in[0], tracks_in[1], video_route)
+            sink.submit(u8, bases[0] + idx)
+            if sink_in is not None:
+                sink_in.submit(edges, bases[1] + idx)
+            # one batch at a time: the rasteriser's output tensors are reused, and collect() waits on the stream's own tail
+            sink.collect()
+            if sink_in is not None:
+                sink_in.collect()
+            if on_frame is not None:
+                for k in range(b):
+                    on_frame(idx + k, None)
+            idx += b
+            continue
         if jpeg_quality is not None:
             from .jpeg import JpegEncoder
             if enc is None:

@@ -1,0 +1,386 @@
+"""The video of demo.py:275-285 (``write_video_with_audio``) as a Motion-JPEG AVI: the JPEG files the render loop already encodes on the
+device (jpeg.py, byte-identical to Pillow's ``pred_<n>.jpg``) are the video chunks, and the clip's 16 kHz waveform is the audio stream.
+
+The reference reads every ``pred_<n>.jpg`` back, re-encodes it (DIVX) and muxes ``librosa.output.write_wav``'s float WAV in with an external
+program's ``-codec copy``; its audio stream is therefore float PCM, which is why ``f32`` is the default here.  We write ``MJPG`` holding the
+files themselves: no second lossy generation.
+
+Layout (AVI 1.0, little-endian, no OpenDML)::
+
+    RIFF 'AVI ' / LIST 'hdrl' (avih, LIST 'strl' video [, LIST 'strl' audio]) / LIST 'movi' (['01wb'] '00dc' per frame) / 'idx1'
+
+``AviWriter`` is host code (no device needed): the headers, the index, the 2 GiB rule, and ``append_jpegs`` which builds a batch's part
+of 'movi' from complete JPEG files.  ``DeviceMuxer`` builds the same bytes on the device (include/lspavi.h) behind ``lspjpeg_encode`` and
+brings them over in one copy; ``AviWriter.append_fragment`` takes them.  No player or demuxer can be run where this is built, so the
+container is pinned on the strict parser of tests/avi_parser.py and on Pillow decoding every chunk: it is *player-unpinned*.
+"""
+from __future__ import annotations
+
+import ctypes
+import struct
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+AUDIO_FORMATS = {"f32": (3, 4), "s16": (1, 2)}                  # name -> (wFormatTag, bytes per sample)
+# which route the render loops take when ``video`` is given: "device" (DeviceMuxer + append_fragment) or "host" (JpegEncoder.collect +
+# append_jpegs).  Set from profiles/avi_time.txt, see DESIGN.md section 20.
+DEFAULT_VIDEO_ROUTE = "device"
+
+
+class AviFull(RuntimeError):
+    """the append would take the file past ``max_bytes``: nothing was written; close this file and start another"""
+
+
+def frame_sample(frame: int, rate: int, fps: int) -> int:
+    """the first audio sample of ``frame``: frame k carries samples [k * rate // fps, (k + 1) * rate // fps)"""
+    return int(frame) * int(rate) // int(fps)
+
+
+def pcm16(x: np.ndarray) -> np.ndarray:
+    """the ``s16`` rule: rintf(x * 32767.0f) clamped to +-32767, NaN as 0"""
+    v = np.rint(np.asarray(x, np.float32) * np.float32(32767.0))
+    v = np.where(np.isnan(v), np.float32(0), np.clip(v, -32767, 32767))
+    return v.astype("<i2")
+
+
+def jpeg_geometry(data: bytes) -> Tuple[int, int, int]:
+    """(width, height, components) of a baseline JPEG file, from its SOF0 segment"""
+    at = 2
+    while at + 4 <= len(data) and data[at] == 0xFF:
+        marker, n = data[at + 1], int.from_bytes(data[at + 2:at + 4], "big")
+        if marker == 0xC0:
+            return int.from_bytes(data[at + 7:at + 9], "big"), int.from_bytes(data[at + 5:at + 7], "big"), data[at + 9]
+        if marker == 0xDA:
+            break
+        at += 2 + n
+    raise ValueError("no SOF0 segment before the scan: not a baseline JPEG file")
+
+
+class AviWriter:
+    """One Motion-JPEG AVI file.  ``channels`` 3 (colour files) or 1 (grayscale); ``audio_rate`` None for a file without an audio stream.
+    The header is written with placeholders at construction; ``close()`` writes 'idx1' and every size and count.  A context manager."""
+
+    def __init__(self, path: str, width: int, height: int, channels: int = 3, fps: int = 60, audio_rate: Optional[int] = 16000,
+                 audio_format: str = "f32", max_bytes: int = 2 ** 31 - 1):
+        if channels not in (1, 3):
+            raise ValueError("channels must be 3 (colour) or 1 (grayscale)")
+        if audio_format not in AUDIO_FORMATS:
+            raise ValueError("audio_format must be one of %s" % sorted(AUDIO_FORMATS))
+        if not (1 <= int(width) <= 65535 and 1 <= int(height) <= 65535 and int(fps) >= 1 and (audio_rate is None or int(audio_rate) >= 1)):
+            raise ValueError("width, height, fps and audio_rate must be positive (width and height below 65536)")
+        if not 0 < int(max_bytes) <= 2 ** 31 - 1:
+            raise ValueError("max_bytes must be in 1..2**31 - 1 (AVI 1.0: no OpenDML)")
+        self.path, self.width, self.height, self.channels, self.fps = path, int(width), int(height), int(channels), int(fps)
+        self.audio_rate = None if audio_rate is None else int(audio_rate)
+        self.audio_format = audio_format if self.audio_rate is not None else None
+        self.max_bytes = int(max_bytes)
+        self.nframes = self.nsamples = 0
+        self._movi = 0                                          # bytes of chunks in 'movi' so far
+        self._index = bytearray()
+        self._largest_video = self._largest_audio = 0
+        self._header_len = 326 if self.has_audio else 224       # bytes up to the first chunk
+        assert len(self._header()) == self._header_len
+        if self._riff_size(0, 0) > self.max_bytes:
+            raise AviFull("max_bytes=%d does not hold an empty file" % self.max_bytes)
+        self._f = open(path, "wb")
+        self._f.write(self._header())
+
+    # ---- layout ------------------------------------------------------------------------------------------------------------
+    @property
+    def has_audio(self) -> bool:
+        return self.audio_rate is not None
+
+    @property
+    def bytes_per_sample(self) -> int:
+        return AUDIO_FORMATS[self.audio_format][1] if self.has_audio else 0
+
+    def span(self, frame0: int, nframes: int) -> Tuple[int, int]:
+        """audio samples [first, last) of frames frame0 .. frame0 + nframes - 1 (0, 0 without audio)"""
+        if not self.has_audio:
+            return 0, 0
+        return frame_sample(frame0, self.audio_rate, self.fps), frame_sample(frame0 + nframes, self.audio_rate, self.fps)
+
+    def _riff_size(self, more_bytes: int, more_chunks: int) -> int:
+        """the RIFF chunk's size field if ``more_bytes`` of chunks in ``more_chunks`` chunks were appended and the file closed"""
+        return self._header_len - 8 + self._movi + more_bytes + 8 + len(self._index) + 16 * more_chunks
+
+    def _header(self) -> bytes:
+        """everything up to the first chunk of 'movi', from the current counts"""
+        W, H, fps, n = self.width, self.height, self.fps, self.nframes
+        bits = 24 if self.channels == 3 else 8
+        strl = [struct.pack("<4s4sIHHIIIIIIIIhhhh", b"vids", b"MJPG", 0, 0, 0, 0, 1, fps, 0, n, self._largest_video, 0xFFFFFFFF, 0, 0, 0, W, H),
+                struct.pack("<IiiHH4sIiiII", 40, W, H, 1, bits, b"MJPG", W * H * bits // 8, 0, 0, 0, 0)]
+        lists = [_list(b"strl", _chunk(b"strh", strl[0]) + _chunk(b"strf", strl[1]))]
+        if self.has_audio:
+            tag, align = AUDIO_FORMATS[self.audio_format]
+            strh = struct.pack("<4s4sIHHIIIIIIIIhhhh", b"auds", b"\0\0\0\0", 0, 0, 0, 0, 1, self.audio_rate, 0, self.nsamples, self._largest_audio,
+                               0xFFFFFFFF, align, 0, 0, 0, 0)
+            strf = struct.pack("<HHIIHHH", tag, 1, self.audio_rate, self.audio_rate * align, align, 8 * align, 0)
+            lists.append(_list(b"strl", _chunk(b"strh", strh) + _chunk(b"strf", strf)))
+        rate = -(-self._movi * fps // n) if n else 0
+        avih = struct.pack("<14I", int(round(1e6 / fps)), rate, 0, 0x110, n, 0, len(lists), max(self._largest_video, self._largest_audio), W, H, 0, 0, 0, 0)
+        hdrl = _list(b"hdrl", _chunk(b"avih", avih) + b"".join(lists))
+        body = b"AVI " + hdrl + b"LIST" + struct.pack("<I", 4 + self._movi) + b"movi"
+        return b"RIFF" + struct.pack("<I", self._riff_size(0, 0)) + body
+
+    # ---- appending ---------------------------------------------------------------------------------------------------------
+    def append_fragment(self, data, index, nframes: int, nsamples: int, largest_video: int, largest_audio: int = 0) -> None:
+        """Append bytes built elsewhere (DeviceMuxer.collect(), or another writer's append_jpegs): ``data`` the chunks of ``nframes`` frames
+        in file order, ``index`` uint32 [chunks][4] (ckid, flags, offset relative to ``data``'s start, unpadded length)."""
+        if self._f is None:
+            raise ValueError("the file is closed")
+        data = memoryview(data).cast("B") if not isinstance(data, np.ndarray) else memoryview(np.ascontiguousarray(data, np.uint8)).cast("B")
+        index = np.ascontiguousarray(index, dtype="<u4").reshape(-1, 4)
+        nframes, nsamples = int(nframes), int(nsamples)
+        first, last = self.span(self.nframes, nframes)
+        if index.shape[0] != nframes * (2 if self.has_audio else 1):
+            raise ValueError("%d index entries for %d frames of a file %s audio" % (index.shape[0], nframes, "with" if self.has_audio else "without"))
+        if nsamples != last - first:
+            raise ValueError("frames %d..%d carry %d samples, the fragment has %d" % (self.nframes, self.nframes + nframes - 1, last - first, nsamples))
+        if len(data) & 1:
+            raise ValueError("a fragment's length is even (chunks are padded)")
+        if nframes and (int(index[0, 2]) != 0 or int(index[-1, 2]) + 8 + int(index[-1, 3]) + (int(index[-1, 3]) & 1) != len(data)):
+            raise ValueError("the index does not span the fragment")
+        if self._riff_size(len(data), index.shape[0]) > self.max_bytes:
+            raise AviFull("%d more bytes take the file past max_bytes=%d: close it and start another" % (len(data), self.max_bytes))
+        index = index.copy()
+        index[:, 2] += np.uint32(4 + self._movi)                # 'idx1' offsets count from the 'movi' fourcc
+        self._f.write(data)
+        self._index += index.tobytes()
+        self._movi += len(data)
+        self.nframes += nframes
+        self.nsamples += nsamples
+        self._largest_video = max(self._largest_video, int(largest_video))
+        self._largest_audio = max(self._largest_audio, int(largest_audio))
+
+    def build_fragment(self, files: Sequence[bytes], samples=None):
+        """What append_fragment takes, for the next ``len(files)`` frames, built on the host from complete JPEG files."""
+        files = [bytes(f) for f in files]
+        first, last = self.span(self.nframes, len(files))
+        if self.has_audio:
+            if samples is None:
+                raise ValueError("this file has an audio stream: frames %d..%d need %d samples" % (self.nframes, self.nframes + len(files) - 1, last - first))
+            samples = np.ascontiguousarray(np.asarray(samples), dtype=np.float32).reshape(-1)
+            if samples.shape[0] != last - first:
+                raise ValueError("frames %d..%d carry %d samples, got %d" % (self.nframes, self.nframes + len(files) - 1, last - first, samples.shape[0]))
+            pcm = samples.astype("<f4") if self.audio_format == "f32" else pcm16(samples)
+        elif samples is not None:
+            raise ValueError("this file has no audio stream")
+        out, index = bytearray(), []
+        largest_video = largest_audio = 0
+        for k, f in enumerate(files):
+            if len(f) < 4 or f[:2] != b"\xff\xd8" or f[-2:] != b"\xff\xd9":
+                raise ValueError("frame %d is not a complete JPEG file (SOI .. EOI)" % (self.nframes + k))
+            if jpeg_geometry(f) != (self.width, self.height, self.channels):
+                raise ValueError("frame %d is %dx%d with %d components, the file %dx%d with %d" % ((self.nframes + k,) + jpeg_geometry(f) +
+                                                                                                  (self.width, self.height, self.channels)))
+            if self.has_audio:
+                a, b = self.span(self.nframes + k, 1)
+                piece = pcm[a - first:b - first].tobytes()
+                index.append((0x62773130, 0x10, len(out), len(piece)))
+                out += b"01wb" + struct.pack("<I", len(piece)) + piece
+                largest_audio = max(largest_audio, len(piece))
+            index.append((0x63643030, 0x10, len(out), len(f)))
+            out += b"00dc" + struct.pack("<I", len(f)) + f + (b"\0" if len(f) & 1 else b"")
+            largest_video = max(largest_video, len(f))
+        return bytes(out), np.array(index, dtype="<u4").reshape(-1, 4), len(files), last - first, largest_video, largest_audio
+
+    def append_jpegs(self, files: Sequence[bytes], samples=None):
+        """Append complete JPEG files (Pillow's, JpegEncoder.encode's, LivePortraitPool.tick(jpeg_quality=...)'s) as the next frames;
+        ``samples``: float32, exactly the samples those frames carry (``span``).  Returns the fragment it appended."""
+        fragment = self.build_fragment(files, samples)
+        self.append_fragment(*fragment)
+        return fragment
+
+    # ---- closing -----------------------------------------------------------------------------------------------------------
+    def close(self) -> None:
+        if self._f is None:
+            return
+        f, self._f = self._f, None
+        try:
+            f.write(b"idx1" + struct.pack("<I", len(self._index)) + bytes(self._index))
+            f.seek(0)
+            f.write(self._header())
+        finally:
+            f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _chunk(fourcc: bytes, payload: bytes) -> bytes:
+    return fourcc + struct.pack("<I", len(payload)) + payload + (b"\0" if len(payload) & 1 else b"")
+
+
+def _list(kind: bytes, body: bytes) -> bytes:
+    return b"LIST" + struct.pack("<I", 4 + len(body)) + kind + body
+
+
+def write_avi(path: str, jpegs: Sequence[bytes], waveform=None, fps: int = 60, audio_rate: int = 16000, audio_format: str = "f32",
+              batch: int = 64) -> int:
+    """Write files the caller already holds (``render_frames(..., jpeg_quality=75)``) as one AVI; ``waveform``: the clip's float32 samples at
+    ``audio_rate`` (None: no audio stream), at least ``len(jpegs) * audio_rate // fps`` of them.  Returns the frame count."""
+    jpegs = list(jpegs)
+    if not jpegs:
+        raise ValueError("no frames: the geometry of the file comes from the first one")
+    w, h, c = jpeg_geometry(bytes(jpegs[0]))
+    wave = None if waveform is None else np.asarray(waveform, dtype=np.float32).reshape(-1)
+    with AviWriter(path, w, h, c, fps, audio_rate if wave is not None else None, audio_format) as out:
+        for k in range(0, len(jpegs), batch):
+            part = jpegs[k:k + batch]
+            a, b = out.span(k, len(part))
+            if wave is not None and b > wave.shape[0]:
+                raise ValueError("%d frames need %d samples, the waveform has %d" % (k + len(part), b, wave.shape[0]))
+            out.append_jpegs(part, None if wave is None else wave[a:b])
+        return out.nframes
+
+
+class DeviceMuxer:
+    """``lspjpeg_encode`` then ``lspavi_pack`` (include/lspavi.h) on the current stream: a batch of uint8 device frames becomes its part of
+    the file's 'movi' list on the device -- chunk headers, the JPEG header, the entropy-coded bytes, pad bytes and the interleaved audio -- and
+    crosses PCIe in ONE copy with its index entries.  Owns the fragment buffer, workspace, index and status tensors and their pinned mirrors;
+    uses ``encoder``'s output slab, so the encoder must not be used on its own while a batch is in flight here."""
+
+    def __init__(self, encoder, audio_format: Optional[str] = "f32", rate: int = 16000, fps: int = 60):
+        import torch
+        from . import _native as N
+        if audio_format is not None and audio_format not in AUDIO_FORMATS:
+            raise ValueError("audio_format must be one of %s or None" % sorted(AUDIO_FORMATS))
+        if encoder.max_batch > N.AVI_MAX_BATCH:
+            raise ValueError("the muxer packs at most %d frames per call (encoder.max_batch = %d)" % (N.AVI_MAX_BATCH, encoder.max_batch))
+        self.N, self.lib, self.enc = N, N.load(), encoder
+        self.audio_format, self.rate, self.fps, self.device = audio_format, int(rate), int(fps), encoder.device
+        B = encoder.max_batch
+        fmt = N.AVI_AUDIO_FORMATS[audio_format]
+        self.capacity = int(self.lib.lspavi_capacity_bytes(len(encoder.header), encoder.capacity, B, fmt, self.rate, self.fps))
+        self._ws_bytes = int(self.lib.lspavi_workspace_bytes(B))
+        if self.capacity == 0 or self._ws_bytes == 0:
+            raise ValueError("lspavi: geometry, batch, rate or fps out of range")
+        dev = self.device
+        self._header = torch.frombuffer(bytearray(encoder.header + b"\0" * (-len(encoder.header) % 4)), dtype=torch.uint8).to(dev)
+        self._out = torch.empty(self.capacity, dtype=torch.uint8, device=dev)
+        self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=dev)
+        self._meta = torch.empty((1 + 2 * B, 4), dtype=torch.int32, device=dev)        # row 0: the status block; then the index
+        self._meta_host = torch.empty((1 + 2 * B, 4), dtype=torch.int32, pin_memory=True)
+        self._host = torch.empty(0, dtype=torch.uint8)
+        self._pending = None
+
+    def submit(self, frames, frame0: int, audio_dev=None) -> None:
+        """Enqueue the encode, the pack and the copy of the status block and the index on the current stream.  ``frame0``: the clip's
+        number of frames[0]; ``audio_dev``: the CLIP's float32 waveform on the device (None: no audio chunks).  A waveform too short for the
+        batch's last sample is refused by lspavi_pack on the host (LspaviError): no pack is enqueued and nothing is left to collect."""
+        import torch
+        if self._pending is not None:
+            raise RuntimeError("collect() the previous batch first: the muxer's buffers are still in use")
+        c = ctypes.c_void_p
+        fmt, wave, nwave = 0, None, 0
+        if audio_dev is not None:
+            if self.audio_format is None:
+                raise ValueError("this muxer was made without an audio format")
+            ok = isinstance(audio_dev, torch.Tensor) and audio_dev.dim() == 1 and audio_dev.dtype == torch.float32 \
+                and audio_dev.device == self.device and audio_dev.is_contiguous()
+            if not ok:
+                raise ValueError("audio_dev must be a contiguous 1-D float32 tensor on %s" % self.device)
+            fmt, wave, nwave = self.N.AVI_AUDIO_FORMATS[self.audio_format], audio_dev.data_ptr(), audio_dev.shape[0]
+        b = self.enc.enqueue(frames)
+        stream = torch.cuda.current_stream(self.device)
+        dst, sizes = self.enc.slab
+        with torch.cuda.device(self.device):
+            self.N.check_avi(self.lib.lspavi_pack(
+                c(self._header.data_ptr()), len(self.enc.header), c(dst.data_ptr()), self.enc.capacity, c(sizes.data_ptr()), b,
+                c(wave), nwave, int(frame0), self.rate, self.fps, fmt, c(self._out.data_ptr()), self.capacity,
+                c(self._meta[1:].data_ptr()), c(self._meta.data_ptr()), c(self._ws.data_ptr()), self._ws_bytes, c(stream.cuda_stream)))
+            n = 1 + (2 * b if fmt else b)
+            self._meta_host[:n].copy_(self._meta[:n], non_blocking=True)
+        self._pending = (b, fmt != 0, int(frame0), stream)
+
+    def collect(self):
+        """Wait for the submitted batch, copy exactly the fragment's bytes in one copy; returns ``(data, index, nframes, nsamples,
+        largest_video, largest_audio)``, what AviWriter.append_fragment takes.  ``data`` is a view of pinned memory, valid until the next
+        collect()."""
+        import torch
+        if self._pending is None:
+            raise RuntimeError("nothing submitted")
+        b, audio, frame0, stream = self._pending
+        self._pending = None
+        stream.synchronize()
+        meta = self._meta_host.numpy().view(np.uint32)
+        total, nchunk, largest_video, largest_audio = (int(v) for v in meta[0])
+        if nchunk != (2 * b if audio else b) or not 0 < total <= self.capacity or total & 1:
+            raise RuntimeError("lspavi_pack returned %d bytes in %d chunks for %d frames (capacity %d)" % (total, nchunk, b, self.capacity))
+        if self._host.numel() < total:
+            self._host = torch.empty(max(total, 2 * self._host.numel()), dtype=torch.uint8, pin_memory=True)
+        with torch.cuda.stream(stream):
+            self._host[:total].copy_(self._out[:total], non_blocking=True)
+        stream.synchronize()
+        nsamples = frame_sample(frame0 + b, self.rate, self.fps) - frame_sample(frame0, self.rate, self.fps) if audio else 0
+        return self._host.numpy()[:total], meta[1:1 + nchunk].copy(), b, nsamples, largest_video, largest_audio
+
+
+def clip_audio(video: AviWriter, audio, device):
+    """The render loops' ``audio`` argument (the CLIP's float32 waveform at the writer's rate: a tensor anywhere, or an array) as
+    (contiguous device tensor, host array); (None, None) for a writer without an audio stream.  Frame k of the FILE carries samples
+    [k * rate // fps, (k + 1) * rate // fps) of it."""
+    import torch
+    if not video.has_audio:
+        if audio is not None:
+            raise ValueError("audio given, but the AviWriter was made with audio_rate=None")
+        return None, None
+    if audio is None:
+        raise ValueError("the AviWriter has an audio stream: pass the clip's waveform as audio (or make the writer with audio_rate=None)")
+    t = audio if isinstance(audio, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(audio), dtype=np.float32))
+    t = t.detach().reshape(-1).to(torch.float32)
+    return t.to(device).contiguous(), t.cpu().numpy()
+
+
+class VideoSink:
+    """What one lane of a render loop puts behind its generator when ``video`` is given: submit() a batch of uint8 device frames on the
+    current stream, collect() it into the writer.  ``route`` "device": DeviceMuxer + append_fragment (one copy per batch); "host":
+    JpegEncoder.submit / collect + append_jpegs (one copy per frame, the fragment built on the host).  Both write the same bytes."""
+
+    def __init__(self, video: AviWriter, size, quality: int, device, max_batch: int, audio_dev=None, audio_host=None, route: Optional[str] = None):
+        from .jpeg import JpegEncoder
+        route = route or DEFAULT_VIDEO_ROUTE
+        if route not in ("device", "host"):
+            raise ValueError("video_route must be 'device' or 'host'")
+        size = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+        if (size[1], size[0]) != (video.width, video.height):
+            raise ValueError("the frames are %dx%d, the AviWriter %dx%d" % (size[1], size[0], video.width, video.height))
+        self.video, self.route, self.audio_dev, self.audio_host = video, route, audio_dev, audio_host
+        self.enc = JpegEncoder(size, video.channels, quality, device, max_batch=max_batch)
+        self.mux = DeviceMuxer(self.enc, video.audio_format, video.audio_rate or 16000, video.fps) if route == "device" else None
+        self._frame0 = None
+
+    def submit(self, frames, frame0: int) -> None:
+        if self.mux is not None:
+            self.mux.submit(frames, frame0, self.audio_dev)
+        else:
+            a, b = self.video.span(frame0, int(frames.shape[0]))
+            if self.audio_host is not None and b > self.audio_host.shape[0]:
+                raise ValueError("frames %d..%d need %d samples, the waveform has %d" % (frame0, frame0 + frames.shape[0] - 1, b, self.audio_host.shape[0]))
+            self.enc.submit(frames)
+        self._frame0 = int(frame0)
+
+    def collect(self) -> int:
+        """the submitted batch, appended to the writer (in the order of the calls: the caller drains its lanes oldest first)"""
+        if self._frame0 != self.video.nframes:
+            raise RuntimeError("batch of frame %s collected when the file holds %d frames: fragments must be appended in frame order" % (self._frame0, self.video.nframes))
+        if self.mux is not None:
+            fragment = self.mux.collect()
+            self.video.append_fragment(*fragment)
+            return fragment[2]
+        files = self.enc.collect()
+        a, b = self.video.span(self._frame0, len(files))
+        self.video.append_jpegs(files, None if self.audio_host is None else self.audio_host[a:b])
+        return len(files)
