@@ -66,6 +66,53 @@ int lspavi_pack(const unsigned char *jpeg_header_dev, int jpeg_header_len, const
                 int audio_format, unsigned char *out_dev, size_t out_capacity, uint32_t *index_dev, uint32_t *status_dev,
                 void *workspace_dev, size_t workspace_bytes, void *hip_stream);
 
+/* ---- many files from one batch: live sessions (livespeechportraits_amd/live_render.py) ------------------------------------------------
+ * lspavi_pack_multi() splits one encoded batch into at most LSPAVI_MAX_STREAMS runs.  A run is the consecutive frames
+ * [first, first + count) of the batch, count >= 1; runs are ascending and cover the batch.  Every run is a fragment of a file of its own:
+ * its bytes and its index entries (offsets relative to its own start) are exactly what lspavi_pack() writes for those frames alone from a
+ * linear waveform.  The audio of a run comes from a ring: stream sample i lives at ring_dev[i % ring_samples], and the file's frame k carries
+ * stream samples sample0 + [s(k), s(k + 1)), s as above on the FILE's frame numbers -- so a file may begin at any stream frame.
+ * The host side of the call refuses a run whose span sample0 + [s(frame0), s(frame0 + count)) leaves [avail_begin, avail_end) or is longer
+ * than the ring, and launches nothing then: the device never reads a sample the caller did not vouch for.
+ *
+ * Output: run j's fragment starts at a 16-byte-aligned offset of out_dev (status row j).  Every byte below a fragment's length is written
+ * exactly once, by one lane; the up to 14 bytes between a fragment's end and the next fragment's start and everything above the last
+ * fragment are never touched.  Still two launches per call, whatever the number of runs.
+ *
+ * Output bound (lspavi_capacity_bytes_multi), a multiple of 16: lspavi_pack's bound with the audio term at 4 bytes per sample, plus per run
+ * 16 bytes (alignment) and 4 bytes (each run may round one sample up):
+ *     batch * (8 + jpeg_header_len + jpeg_capacity + 1)  +  batch * 8 + (batch * rate / fps + 1) * 4  +  runs * 20 */
+#define LSPAVI_MAX_STREAMS 16
+
+typedef struct lspavi_run {
+    int32_t first, count;        /* frames [first, first + count) of the batch */
+    int32_t audio_format;        /* LSPAVI_AUDIO_*, per run: the files belong to the caller */
+    int32_t reserved;            /* 0 */
+    int64_t frame0;              /* the FILE's number of the run's first frame, 0..2^31 */
+    const float *ring_dev;       /* float32 [ring_samples], 4-byte aligned; NULL with LSPAVI_AUDIO_NONE (the fields below are then ignored) */
+    int64_t ring_samples;        /* 1..2^31 */
+    int64_t sample0;             /* the stream sample of the first sample of the file's frame 0, >= 0 */
+    int64_t avail_begin, avail_end; /* the ring holds stream samples [avail_begin, avail_end), at most ring_samples of them */
+} lspavi_run;
+
+/* uint32 per status row: offset of the fragment in out_dev, fragment bytes, chunk count, largest video chunk, largest audio chunk
+ * (unpadded lengths), the fragment's first row in index_dev, 0, 0 */
+#define LSPAVI_STATUS_WORDS 8
+
+/* 0 for arguments lspavi_pack_multi would refuse; no device is touched */
+size_t lspavi_capacity_bytes_multi(int jpeg_header_len, size_t jpeg_capacity, int batch, int runs, int rate, int fps);
+size_t lspavi_workspace_bytes_multi(int batch);
+
+/* As lspavi_pack, with:  runs        nruns entries, read during the call (they travel to the device as kernel arguments: nothing is uploaded)
+ *                        index_dev   uint32 [2 * batch][4]: the chunks of all runs in batch order; run j's rows start at its status row's
+ *                                    word 5, offsets relative to the run's own fragment
+ *                        status_dev  uint32 [nruns][LSPAVI_STATUS_WORDS]
+ *                        workspace   lspavi_workspace_bytes_multi(batch) bytes */
+int lspavi_pack_multi(const unsigned char *jpeg_header_dev, int jpeg_header_len, const unsigned char *jpeg_dev, size_t jpeg_capacity,
+                      const uint32_t *sizes_dev, int batch, const lspavi_run *runs, int nruns, int rate, int fps, unsigned char *out_dev,
+                      size_t out_capacity, uint32_t *index_dev, uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes,
+                      void *hip_stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

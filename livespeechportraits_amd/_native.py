@@ -346,8 +346,16 @@ LMK_SIGNATURES = {
     "lsplmk_check_tick": (c_int, [c_void_p, c_int, POINTER(LmkSessionCall)]),
 }
 
+class AviRun(Structure):
+    """lspavi_run (include/lspavi.h)"""
+    _fields_ = [(n, c_int32) for n in ("first", "count", "audio_format", "reserved")] + [("frame0", ctypes.c_int64), ("ring_dev", c_void_p)] + \
+               [(n, ctypes.c_int64) for n in ("ring_samples", "sample0", "avail_begin", "avail_end")]
+
+
 # every symbol include/lspavi.h declares
 AVI_MAX_BATCH = 64
+AVI_MAX_STREAMS = 16
+AVI_STATUS_WORDS = 8
 AVI_AUDIO_FORMATS = {None: 0, "s16": 1, "f32": 3}               # the WAVEFORMATEX wFormatTag
 AVI_SIGNATURES = {
     "lspavi_last_error": (c_char_p, []),
@@ -355,6 +363,10 @@ AVI_SIGNATURES = {
     "lspavi_workspace_bytes": (c_size_t, [c_int]),
     "lspavi_pack": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int,
                             c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "lspavi_capacity_bytes_multi": (c_size_t, [c_int, c_size_t, c_int, c_int, c_int, c_int]),
+    "lspavi_workspace_bytes_multi": (c_size_t, [c_int]),
+    "lspavi_pack_multi": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, POINTER(AviRun), c_int, c_int, c_int, c_void_p, c_size_t,
+                                  c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

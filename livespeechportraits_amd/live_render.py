@@ -10,7 +10,10 @@ layers is cached by the engine as in the render loop.  Inside a tick:
 4. the generator with fused ``tensor2im`` in groups of at most ``max_batch`` frames (``last_groups`` records them);
 5. JPEG when asked for.
 
-The only host copy is the last one, when ``host`` or ``jpeg_quality`` asks for it.  A frame leaves ``delay`` frames after its audio: the
+6. recording, for the sessions that have a writer: the frames of a tick are encoded and muxed in groups of at most ``max_batch``, one
+   fragment per file out of one ``lspavi_pack_multi`` call, the audio from per-session rings on the device.
+
+The only host copy is the last one, when ``host`` or ``jpeg_quality`` asks for it (and a recorded fragment's bytes).  A frame leaves ``delay`` frames after its audio: the
 audio models' lookahead (frame_future, ~18 frames) plus the largest filter radius of the landmark stage (or its ``max_lookahead``)."""
 from __future__ import annotations
 
@@ -21,9 +24,17 @@ class LivePortraitPool:
     """``audio``: a LiveSessionPool; ``stage``: a LandmarkStage on the same device with at least as many sessions; ``model``: a
     Feature2FaceModel (set up, eval); ``cand_image``: demo.py's ``img_candidates`` [1, 12, H, W] on the device.  ``max_batch``: frames per
     generator forward.  ``raster_chunk``: frames per rasteriser launch (one launch per tick unless a tick emits more: 1 MiB of map per
-    frame).  A tick may bring a session at most ``max_tick_samples`` samples: what the stage's rings (its ``max_push``) can take."""
+    frame).  A tick may bring a session at most ``max_tick_samples`` samples: what the stage's rings (its ``max_push``) can take.
 
-    def __init__(self, audio, stage, model, cand_image, load_size: int = 512, max_batch: int = 8, raster_chunk: int = 64):
+    ``record_quality`` (a JPEG quality) makes the pool able to record: it then keeps every session's last ``ring_samples`` samples on the
+    device, and ``open`` / ``record`` take AviWriters that ``tick`` appends the session's frames and their audio to.  ``record_route``
+    "device" (one lspavi_pack_multi per group of frames) or "host" (JpegEncoder + append_jpegs per session); both write the same files."""
+
+    fps = 60                                                                       # live.py: a clip of N samples has int(N / 16000 * 60) frames
+    rate = 16000
+
+    def __init__(self, audio, stage, model, cand_image, load_size: int = 512, max_batch: int = 8, raster_chunk: int = 64,
+                 record_quality: Optional[int] = None, record_route: Optional[str] = None):
         import torch
         from .feature_map import FeatureMapRasteriser
         self.torch = torch
@@ -49,16 +60,102 @@ class LivePortraitPool:
         self._jpeg: Dict[int, object] = {}                                         # quality -> JpegEncoder
         self.last_groups: List[List[Tuple[int, int]]] = []
         self.last_points = None
+        self.record_quality = self.record_route = None
+        self._rec: Dict[int, Dict[str, object]] = {}                               # session id -> {"video" / "video_input": LiveRecording}
+        self.recording_stopped: Dict[int, Exception] = {}                          # session id -> the AviFull that ended its recording
+        if record_quality is None:
+            if record_route is not None:
+                raise ValueError("record_route needs record_quality")
+            return
+        from . import video as V
+        if not 1 <= int(record_quality) <= 100:
+            raise ValueError("record_quality must be in 1..100")
+        self.record_route = record_route or V.DEFAULT_LIVE_RECORD_ROUTE
+        if self.record_route not in ("device", "host"):
+            raise ValueError("record_route must be 'device' or 'host'")
+        if self.max_batch > 64:
+            raise ValueError("a recording pool encodes at most 64 frames per group (max_batch = %d)" % self.max_batch)
+        self.record_quality = int(record_quality)
+        # the oldest frame a tick can emit: delay frames behind the audio, or the landmark filters' full radius while max_lookahead holds the first frames back
+        lag = max(audio.ff_mouth, audio.ff_head) + max(stage.radii)
+        self.ring_samples = V.live_ring_samples(lag, self.max_tick_samples, self.rate, self.fps)
+        self._ring = torch.zeros((audio.max_sessions, self.ring_samples), dtype=torch.float32, device=self.device)
+        self._book: Dict[int, object] = {}                                         # session id -> RingBook
+        self._emitted: Dict[int, int] = {}                                         # session id -> frames emitted so far
+        self._row: Dict[int, int] = {}                                             # session id -> its ring (the audio pool's slot, which it frees at finish)
+        self._mux: Dict[str, tuple] = {}                                           # "video" / "video_input" -> (JpegEncoder, DeviceMultiMuxer or None)
 
     # ---- sessions ----------------------------------------------------------------------------------------------------------------
-    def open(self, pre_headpose, generator=None) -> int:
+    def open(self, pre_headpose, generator=None, video=None, video_input=None, on_full=None) -> int:
+        """``video`` / ``video_input`` / ``on_full``: record the session from its first frame (see ``record``)"""
+        if video is None and (video_input is not None or on_full is not None):
+            raise ValueError("video_input and on_full go with video")
+        if video is not None:
+            self._check_recording(video, video_input)
         sid = self.audio.open(pre_headpose, generator)
         self._lm[sid] = self.stage.open()
+        if self.record_quality is not None:
+            from .video import RingBook
+            self._book[sid], self._emitted[sid], self._row[sid] = RingBook(self.ring_samples), 0, self.audio.plan.slot[sid]
+            self.recording_stopped.pop(sid, None)
+            if video is not None:
+                self.record(sid, video, video_input, on_full)
         return sid
 
     def close(self, sid: int) -> None:
         self.audio.close(sid)
         self.stage.close(self._lm.pop(sid))
+        self._forget(sid)
+
+    def _forget(self, sid: int) -> None:
+        self._rec.pop(sid, None)
+        if self.record_quality is not None:
+            self._book.pop(sid, None)
+            self._emitted.pop(sid, None)
+            self._row.pop(sid, None)
+
+    # ---- recording ---------------------------------------------------------------------------------------------------------------
+    def _check_writer(self, writer, which: str) -> None:
+        from .video import AviWriter
+        channels = 3 if which == "video" else 1
+        if not isinstance(writer, AviWriter) or writer._f is None:
+            raise ValueError("%s must be an open AviWriter" % which)
+        if (writer.width, writer.height, writer.channels, writer.fps) != (self.load_size, self.load_size, channels, self.fps):
+            raise ValueError("%s must be an AviWriter of %dx%d with %d channel(s) at %d fps (got %dx%d, %d, %d fps)" % (
+                which, self.load_size, self.load_size, channels, self.fps, writer.width, writer.height, writer.channels, writer.fps))
+        if writer.audio_rate not in (None, self.rate):
+            raise ValueError("%s: the audio stream of a live recording is %d Hz (or audio_rate=None), not %d" % (which, self.rate, writer.audio_rate))
+        if writer.nframes or writer.nsamples:
+            raise ValueError("%s already holds %d frames; a recording starts an empty file" % (which, writer.nframes))
+
+    def _check_recording(self, video, video_input) -> None:
+        if self.record_quality is None:
+            raise ValueError("this pool was made without record_quality: it cannot record")
+        self._check_writer(video, "video")
+        if video_input is not None:
+            self._check_writer(video_input, "video_input")
+
+    def record(self, sid: int, video, video_input=None, on_full=None) -> None:
+        """Record session ``sid`` from its next emitted frame: ``video`` an AviWriter of load_size x load_size x 3 at the pool's fps,
+        with a 16 kHz audio stream or none; ``video_input`` a grayscale one for the rasterised edge maps.  ``on_full(sid, which)`` (which:
+        "video" / "video_input") hands out the next writer when a file is full; without it the recording stops there
+        (``recording_stopped``).  The writers stay the caller's: ``tick`` appends to them, the caller closes them."""
+        from .video import LiveRecording
+        if sid not in self._lm:
+            self.audio.plan.check(sid)
+            raise KeyError("unknown session id %r" % (sid,))
+        self._check_recording(video, video_input)
+        if sid in self._rec:
+            raise ValueError("session %d is being recorded already: stop_recording() first" % sid)
+        at = self._emitted[sid]
+        self._rec[sid] = {"video": LiveRecording(sid, "video", video, on_full, at)}
+        if video_input is not None:
+            self._rec[sid]["video_input"] = LiveRecording(sid, "video_input", video_input, on_full, at)
+        self.recording_stopped.pop(sid, None)
+
+    def stop_recording(self, sid: int) -> None:
+        """no more frames go to the session's writers (the caller closes them)"""
+        self._rec.pop(sid, None)
 
     @property
     def open_sessions(self) -> List[int]:
@@ -82,6 +179,8 @@ class LivePortraitPool:
         if jpeg_quality is not None and not 1 <= int(jpeg_quality) <= 100:
             raise ValueError("jpeg_quality must be in 1..100")
         self._dry_run({sid: len(smp) for sid, smp in pairs}, finish)              # the landmark rings take this tick's rows, or nothing runs
+        if self.record_quality is not None:
+            pairs = self._to_rings(pairs)
         live = self.audio.tick(pairs, finish=finish, host=False)                  # 1. mouth rows and poses, on the device
         named = sorted(live)
         try:                                                                       # 2. one launch: the points of every final frame
@@ -99,11 +198,16 @@ class LivePortraitPool:
         H = self.load_size
         owner = [(sid, spans[sid][0] + i) for sid in named for i in range(spans[sid][2])]
         self.last_groups = []
+        recorded = [sid for sid in named if sid in self._rec and spans[sid][2]]
         with torch.cuda.device(self.device):
             frames = torch.empty((total, H, H, 3), dtype=torch.uint8, device=self.device)
+            edges = None
+            if any("video_input" in self._rec[sid] for sid in recorded):          # the {0, 255} maps of the same launch, for the gray files
+                edges = torch.empty((total, H, H), dtype=torch.uint8, device=self.device)
             for c0 in range(0, total, self.raster_chunk):
                 c1 = min(total, c0 + self.raster_chunk)
-                maps = self.raster.rasterise_points(pts[c0:c1], out=self._maps[:c1 - c0])            # 3. one launch over the emitted frames
+                maps = self.raster.rasterise_points(pts[c0:c1], out=self._maps[:c1 - c0],            # 3. one launch over the emitted frames
+                                                    out_u8=None if edges is None else edges[c0:c1])
                 for g0 in range(c0, c1, self.max_batch):                                            # 4. the generator, uint8 HWC out of its last kernel
                     g1 = min(c1, g0 + self.max_batch)
                     self.model.inference_image(maps[g0 - c0:g1 - c0], self.cand, out=frames[g0:g1])
@@ -122,9 +226,113 @@ class LivePortraitPool:
                 for sid in named:
                     start, a, n = spans[sid]
                     result[sid] = (start, data[a:a + n])
+            if recorded:                                                           # 6. the recorded sessions' frames, into their files
+                self._record_track("video", [(sid,) + spans[sid] for sid in recorded], frames)
+                self._record_track("video_input", [(sid,) + spans[sid] for sid in recorded], edges)
+        if self.record_quality is not None:
+            for sid in named:
+                self._emitted[sid] += spans[sid][2]
         for sid in finish:
             del self._lm[sid]
+            self._forget(sid)
         return result
+
+    def _to_rings(self, pairs):
+        """This tick's samples as ONE device tensor (one upload for all host arrays), appended to the sessions' rings in one index_copy_
+        whether or not a session is being recorded; -> the pairs with device views, which LiveSessionPool.tick takes as they are."""
+        import numpy as np
+        torch = self.torch
+        out, parts, at = [], [], []
+        host = [(sid, np.asarray(smp)) for sid, smp in pairs if not isinstance(smp, torch.Tensor)]
+        bad = [sid for sid, a in host if a.dtype != np.float32 or a.ndim != 1]
+        bad += [sid for sid, t in pairs if isinstance(t, torch.Tensor) and (t.dtype != torch.float32 or t.dim() != 1)]
+        if bad or len({sid for sid, _ in pairs}) != len(pairs):
+            return pairs                                                           # the audio pool refuses these, with its own words
+        with torch.cuda.device(self.device):
+            flat = torch.from_numpy(np.ascontiguousarray(np.concatenate([a for _, a in host]))).to(self.device) if host else None
+            off = 0
+            for sid, smp in pairs:
+                if isinstance(smp, torch.Tensor):
+                    t = smp.to(self.device).contiguous()
+                else:
+                    t = flat[off:off + len(smp)]
+                    off += len(smp)
+                out.append((sid, t))
+                if t.shape[0]:
+                    parts.append(t)
+                    at.append(self._row[sid] * self.ring_samples + self._book[sid].push(t.shape[0]))
+            if parts:
+                self._ring.view(-1).index_copy_(0, torch.from_numpy(np.concatenate(at)).to(self.device), parts[0] if len(parts) == 1 else torch.cat(parts))
+        return out
+
+    def _track(self, which: str):
+        pair = self._mux.get(which)
+        if pair is None:
+            from .jpeg import JpegEncoder
+            from .video import DeviceMultiMuxer
+            enc = JpegEncoder(self.load_size, 3 if which == "video" else 1, self.record_quality, self.device, max_batch=self.max_batch)
+            pair = self._mux[which] = (enc, DeviceMultiMuxer(enc, self.rate, self.fps) if self.record_route == "device" else None)
+        return pair
+
+    def _record_track(self, which: str, segments, source) -> None:
+        """``segments``: (sid, first stream frame, first row of ``source``, count) of the recorded sessions, ascending.  Groups of at most
+        ``max_batch`` frames; a group is made of runs, one per file; a session may span two groups.  Before a run is taken into a group its
+        file is asked for room (LiveRecording.make_room): rollover, or the end of that session's recording."""
+        from .video import AviFull
+        queue = [list(s) for s in segments if which in self._rec.get(s[0], ())]
+        if not queue:
+            return
+        enc, mux = self._track(which)
+        frame_bytes = len(enc.header) + enc.capacity
+        while queue:
+            group, room = [], self.max_batch
+            while queue and room:
+                sid, start, row, n = queue[0]
+                if sid not in self._rec:                                           # stopped while its other file was written
+                    queue.pop(0)
+                    continue
+                rec, take = self._rec[sid][which], min(n, room)
+                try:
+                    rec.make_room(take, frame_bytes, start, self._check_writer)
+                except AviFull as e:
+                    self.recording_stopped[sid] = e
+                    del self._rec[sid]
+                    queue.pop(0)
+                    continue
+                if rec.base + rec.writer.nframes != start:
+                    raise RuntimeError("session %d: frame %d follows %d recorded frames from %d" % (sid, start, rec.writer.nframes, rec.base))
+                group.append((sid, rec, row, take))
+                room -= take
+                if take == n:
+                    queue.pop(0)
+                else:
+                    queue[0] = [sid, start + take, row + take, n - take]
+            if group:
+                self._record_group(enc, mux, group, source)
+
+    def _record_group(self, enc, mux, group, source) -> None:
+        torch = self.torch
+        if all(a[2] + a[3] == b[2] for a, b in zip(group, group[1:])):            # consecutive in ``source``: no copy
+            frames = source[group[0][2]:group[-1][2] + group[-1][3]]
+        else:                                                                      # an unrecorded session's frames lie in between
+            frames = torch.cat([source[row:row + n] for _, _, row, n in group])
+        runs = []
+        for sid, rec, row, n in group:
+            fmt = rec.writer.audio_format
+            a, b = self._book[sid].avail
+            runs.append((n, rec.writer.nframes, fmt, self._ring[self._row[sid]] if fmt else None, rec.sample0, a, b))
+        if mux is not None:
+            for (sid, rec, _, _), fragment in zip(group, mux.pack(frames, runs)):
+                rec.writer.append_fragment(*fragment)
+            return
+        files, at = enc.encode(frames), 0
+        for sid, rec, _, n in group:
+            samples = None
+            if rec.writer.has_audio:
+                pos = self._book[sid].positions(*rec.span(n))
+                samples = self._ring[self._row[sid]][torch.from_numpy(pos).to(self.device)].cpu().numpy()
+            rec.writer.append_jpegs(files[at:at + n], samples)
+            at += n
 
     def _dry_run(self, lengths, finish) -> None:
         """How many mouth rows and poses the audio stages will hand over is host arithmetic (PoolPlanner.preview): push the counts through

@@ -26,6 +26,9 @@ AUDIO_FORMATS = {"f32": (3, 4), "s16": (1, 2)}                  # name -> (wForm
 # which route the render loops take when ``video`` is given: "device" (DeviceMuxer + append_fragment) or "host" (JpegEncoder.collect +
 # append_jpegs).  Set from profiles/avi_time.txt, see DESIGN.md section 20.
 DEFAULT_VIDEO_ROUTE = "device"
+# which route LivePortraitPool records by when ``record_route`` is not given: "device" (DeviceMultiMuxer, one lspavi_pack_multi per group of
+# frames) or "host" (JpegEncoder + append_jpegs per session).  By section 20's rule, see DESIGN.md section 21.
+DEFAULT_LIVE_RECORD_ROUTE = "device"
 
 
 class AviFull(RuntimeError):
@@ -104,6 +107,11 @@ class AviWriter:
     def _riff_size(self, more_bytes: int, more_chunks: int) -> int:
         """the RIFF chunk's size field if ``more_bytes`` of chunks in ``more_chunks`` chunks were appended and the file closed"""
         return self._header_len - 8 + self._movi + more_bytes + 8 + len(self._index) + 16 * more_chunks
+
+    def room_for(self, nbytes: int, nchunks: int) -> bool:
+        """would ``nbytes`` more bytes of 'movi' in ``nchunks`` chunks still close within ``max_bytes``?  (what append_fragment checks
+        before it writes; a caller that cannot know a fragment's size yet asks with its worst case)"""
+        return self._riff_size(int(nbytes), int(nchunks)) <= self.max_bytes
 
     def _header(self) -> bytes:
         """everything up to the first chunk of 'movi', from the current counts"""
@@ -384,3 +392,170 @@ class VideoSink:
         a, b = self.video.span(self._frame0, len(files))
         self.video.append_jpegs(files, None if self.audio_host is None else self.audio_host[a:b])
         return len(files)
+
+
+# ---- live sessions: one file per session, fragments of many files from one batch ------------------------------
+def live_ring_samples(lag_frames: int, max_tick_samples: int, rate: int = 16000, fps: int = 60) -> int:
+    """Samples a live session's audio ring must hold so that the span of every frame a tick emits is still in it.  ``lag_frames``: how
+    far the oldest frame a tick can emit lies behind the audio pushed BEFORE that tick (the audio models' lookahead plus the landmark
+    filters' radius); 4 frames on top for the mel windows' rounding and the one-sample slack of ``sample0``; then the tick's own push."""
+    return int(max_tick_samples) + (int(lag_frames) + 4) * -(-int(rate) // int(fps))
+
+
+class RingBook:
+    """The host's account of one audio ring: stream sample i lives at ``i % ring_samples``; ``pushed`` samples have been appended."""
+
+    def __init__(self, ring_samples: int):
+        if int(ring_samples) < 1:
+            raise ValueError("ring_samples must be >= 1")
+        self.ring_samples, self.pushed = int(ring_samples), 0
+
+    @property
+    def avail(self) -> Tuple[int, int]:
+        """the stream samples [begin, end) the ring holds"""
+        return max(0, self.pushed - self.ring_samples), self.pushed
+
+    def push(self, n: int) -> np.ndarray:
+        """account for ``n`` more samples: the ring positions they go to, in order"""
+        n = int(n)
+        if not 0 <= n <= self.ring_samples:
+            raise ValueError("a push of %d samples does not fit a ring of %d" % (n, self.ring_samples))
+        at = (self.pushed + np.arange(n, dtype=np.int64)) % self.ring_samples
+        self.pushed += n
+        return at
+
+    def positions(self, first: int, last: int) -> np.ndarray:
+        """the ring positions of stream samples [first, last); refused when the ring does not hold them all"""
+        begin, end = self.avail
+        if not begin <= first <= last <= end:
+            raise ValueError("samples %d..%d are not in the ring, which holds %d..%d" % (first, last, begin, end))
+        return np.arange(first, last, dtype=np.int64) % self.ring_samples
+
+
+class LiveRecording:
+    """One file of one live session.  The file's frame 0 is the stream's frame ``base``; its frame k carries the stream samples
+    ``sample0 + [s(k), s(k + 1))`` with ``sample0 = s(base)`` and s = frame_sample -- AviWriter.span's rule on the file's own numbering,
+    at most one sample off the stream's own s(base + k).  ``make_room`` is the rollover rule, the same for every route."""
+
+    def __init__(self, sid: int, which: str, writer: AviWriter, on_full, stream_frame: int):
+        self.sid, self.which, self.on_full = sid, which, on_full
+        self._start(writer, stream_frame)
+
+    def _start(self, writer: AviWriter, stream_frame: int) -> None:
+        if writer.nframes or writer.nsamples:
+            raise ValueError("session %d: the %s writer already holds %d frames; a recording starts an empty file" % (self.sid, self.which, writer.nframes))
+        self.writer, self.base = writer, int(stream_frame)
+        self.sample0 = frame_sample(self.base, writer.audio_rate, writer.fps) if writer.has_audio else 0
+
+    def span(self, count: int) -> Tuple[int, int]:
+        """stream samples [first, last) of the file's next ``count`` frames ((0, 0) without audio)"""
+        a, b = self.writer.span(self.writer.nframes, count)
+        return (self.sample0 + a, self.sample0 + b) if self.writer.has_audio else (0, 0)
+
+    def worst_case(self, count: int, frame_bytes: int) -> Tuple[int, int]:
+        """(bytes, chunks) the next ``count`` frames take at most: every JPEG file at its bound ``frame_bytes``, padded"""
+        a, b = self.span(count)
+        audio = count * 8 + (b - a) * self.writer.bytes_per_sample if self.writer.has_audio else 0
+        return count * (8 + int(frame_bytes) + 1) + audio, count * (2 if self.writer.has_audio else 1)
+
+    def make_room(self, count: int, frame_bytes: int, stream_frame: int, check=None) -> None:
+        """Before a run of ``count`` frames (the stream's ``stream_frame`` ..) is built: if its worst case no longer fits the file, ask
+        ``on_full(sid, which)`` for a fresh writer, whose frame 0 is then ``stream_frame``; AviFull without ``on_full`` (or when the fresh
+        file cannot take the run either).  The full writer is the caller's to close."""
+        if self.writer.room_for(*self.worst_case(count, frame_bytes)):
+            return
+        if self.on_full is None:
+            raise AviFull("session %d: %d more frames may take the %s file past max_bytes=%d and no on_full was given" % (
+                self.sid, count, self.which, self.writer.max_bytes))
+        fresh = self.on_full(self.sid, self.which)
+        if check is not None:
+            check(fresh, self.which)
+        self._start(fresh, stream_frame)
+        if not self.writer.room_for(*self.worst_case(count, frame_bytes)):
+            raise AviFull("session %d: the fresh %s file (max_bytes=%d) cannot take %d frames" % (self.sid, self.which, self.writer.max_bytes, count))
+
+
+class DeviceMultiMuxer:
+    """``lspjpeg_encode`` then ``lspavi_pack_multi`` (include/lspavi.h): one batch of device frames that belongs to up to 16 files becomes
+    one fragment per file on the device, with the audio taken from per-session rings.  One encode, two launches, one copy of status + index
+    and one copy of the bytes, whatever the number of files.  Uses ``encoder``'s slab like DeviceMuxer."""
+
+    def __init__(self, encoder, rate: int = 16000, fps: int = 60):
+        import torch
+        from . import _native as N
+        if encoder.max_batch > N.AVI_MAX_BATCH:
+            raise ValueError("the muxer packs at most %d frames per call (encoder.max_batch = %d)" % (N.AVI_MAX_BATCH, encoder.max_batch))
+        self.N, self.lib, self.enc = N, N.load(), encoder
+        self.rate, self.fps, self.device = int(rate), int(fps), encoder.device
+        B = encoder.max_batch
+        self.max_runs = R = min(B, N.AVI_MAX_STREAMS)
+        self.capacity = int(self.lib.lspavi_capacity_bytes_multi(len(encoder.header), encoder.capacity, B, R, self.rate, self.fps))
+        self._ws_bytes = int(self.lib.lspavi_workspace_bytes_multi(B))
+        if self.capacity == 0 or self._ws_bytes == 0:
+            raise ValueError("lspavi: geometry, batch, rate or fps out of range")
+        dev = self.device
+        self._header = torch.frombuffer(bytearray(encoder.header + b"\0" * (-len(encoder.header) % 4)), dtype=torch.uint8).to(dev)
+        self._out = torch.empty(self.capacity, dtype=torch.uint8, device=dev)
+        self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=dev)
+        self._srows = R * N.AVI_STATUS_WORDS // 4                                     # rows of 4 words the status rows take
+        self._meta = torch.empty((self._srows + 2 * B, 4), dtype=torch.int32, device=dev)  # the status rows, then the index
+        self._meta_host = torch.empty((self._srows + 2 * B, 4), dtype=torch.int32, pin_memory=True)
+        self._host = torch.empty(0, dtype=torch.uint8)
+        self._table = (N.AviRun * N.AVI_MAX_STREAMS)()
+
+    def pack(self, frames, runs):
+        """``frames``: what JpegEncoder takes; ``runs``: per file, in batch order, ``(count, frame0, audio_format, ring, sample0,
+        avail_begin, avail_end)`` -- ``audio_format`` None / "s16" / "f32", ``ring`` that session's contiguous 1-D float32 device tensor.
+        -> per run what AviWriter.append_fragment takes; the ``data`` are views of pinned memory, valid until the next pack().  A run the
+        ring cannot serve is refused by lspavi_pack_multi on the host (LspaviError): nothing was launched for the mux."""
+        import torch
+        c = ctypes.c_void_p
+        runs = list(runs)
+        if not 1 <= len(runs) <= self.N.AVI_MAX_STREAMS:
+            raise ValueError("a batch is split into 1..%d runs (got %d)" % (self.N.AVI_MAX_STREAMS, len(runs)))
+        first = 0
+        for j, (count, frame0, fmt, ring, sample0, begin, end) in enumerate(runs):
+            if fmt is not None:
+                ok = isinstance(ring, torch.Tensor) and ring.dim() == 1 and ring.dtype == torch.float32 and ring.device == self.device \
+                    and ring.is_contiguous()
+                if not ok:
+                    raise ValueError("run %d: the ring must be a contiguous 1-D float32 tensor on %s" % (j, self.device))
+            t = self._table[j]
+            t.first, t.count, t.audio_format, t.reserved, t.frame0 = first, int(count), self.N.AVI_AUDIO_FORMATS[fmt], 0, int(frame0)
+            t.ring_dev = ring.data_ptr() if fmt is not None else None
+            t.ring_samples = ring.shape[0] if fmt is not None else 0
+            t.sample0, t.avail_begin, t.avail_end = int(sample0), int(begin), int(end)
+            first += int(count)
+        b = self.enc.enqueue(frames)
+        stream = torch.cuda.current_stream(self.device)
+        dst, sizes = self.enc.slab
+        R = self._srows
+        with torch.cuda.device(self.device):
+            self.N.check_avi(self.lib.lspavi_pack_multi(
+                c(self._header.data_ptr()), len(self.enc.header), c(dst.data_ptr()), self.enc.capacity, c(sizes.data_ptr()), b,
+                self._table, len(runs), self.rate, self.fps, c(self._out.data_ptr()), self.capacity,
+                c(self._meta[R:].data_ptr()), c(self._meta.data_ptr()), c(self._ws.data_ptr()), self._ws_bytes, c(stream.cuda_stream)))
+            self._meta_host[:R + 2 * b].copy_(self._meta[:R + 2 * b], non_blocking=True)
+        stream.synchronize()
+        meta = self._meta_host.numpy().view(np.uint32)
+        status = meta[:R].reshape(-1, self.N.AVI_STATUS_WORDS)[:len(runs)]
+        at = row = 0
+        for j, (count, frame0, fmt, *_rest) in enumerate(runs):
+            off, nbytes, nchunk, _, _, row0 = (int(v) for v in status[j][:6])
+            if off != at or row0 != row or nchunk != int(count) * (2 if fmt is not None else 1) or nbytes == 0 or nbytes & 1 \
+                    or off + nbytes > self.capacity:
+                raise RuntimeError("lspavi_pack_multi: run %d came back as %d bytes at %d in %d chunks from row %d (expected offset %d, row %d)" % (
+                    j, nbytes, off, nchunk, row0, at, row))
+            at, row = (off + nbytes + 15) & ~15, row + nchunk
+        total = int(status[-1][0]) + int(status[-1][1])
+        if self._host.numel() < total:
+            self._host = torch.empty(max(total, 2 * self._host.numel()), dtype=torch.uint8, pin_memory=True)
+        with torch.cuda.stream(stream):
+            self._host[:total].copy_(self._out[:total], non_blocking=True)
+        stream.synchronize()
+        host, out = self._host.numpy(), []
+        for j, (count, frame0, fmt, *_rest) in enumerate(runs):
+            off, nbytes, nchunk, largest_video, largest_audio, row0 = (int(v) for v in status[j][:6])
+            nsamples = frame_sample(int(frame0) + int(count), self.rate, self.fps) - frame_sample(frame0, self.rate, self.fps) if fmt is not None else 0
+            out.append((host[off:off + nbytes], meta[R + row0:R + row0 + nchunk].copy(), int(count), nsamples, largest_video, largest_audio))
+        return out
