@@ -1,4 +1,4 @@
-"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h, include/lsplmk.h, include/lspavi.h).
+"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h, include/lsplmk.h, include/lspavi.h, include/lsprs.h).
 
 There is deliberately no fallback: if the shared library is missing or does not
 load, importing the hot path raises -- a GPU box must never silently run
@@ -369,6 +369,43 @@ AVI_SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+
+
+class RsConfig(Structure):
+    """lsprs_config (include/lsprs.h)"""
+    _fields_ = [("abi_version", c_int32), ("n_rates", c_int32), ("rates", c_int32 * 4), ("max_sessions", c_int32), ("max_push", c_int32)]
+
+
+class RsSessionCall(Structure):
+    """lsprs_session_call (include/lsprs.h)"""
+    _fields_ = [(n, c_int32) for n in ("slot", "rate_index", "format", "channels")] + [("n_have", c_int64), ("out0", c_int64)] + \
+               [(n, c_int32) for n in ("n_fresh", "n_out", "finished", "reserved")] + [("fresh_dev", c_void_p), ("out_dev", c_void_p)]
+
+
+RS_ABI_VERSION = 1
+RS_MAX_SESSIONS = 16
+RS_MAX_RATES = 4
+RS_FORMATS = {"f32": 0, "s16": 1}
+# every symbol include/lsprs.h declares
+RS_SIGNATURES = {
+    "lsprs_create": (c_int, [POINTER(RsConfig), POINTER(c_void_p)]),
+    "lsprs_destroy": (c_int, [c_void_p]),
+    "lsprs_last_error": (c_char_p, []),
+    "lsprs_abi_version": (c_int, []),
+    "lsprs_rate_info": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_size_t)]),
+    "lsprs_history": (c_int, [c_void_p]),
+    "lsprs_params_bytes": (c_size_t, [c_void_p]),
+    "lsprs_pack_params": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "lsprs_bind_params": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "lsprs_state_bytes": (c_size_t, [c_void_p]),
+    "lsprs_bind_state": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "lsprs_out_count": (c_int64, [c_void_p, c_int, c_int64, c_int]),
+    "lsprs_clip": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "lsprs_tick": (c_int, [c_void_p, c_int, POINTER(RsSessionCall), c_void_p]),
+    "lsprs_check_tick": (c_int, [c_void_p, c_int, POINTER(RsSessionCall)]),
+    "lsprs_launch_count": (c_int64, [c_void_p]),
+}
+
 _lib = None
 
 
@@ -386,7 +423,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise NativeLibraryError("failed to load %s: %s" % (LIB_PATH, e)) from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(LMK_SIGNATURES.items()) + list(AVI_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(LMK_SIGNATURES.items()) + list(AVI_SIGNATURES.items()) + list(RS_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -403,6 +440,8 @@ def load() -> ctypes.CDLL:
         raise NativeLibraryError("lspunet ABI version mismatch: library %d, binding %d" % (lib.lspunet_abi_version(), UNET_ABI_VERSION))
     if lib.lsplmk_abi_version() != LMK_ABI_VERSION:
         raise NativeLibraryError("lsplmk ABI version mismatch: library %d, binding %d" % (lib.lsplmk_abi_version(), LMK_ABI_VERSION))
+    if lib.lsprs_abi_version() != RS_ABI_VERSION:
+        raise NativeLibraryError("lsprs ABI version mismatch: library %d, binding %d" % (lib.lsprs_abi_version(), RS_ABI_VERSION))
     _lib = lib
     return lib
 
@@ -519,3 +558,15 @@ def check_lmk(rc: int) -> None:
     if rc != OK:
         msg = load().lsplmk_last_error()
         raise LsplmkError(rc, msg.decode() if msg else "")
+
+
+class LsprsError(RuntimeError):
+    def __init__(self, code: int, msg: str):
+        super().__init__("lsprs error %d: %s" % (code, msg))
+        self.code = code
+
+
+def check_rs(rc: int) -> None:
+    if rc != OK:
+        msg = load().lsprs_last_error()
+        raise LsprsError(rc, msg.decode() if msg else "")

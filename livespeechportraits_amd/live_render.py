@@ -13,6 +13,10 @@ layers is cached by the engine as in the render loop.  Inside a tick:
 6. recording, for the sessions that have a writer: the frames of a tick are encoded and muxed in groups of at most ``max_batch``, one
    fragment per file out of one ``lspavi_pack_multi`` call, the audio from per-session rings on the device.
 
+0. the audio input stage, for the sessions opened at a capture rate (``open(input_rate=...)``, with a pool built with ``audio_input``):
+   ONE launch turns their raw samples (any supported rate, int16 or float32, mono or stereo) into the 16 kHz float32 views that steps 1
+   and 6 take exactly as they take device-tensor samples.  Sessions opened without a rate skip it.
+
 The only host copy is the last one, when ``host`` or ``jpeg_quality`` asks for it (and a recorded fragment's bytes).  A frame leaves ``delay`` frames after its audio: the
 audio models' lookahead (frame_future, ~18 frames) plus the largest filter radius of the landmark stage (or its ``max_lookahead``)."""
 from __future__ import annotations
@@ -28,13 +32,16 @@ class LivePortraitPool:
 
     ``record_quality`` (a JPEG quality) makes the pool able to record: it then keeps every session's last ``ring_samples`` samples on the
     device, and ``open`` / ``record`` take AviWriters that ``tick`` appends the session's frames and their audio to.  ``record_route``
-    "device" (one lspavi_pack_multi per group of frames) or "host" (JpegEncoder + append_jpegs per session); both write the same files."""
+    "device" (one lspavi_pack_multi per group of frames) or "host" (JpegEncoder + append_jpegs per session); both write the same files.
+
+    ``audio_input``: an AudioInputStage on the same device with at least as many sessions; sessions may then be opened at one of its rates
+    and pushed raw capture audio.  The stage's lookahead (R input samples, at most 8 ms) adds at most one frame to ``delay``."""
 
     fps = 60                                                                       # live.py: a clip of N samples has int(N / 16000 * 60) frames
     rate = 16000
 
     def __init__(self, audio, stage, model, cand_image, load_size: int = 512, max_batch: int = 8, raster_chunk: int = 64,
-                 record_quality: Optional[int] = None, record_route: Optional[str] = None):
+                 record_quality: Optional[int] = None, record_route: Optional[str] = None, audio_input=None):
         import torch
         from .feature_map import FeatureMapRasteriser
         self.torch = torch
@@ -48,6 +55,14 @@ class LivePortraitPool:
             raise ValueError("the landmark stage has %d sessions, the audio pool %d" % (stage.max_sessions, audio.max_sessions))
         if max_batch < 1 or raster_chunk < 1:
             raise ValueError("max_batch and raster_chunk must be >= 1")
+        if audio_input is not None:
+            if (audio_input.device.index or 0) != (self.device.index or 0):
+                raise ValueError("the audio pool and the audio input stage must live on the same device")
+            if audio_input.max_sessions < audio.max_sessions:
+                raise ValueError("the audio input stage has %d sessions, the audio pool %d" % (audio_input.max_sessions, audio.max_sessions))
+        self.audio_input = audio_input
+        self._in: Dict[int, int] = {}                                              # audio session id -> input stage session id
+        self.last_heard: Dict[int, tuple] = {}                                     # the input stage's output of the last tick, per session
         self.load_size, self.max_batch, self.raster_chunk = int(load_size), int(max_batch), int(raster_chunk)
         self.raster = FeatureMapRasteriser(self.load_size, 18, self.device)
         rows = stage.max_push - audio.ff_mouth - 2                                # a push's frames, + the mouth tail at finish, + rounding
@@ -86,14 +101,26 @@ class LivePortraitPool:
         self._mux: Dict[str, tuple] = {}                                           # "video" / "video_input" -> (JpegEncoder, DeviceMultiMuxer or None)
 
     # ---- sessions ----------------------------------------------------------------------------------------------------------------
-    def open(self, pre_headpose, generator=None, video=None, video_input=None, on_full=None) -> int:
-        """``video`` / ``video_input`` / ``on_full``: record the session from its first frame (see ``record``)"""
+    def open(self, pre_headpose, generator=None, video=None, video_input=None, on_full=None, input_rate: Optional[int] = None,
+             input_format: str = "f32", input_channels: int = 1) -> int:
+        """``video`` / ``video_input`` / ``on_full``: record the session from its first frame (see ``record``).  ``input_rate`` (with
+        ``input_format`` "f32" / "s16" and ``input_channels`` 1 / 2): the session is pushed raw capture audio of that rate, which the
+        pool's ``audio_input`` stage resamples; None: 16 kHz float32 samples, as ever."""
+        if input_rate is None:
+            if input_format != "f32" or input_channels != 1:
+                raise ValueError("input_format and input_channels go with input_rate")
+        else:
+            if self.audio_input is None:
+                raise ValueError("this pool was made without audio_input: it takes 16 kHz float32 samples only")
+            self.audio_input.check_spec(input_rate, input_format, input_channels)
         if video is None and (video_input is not None or on_full is not None):
             raise ValueError("video_input and on_full go with video")
         if video is not None:
             self._check_recording(video, video_input)
         sid = self.audio.open(pre_headpose, generator)
         self._lm[sid] = self.stage.open()
+        if input_rate is not None:
+            self._in[sid] = self.audio_input.open(input_rate, input_format, input_channels)
         if self.record_quality is not None:
             from .video import RingBook
             self._book[sid], self._emitted[sid], self._row[sid] = RingBook(self.ring_samples), 0, self.audio.plan.slot[sid]
@@ -105,6 +132,8 @@ class LivePortraitPool:
     def close(self, sid: int) -> None:
         self.audio.close(sid)
         self.stage.close(self._lm.pop(sid))
+        if sid in self._in:
+            self.audio_input.close(self._in.pop(sid))
         self._forget(sid)
 
     def _forget(self, sid: int) -> None:
@@ -163,14 +192,20 @@ class LivePortraitPool:
 
     # ---- a tick ------------------------------------------------------------------------------------------------------------------
     def tick(self, samples=None, finish=(), host: bool = False, jpeg_quality: Optional[int] = None):
-        """Push ``samples`` ({session id: float32 16 kHz samples}) and end the sessions in ``finish`` (closed afterwards).  -> {id:
+        """Push ``samples`` ({session id: float32 16 kHz samples -- or, for a session opened with ``input_rate``, its raw samples: int16 or
+        float32, [n] or [n, channels]}) and end the sessions in ``finish`` (closed afterwards).  -> {id:
         (frame_start, frames)} for every session named: the frames that became final, uint8 [k, H, W, 3] on the device (a numpy array with
         ``host``), or a list of k complete JPEG files (``bytes``) with ``jpeg_quality``.  Nothing is changed when an argument is refused."""
         torch = self.torch
         pairs = list(samples.items()) if hasattr(samples, "items") else list(samples or ())
         finish = list(finish)
         for sid, smp in pairs:
-            if len(smp) > self.max_tick_samples:
+            if sid in self._in:                                                    # the raw count, scaled by M / L
+                n16 = -(-len(smp) * 16000 // self.audio_input._sess[self._in[sid]].rate)
+                if n16 > self.max_tick_samples:
+                    raise ValueError("session %d: %d raw samples (%d at 16 kHz) in one tick; this pool takes at most %d at 16 kHz (the landmark "
+                                     "stage's max_push)" % (sid, len(smp), n16, self.max_tick_samples))
+            elif len(smp) > self.max_tick_samples:
                 raise ValueError("session %d: %d samples in one tick; this pool takes at most %d (the landmark stage's max_push)" % (sid, len(smp), self.max_tick_samples))
         for sid in [s for s, _ in pairs] + finish:
             if sid not in self._lm:
@@ -178,10 +213,32 @@ class LivePortraitPool:
                 raise KeyError("unknown session id %r" % (sid,))
         if jpeg_quality is not None and not 1 <= int(jpeg_quality) <= 100:
             raise ValueError("jpeg_quality must be in 1..100")
-        self._dry_run({sid: len(smp) for sid, smp in pairs}, finish)              # the landmark rings take this tick's rows, or nothing runs
-        if self.record_quality is not None:
-            pairs = self._to_rings(pairs)
-        live = self.audio.tick(pairs, finish=finish, host=False)                  # 1. mouth rows and poses, on the device
+        lengths = {sid: len(smp) for sid, smp in pairs}
+        staged = [sid for sid in dict.fromkeys([s for s, _ in pairs] + finish) if sid in self._in]
+        if staged:
+            if len(lengths) != len(pairs):
+                raise ValueError("a session appears twice in one tick")
+            raw = {self._in[sid]: smp for sid, smp in pairs if sid in self._in}
+            fin_in = [self._in[sid] for sid in finish if sid in self._in]
+            emits = self.audio_input.preview(raw, fin_in)                          # every check of the input stage, and its 16 kHz counts
+            lengths.update({sid: emits[self._in[sid]] for sid in staged})
+        self._dry_run(lengths, finish)                                            # the landmark rings take this tick's rows, or nothing runs
+        snap, self.last_heard = None, {}
+        if staged:                                                                 # 0. one launch: raw capture audio -> 16 kHz views
+            snap = self.audio_input.snapshot()
+            heard = self.audio_input.tick(raw, finish=fin_in)
+            self.last_heard = {sid: heard[self._in[sid]] for sid in staged}       # (first 16 kHz sample, the samples): what the models hear
+            pushed = {sid for sid, _ in pairs}
+            pairs = [(sid, heard[self._in[sid]][1] if sid in self._in else smp) for sid, smp in pairs]
+            pairs += [(sid, heard[self._in[sid]][1]) for sid in staged if sid not in pushed]           # finished without a push: its tail
+        try:
+            if self.record_quality is not None:
+                pairs = self._to_rings(pairs)
+            live = self.audio.tick(pairs, finish=finish, host=False)              # 1. mouth rows and poses, on the device
+        except Exception:
+            if snap is not None:
+                self.audio_input.restore(snap)                                     # the audio pool refused an argument: nothing has changed
+            raise
         named = sorted(live)
         try:                                                                       # 2. one launch: the points of every final frame
             out = self.stage.tick({self._lm[sid]: live[sid] for sid in named}, finish=[self._lm[sid] for sid in finish])
@@ -234,6 +291,7 @@ class LivePortraitPool:
                 self._emitted[sid] += spans[sid][2]
         for sid in finish:
             del self._lm[sid]
+            self._in.pop(sid, None)                                                # the input stage closed it in its own tick
             self._forget(sid)
         return result
 
