@@ -8,6 +8,7 @@ include/lspf2f.h.  (SURVEY.md 8b option 1: "keep the reference class and swap on
     model = create_model(opt); model.setup(opt); model.eval()            # the reference's own code (demo.py:168-172)
     install(model, device="cuda:0")                                        # <- the one added line
     pred = model.inference(feature_map, cand_image)                        # demo.py:266, unchanged
+    pred = model.inference(feature_map, load_candidates(data_root))        # or: demo.py:88-95 on the device (livespeechportraits_amd.candidates)
 
 Entry points used and the reference interface each replaces:
   lspf2f_create                         Feature2Face_G.__init__ (models/feature2face_G.py:9-24), networks.py:554-572 / 458-476

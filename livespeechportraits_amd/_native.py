@@ -1,4 +1,4 @@
-"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h, include/lsplmk.h, include/lspavi.h, include/lsprs.h).
+"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h, include/lspjpegdec.h, include/lsplmk.h, include/lspavi.h, include/lsprs.h).
 
 There is deliberately no fallback: if the shared library is missing or does not
 load, importing the hot path raises -- a GPU box must never silently run
@@ -308,6 +308,39 @@ JPEG_SIGNATURES = {
 }
 
 
+class JpegDecInfo(ctypes.Structure):
+    """lspjpeg_dec_info"""
+    _fields_ = [("status", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("components", ctypes.c_int32),
+                ("hsamp", ctypes.c_int32), ("vsamp", ctypes.c_int32), ("restart_interval", ctypes.c_int32), ("mcus", ctypes.c_int32),
+                ("segments", ctypes.c_int32), ("default_tables", ctypes.c_int32), ("scan_offset", ctypes.c_uint64), ("scan_bytes", ctypes.c_uint64)]
+
+
+class JpegDecOutput(ctypes.Structure):
+    """lspjpeg_dec_output"""
+    _fields_ = [("ptr", c_void_p), ("table", c_void_p), ("plane_stride", c_int64), ("form", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class JpegDecSummary(ctypes.Structure):
+    """lspjpeg_dec_summary"""
+    _fields_ = [("files", ctypes.c_uint32), ("segments", ctypes.c_uint32), ("max_blocks", ctypes.c_uint32), ("max_pixels", ctypes.c_uint32),
+                ("total_blocks", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("workspace_bytes", ctypes.c_uint64), ("status_offset", ctypes.c_uint64)]
+
+
+# every symbol include/lspjpegdec.h declares
+JPEGDEC_SIGNATURES = {
+    "lspjpeg_dec_last_error": (c_char_p, []),
+    "lspjpeg_dec_probe": (c_int, [c_void_p, c_size_t, POINTER(JpegDecInfo)]),
+    "lspjpeg_dec_plan": (c_int64, [POINTER(c_void_p), POINTER(c_size_t), POINTER(JpegDecOutput), c_int, c_int, c_void_p, c_size_t]),
+    "lspjpeg_dec_summary_of": (c_int, [c_void_p, POINTER(JpegDecSummary)]),
+    "lspjpeg_dec_plan_file": (c_int, [c_void_p, c_int, POINTER(JpegDecInfo)]),
+    "lspjpeg_dec_plan_qtable": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "lspjpeg_dec_plan_segment": (c_int, [c_void_p, c_int, POINTER(ctypes.c_uint32), POINTER(ctypes.c_uint32), POINTER(ctypes.c_uint32),
+                                         POINTER(ctypes.c_uint64), POINTER(ctypes.c_uint64)]),
+    "lspjpeg_dec_host_coefficients": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "lspjpeg_dec_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
+
 
 class LmkConfig(Structure):
     """lsplmk_config (include/lsplmk.h)"""
@@ -423,7 +456,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise NativeLibraryError("failed to load %s: %s" % (LIB_PATH, e)) from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(LMK_SIGNATURES.items()) + list(AVI_SIGNATURES.items()) + list(RS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JPEGDEC_SIGNATURES.items()) + list(LMK_SIGNATURES.items()) + list(AVI_SIGNATURES.items()) + list(RS_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -534,6 +567,14 @@ def check_jpeg(rc: int) -> None:
     if rc != OK:
         msg = load().lspjpeg_last_error()
         raise LspjpegError(rc, msg.decode() if msg else "")
+
+
+def check_jpeg_dec(rc: int) -> int:
+    """negative codes of include/lspjpegdec.h raise; anything else (0, a size, a status word) is handed back"""
+    if rc < 0:
+        msg = load().lspjpeg_dec_last_error()
+        raise LspjpegError(rc, msg.decode() if msg else "")
+    return rc
 
 
 class LspaviError(RuntimeError):

@@ -1,0 +1,447 @@
+// jpegdec.hip -- the baseline JPEG decoder of include/lspjpegdec.h: three stages on the device (entropy decode, dequantise + IDCT, upsample +
+// colour + store) behind a host planner.  The arithmetic is libjpeg's integer arithmetic step by step (jdhuff.c, jidctint.c, jdsample.c,
+// jdcolor.c): for a file Pillow can open the output equals Pillow's pixels.  The parser and the segment decoder live in jpegdec_core.h, which is
+// also built for the host alone and run under sanitizers (make check-jpegdec).
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/lspjpeg.h"
+#include "../../include/lspjpegdec.h"
+#include "jpegdec_plan.h"
+
+namespace {
+
+using namespace lspdec;
+
+thread_local std::string g_err;
+int fail(int code, const std::string &msg)
+{
+    g_err = msg;
+    return code;
+}
+
+struct Params {
+    unsigned char *blob;                    // the descriptor block on the device
+    const FileDesc *files;
+    const SegDesc *segs;
+    const HuffTable *tables;
+    unsigned *status;                       // [nfiles]
+    short *coef;                            // [total blocks][64] natural order, MCU order per file
+    unsigned char *planes;
+    unsigned nfiles, nsegs;
+    unsigned long long bytes;               // of the block: no load reaches past it
+};
+
+constexpr int kWave = 64;
+constexpr unsigned kRing = 8192;            // bytes of the stream window in LDS: > kMcuBytesBound + one refill of kWave * 16 bytes
+static_assert(kRing >= kMcuBytesBound + 2 * kWave * 16 && (kRing & (kRing - 1)) == 0, "the window holds one MCU's worst case behind a refill");
+
+// the byte source of BitReader on the device: the window, indexed by the offset inside the block
+struct RingSrc {
+    const unsigned char *ring;
+    __device__ uint8_t at(uint64_t pos) const { return ring[pos & (kRing - 1)]; }
+};
+
+// ---- stage 1: one wave per restart interval.  All lanes stage the stream (16 bytes per lane and refill) and move finished MCUs to memory
+// (16 bytes per lane); lane 0 walks the Huffman codes out of LDS.  Reads are bounded by the segment's end (BitReader) and by the block's end
+// (the refill); writes by the segment's MCU count, which the planner derived from the file's geometry.
+__global__ __launch_bounds__(kWave) void jpegdec_entropy(Params p)
+{
+    __shared__ uint4 s_tab[4 * sizeof(HuffTable) / 16];
+    __shared__ uint4 s_ring[kRing / 16];
+    __shared__ uint4 s_mcu[kMaxBlocksPerMcu * 8];
+    __shared__ unsigned long long s_pos;
+    __shared__ unsigned s_st;
+    if (blockIdx.x >= p.nsegs) return;
+    const SegDesc sg = p.segs[blockIdx.x];
+    const FileDesc &f = p.files[sg.file];
+    const int lane = threadIdx.x;
+    const uint4 *tab = reinterpret_cast<const uint4 *>(p.tables + f.table0);
+    for (unsigned k = lane; k < 4 * sizeof(HuffTable) / 16; k += kWave) s_tab[k] = tab[k];
+    if (lane < kMaxBlocksPerMcu * 8) s_mcu[lane] = make_uint4(0, 0, 0, 0);
+    uint8_t comp_of[kMaxBlocksPerMcu];
+    int bpm;
+    block_components(f.ncomp, f.hs, f.vs, comp_of, &bpm);
+    const RingSrc src{reinterpret_cast<const unsigned char *>(s_ring)};
+    BitReader<RingSrc> br(src, sg.begin, sg.end);
+    int pred[3] = {0, 0, 0};
+    unsigned long long filled = sg.begin & ~15ull, pos = sg.begin;
+    uint4 *dst = reinterpret_cast<uint4 *>(p.coef + (f.coef_off + (unsigned long long)sg.mcu0 * bpm) * 64);
+    unsigned st = ST_OK;
+    for (unsigned m = 0; m < sg.nmcu; ++m) {
+        unsigned long long want = pos + kMcuBytesBound;
+        if (want > sg.end) want = sg.end;
+        while (filled < want) {
+            const unsigned long long off = filled + (unsigned long long)lane * 16;
+            if (off + 16 <= p.bytes) s_ring[(off >> 4) & (kRing / 16 - 1)] = *reinterpret_cast<const uint4 *>(p.blob + off);
+            filled += kWave * 16;
+        }
+        __syncthreads();
+        if (lane == 0) {
+            unsigned r = decode_mcu(br, reinterpret_cast<const HuffTable *>(s_tab), f.dc_sel, f.ac_sel, comp_of, bpm, pred, reinterpret_cast<int16_t *>(s_mcu));
+            if (r == ST_OK && m + 1 == sg.nmcu && !br.drained()) r = ST_CORRUPT;
+            s_st = r;
+            s_pos = br.pos;
+        }
+        __syncthreads();
+        st = s_st;
+        pos = s_pos;
+        if (st != ST_OK) break;
+        if (lane < bpm * 8) {
+            dst[(size_t)m * bpm * 8 + lane] = s_mcu[lane];
+            s_mcu[lane] = make_uint4(0, 0, 0, 0);
+        }
+    }
+    if (st != ST_OK && lane == 0) atomicCAS(p.status + sg.file, 0u, st);
+}
+
+// ---- stage 2: jidctint.c jpeg_idct_islow on one block per thread.
+// The library Pillow ships runs this transform in 16-bit SIMD lanes (jidctint-sse2 / -avx2): in0 +- in4, in7 + in3 and in5 + in1 are 16-bit adds,
+// each pass packs its output to int16 with saturation, and the final pack to bytes saturates where the C code's range table wraps (|x| >= 512).
+// Inside those lanes the SIMD code and the C code give the same samples, and no file an encoder writes leaves them; a block that does is the
+// RANGE status (`wide`), like a dequantised product outside int16: it is refused, not given pixels that differ from Pillow's.
+constexpr int kIdctThreads = 128;
+
+__device__ __forceinline__ bool fits16(long long v) { return v >= -32768 && v <= 32767; }
+
+__device__ __forceinline__ void idct_1d(const long long in[8], long long out[8], int shift, bool &wide)
+{
+    wide |= !(fits16(in[0] + in[4]) && fits16(in[0] - in[4]) && fits16(in[7] + in[3]) && fits16(in[5] + in[1]));
+    long long z2 = in[2], z3 = in[6];
+    long long z1 = (z2 + z3) * 4433;
+    long long tmp2 = z1 + z3 * (-15137);
+    long long tmp3 = z1 + z2 * 6270;
+    z2 = in[0];
+    z3 = in[4];
+    long long tmp0 = (z2 + z3) * 8192;
+    long long tmp1 = (z2 - z3) * 8192;
+    const long long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    tmp0 = in[7];
+    tmp1 = in[5];
+    tmp2 = in[3];
+    tmp3 = in[1];
+    z1 = tmp0 + tmp3;
+    z2 = tmp1 + tmp2;
+    z3 = tmp0 + tmp2;
+    long long z4 = tmp1 + tmp3;
+    const long long z5 = (z3 + z4) * 9633;
+    tmp0 *= 2446;
+    tmp1 *= 16819;
+    tmp2 *= 25172;
+    tmp3 *= 12299;
+    z1 *= -7373;
+    z2 *= -20995;
+    z3 = z3 * (-16069) + z5;
+    z4 = z4 * (-3196) + z5;
+    tmp0 += z1 + z3;
+    tmp1 += z2 + z4;
+    tmp2 += z2 + z3;
+    tmp3 += z1 + z4;
+    const long long r = 1ll << (shift - 1);
+    out[0] = (tmp10 + tmp3 + r) >> shift;
+    out[7] = (tmp10 - tmp3 + r) >> shift;
+    out[1] = (tmp11 + tmp2 + r) >> shift;
+    out[6] = (tmp11 - tmp2 + r) >> shift;
+    out[2] = (tmp12 + tmp1 + r) >> shift;
+    out[5] = (tmp12 - tmp1 + r) >> shift;
+    out[3] = (tmp13 + tmp0 + r) >> shift;
+    out[4] = (tmp13 - tmp0 + r) >> shift;
+}
+
+// libjpeg's range table (jdmaster.c prepare_range_limit_table), indexed by x & 1023
+__device__ __forceinline__ unsigned range_limit(long long v)
+{
+    const unsigned x = (unsigned)v & 1023u;
+    return x < 128 ? x + 128 : x < 512 ? 255u : x < 896 ? 0u : x - 896;
+}
+
+__global__ __launch_bounds__(kIdctThreads) void jpegdec_idct(Params p)
+{
+    const unsigned fi = blockIdx.y;
+    const FileDesc &f = p.files[fi];
+    const unsigned g = blockIdx.x * kIdctThreads + threadIdx.x;
+    if (g >= f.nblk || p.status[fi] != ST_OK) return;
+    const unsigned mcu = g / f.bpm, k = g - mcu * f.bpm;
+    const unsigned mx = mcu % f.mcux, my = mcu / f.mcux;
+    unsigned c, bx, by;
+    if (f.ncomp == 1 || k >= f.hs * f.vs) {
+        c = f.ncomp == 1 ? 0 : 1 + (k - f.hs * f.vs);
+        bx = mx;
+        by = my;
+    } else {
+        c = 0;
+        bx = mx * f.hs + k % f.hs;
+        by = my * f.vs + k / f.hs;
+    }
+    const uint4 *src = reinterpret_cast<const uint4 *>(p.coef + (f.coef_off + g) * 64);
+    int v[64];
+    bool range = false;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const uint4 w = src[r];
+        const unsigned ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int coef = (short)(ww[j >> 1] >> (16 * (j & 1)));
+            const int d = coef * (int)f.q[c][r * 8 + j];
+            range |= d < -32768 || d > 32767;
+            v[r * 8 + j] = d;
+        }
+    }
+    long long ws[64];
+#pragma unroll
+    for (int x = 0; x < 8; ++x) {                                              // pass 1: columns, descaled by CONST_BITS - PASS1_BITS
+        long long in[8], out[8];
+#pragma unroll
+        for (int y = 0; y < 8; ++y) in[y] = v[y * 8 + x];
+        idct_1d(in, out, 11, range);
+#pragma unroll
+        for (int y = 0; y < 8; ++y) {
+            range |= !fits16(out[y]);
+            ws[y * 8 + x] = out[y];
+        }
+    }
+    unsigned char *dst = p.planes + f.plane_off[c] + ((size_t)by * 8) * f.plane_w[c] + (size_t)bx * 8;
+#pragma unroll
+    for (int y = 0; y < 8; ++y) {                                              // pass 2: rows, descaled by CONST_BITS + PASS1_BITS + 3
+        long long out[8];
+        idct_1d(ws + y * 8, out, 18, range);
+        unsigned lo = 0, hi = 0;
+#pragma unroll
+        for (int x = 0; x < 8; ++x) range |= out[x] < -512 || out[x] > 511;
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+            lo |= range_limit(out[x]) << (8 * x);
+            hi |= range_limit(out[x + 4]) << (8 * x);
+        }
+        *reinterpret_cast<uint2 *>(dst + (size_t)y * f.plane_w[c]) = make_uint2(lo, hi);
+    }
+    if (range) atomicCAS(p.status + fi, 0u, (unsigned)ST_RANGE);           // stage 3 then leaves the file's output alone
+}
+
+// ---- stage 3: jdsample.c + jdcolor.c, one thread per pixel
+constexpr int kStoreThreads = 256;
+
+// the chroma sample of output pixel (x, y): plane cropped to dw x dh, mode by the luma sampling factors
+__device__ __forceinline__ int chroma_at(const unsigned char *pl, unsigned stride, unsigned hs, unsigned vs, int dw, int dh, int x, int y)
+{
+    if (hs == 1) return pl[(size_t)y * stride + x];
+    const int cx = x >> 1;
+    if (vs == 1) {                                                             // h2v1
+        const unsigned char *row = pl + (size_t)y * stride;
+        const int s = row[cx];
+        if (dw <= 2) return s;                                                 // the narrow-image rule: h2v1_upsample
+        if (x & 1) return cx == dw - 1 ? s : (3 * s + row[cx + 1] + 2) >> 2;
+        return cx == 0 ? s : (3 * s + row[cx - 1] + 1) >> 2;
+    }
+    const int cy = y >> 1;                                                     // h2v2
+    const unsigned char *near = pl + (size_t)cy * stride;
+    if (dw <= 2) return near[cx];                                              // h2v2_upsample
+    int fy = (y & 1) ? cy + 1 : cy - 1;
+    fy = fy < 0 ? 0 : fy > dh - 1 ? dh - 1 : fy;
+    const unsigned char *far = pl + (size_t)fy * stride;
+    const int s = 3 * near[cx] + far[cx];
+    if (x & 1) return cx == dw - 1 ? (4 * s + 7) >> 4 : (3 * s + 3 * near[cx + 1] + far[cx + 1] + 7) >> 4;
+    return cx == 0 ? (4 * s + 8) >> 4 : (3 * s + 3 * near[cx - 1] + far[cx - 1] + 8) >> 4;
+}
+
+__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+
+__global__ __launch_bounds__(kStoreThreads) void jpegdec_store(Params p)
+{
+    const unsigned fi = blockIdx.y;
+    const FileDesc &f = p.files[fi];
+    const unsigned g = blockIdx.x * kStoreThreads + threadIdx.x;
+    if (g >= f.width * f.height || p.status[fi] != ST_OK) return;
+    const int x = g % f.width, y = g / f.width;
+    int px[3];
+    px[0] = p.planes[f.plane_off[0] + (size_t)y * f.plane_w[0] + x];
+    if (f.ncomp == 3) {
+        const int dw = (f.width + f.hs - 1) / f.hs, dh = (f.height + f.vs - 1) / f.vs;
+        const int cb = chroma_at(p.planes + f.plane_off[1], f.plane_w[1], f.hs, f.vs, dw, dh, x, y) - 128;
+        const int cr = chroma_at(p.planes + f.plane_off[2], f.plane_w[2], f.hs, f.vs, dw, dh, x, y) - 128;
+        const int yy = px[0];
+        // FIX(1.402) = 91881, FIX(1.772) = 116130, FIX(0.34414) = 22554, FIX(0.71414) = 46802
+        px[0] = clamp255(yy + ((91881 * cr + 32768) >> 16));
+        px[1] = clamp255(yy + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+        px[2] = clamp255(yy + ((116130 * cb + 32768) >> 16));
+    }
+    if (f.form == LSPJPEG_DEC_FORM_PLANAR_F32) {
+        float *out = reinterpret_cast<float *>(f.out_ptr);
+        const float *table = reinterpret_cast<const float *>(f.table_ptr);
+        for (unsigned c = 0; c < f.ncomp; ++c) out[(size_t)c * f.plane_stride + g] = table[px[c]];
+    } else {
+        unsigned char *out = reinterpret_cast<unsigned char *>(f.out_ptr);
+        if (f.ncomp == 3) {
+            out[(size_t)g * 3 + 0] = (unsigned char)px[0];
+            out[(size_t)g * 3 + 1] = (unsigned char)px[1];
+            out[(size_t)g * 3 + 2] = (unsigned char)px[2];
+        } else {
+            out[g] = (unsigned char)px[0];
+        }
+    }
+}
+
+void fill_info(const Parsed &f, uint32_t status, uint32_t nseg, uint64_t scan_end, lspjpeg_dec_info *info)
+{
+    *info = lspjpeg_dec_info{};
+    info->status = (int32_t)status;
+    info->width = (int32_t)f.width;
+    info->height = (int32_t)f.height;
+    info->components = (int32_t)f.ncomp;
+    info->hsamp = (int32_t)f.hs;
+    info->vsamp = (int32_t)f.vs;
+    info->restart_interval = (int32_t)f.restart;
+    if (status != ST_OK) return;
+    info->mcus = (int32_t)mcu_count(f);
+    info->segments = (int32_t)nseg;
+    for (uint32_t c = 0; c < f.ncomp; ++c) {
+        if (!f.huff_seen[0][f.dc_sel[c]]) info->default_tables |= 1 << (2 * f.dc_sel[c]);
+        if (!f.huff_seen[1][f.ac_sel[c]]) info->default_tables |= 1 << (2 * f.ac_sel[c] + 1);
+    }
+    info->scan_offset = f.scan_begin;
+    info->scan_bytes = scan_end - f.scan_begin;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *lspjpeg_dec_last_error(void) { return g_err.c_str(); }
+
+int lspjpeg_dec_probe(const unsigned char *bytes, size_t len, lspjpeg_dec_info *info)
+{
+    if (!bytes || !info) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "null argument");
+    Parsed f;
+    uint32_t nseg;
+    uint64_t end;
+    const uint32_t st = examine(bytes, len, LSPJPEG_MAX_SIDE, &f, &nseg, &end);
+    fill_info(f, st, nseg, end, info);
+    return LSPJPEG_DEC_OK;
+}
+
+int64_t lspjpeg_dec_plan(const unsigned char *const *files, const size_t *lens, const lspjpeg_dec_output *outs, int n, int max_side, void *blob,
+                         size_t cap)
+{
+    if (!files || !lens || n < 1 || n > 65535) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "files, lens and 1..65535 files are required");
+    if (max_side < 1 || max_side > LSPJPEG_MAX_SIDE) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "max_side must be in 1.." + std::to_string(LSPJPEG_MAX_SIDE));
+    for (int i = 0; i < n; ++i)
+        if (!files[i]) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "file " + std::to_string(i) + " is null");
+    const int64_t need = plan(files, lens, nullptr, n, (uint32_t)max_side, nullptr);
+    if (need < 0) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "the batch needs a descriptor block of 4 GiB or more: split it");
+    if (!blob) return need;
+    if (cap < (size_t)need || reinterpret_cast<uintptr_t>(blob) % 16)
+        return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "blob must be 16-byte aligned and hold " + std::to_string(need) + " bytes");
+    std::string keep;                                                          // OutputDesc is the planner's own view of lspjpeg_dec_output
+    keep.resize(outs ? (size_t)n * sizeof(OutputDesc) : 0);
+    OutputDesc *od = outs ? reinterpret_cast<OutputDesc *>(&keep[0]) : nullptr;
+    for (int i = 0; outs && i < n; ++i) {
+        od[i].ptr = reinterpret_cast<uint64_t>(outs[i].ptr);
+        od[i].table = reinterpret_cast<uint64_t>(outs[i].table);
+        od[i].plane_stride = outs[i].plane_stride;
+        od[i].form = (uint32_t)outs[i].form;
+    }
+    const int64_t got = plan(files, lens, od, n, (uint32_t)max_side, blob);
+    if (got == -1) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "an output's form does not fit its file (RGB8: 3 components, GRAY8: 1, PLANAR_F32: a table and plane_stride >= H * W)");
+    return got;
+}
+
+int lspjpeg_dec_summary_of(const void *blob, lspjpeg_dec_summary *out)
+{
+    const BlobHeader *h = header_of(blob);
+    if (!h || !out) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "not a descriptor block of lspjpeg_dec_plan");
+    out->files = h->nfiles;
+    out->segments = h->nsegs;
+    out->max_blocks = h->max_blocks;
+    out->max_pixels = h->max_pixels;
+    out->total_blocks = h->total_blocks;
+    out->bytes = h->bytes;
+    out->workspace_bytes = h->workspace_bytes;
+    out->status_offset = h->status_off;
+    return LSPJPEG_DEC_OK;
+}
+
+int lspjpeg_dec_plan_file(const void *blob, int i, lspjpeg_dec_info *info)
+{
+    const BlobHeader *h = header_of(blob);
+    if (!h || !info || i < 0 || (uint32_t)i >= h->nfiles) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "no such file in the block");
+    const FileDesc &d = files_of(blob)[i];
+    *info = lspjpeg_dec_info{};
+    info->status = (int32_t)d.status;
+    if (d.status != ST_OK) return LSPJPEG_DEC_OK;
+    info->width = (int32_t)d.width;
+    info->height = (int32_t)d.height;
+    info->components = (int32_t)d.ncomp;
+    info->hsamp = (int32_t)d.hs;
+    info->vsamp = (int32_t)d.vs;
+    info->restart_interval = (int32_t)d.restart;
+    info->mcus = (int32_t)(d.mcux * d.mcuy);
+    info->segments = (int32_t)d.nseg;
+    const SegDesc *s = segs_of(blob) + d.seg0;
+    info->scan_offset = s[0].begin;
+    info->scan_bytes = s[d.nseg - 1].end - s[0].begin;
+    return LSPJPEG_DEC_OK;
+}
+
+int lspjpeg_dec_plan_qtable(const void *blob, int i, int c, uint16_t out[64])
+{
+    const BlobHeader *h = header_of(blob);
+    if (!h || !out || i < 0 || (uint32_t)i >= h->nfiles || c < 0 || c > 2) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "no such table in the block");
+    for (int k = 0; k < 64; ++k) out[k] = files_of(blob)[i].q[c][k];
+    return LSPJPEG_DEC_OK;
+}
+
+int lspjpeg_dec_plan_segment(const void *blob, int k, uint32_t *file, uint32_t *mcu0, uint32_t *nmcu, uint64_t *begin, uint64_t *end)
+{
+    const BlobHeader *h = header_of(blob);
+    if (!h || k < 0 || (uint32_t)k >= h->nsegs || !file || !mcu0 || !nmcu || !begin || !end)
+        return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "no such segment in the block");
+    const SegDesc &s = segs_of(blob)[k];
+    *file = s.file;
+    *mcu0 = s.mcu0;
+    *nmcu = s.nmcu;
+    *begin = s.begin;
+    *end = s.end;
+    return LSPJPEG_DEC_OK;
+}
+
+int lspjpeg_dec_host_coefficients(const void *blob, int i, int16_t *out, size_t cap_values)
+{
+    const BlobHeader *h = header_of(blob);
+    if (!h || !out || i < 0 || (uint32_t)i >= h->nfiles) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "no such file in the block");
+    if (cap_values < (size_t)files_of(blob)[i].nblk * 64) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "out is too small for the file's blocks");
+    return (int)host_coefficients(blob, i, out);
+}
+
+int lspjpeg_dec_decode(const void *blob_host, void *blob_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream)
+{
+    const BlobHeader *h = header_of(blob_host);
+    if (!h || !blob_dev || !workspace_dev) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "a planned block, its device copy and a workspace are required");
+    if (!h->has_outputs) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "the block was planned without outputs (host only)");
+    if (reinterpret_cast<uintptr_t>(blob_dev) % 16 || reinterpret_cast<uintptr_t>(workspace_dev) % 256)
+        return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "blob_dev must be 16-byte aligned and workspace_dev 256-byte aligned");
+    if (workspace_bytes < h->workspace_bytes) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "workspace needs " + std::to_string(h->workspace_bytes) + " bytes");
+    unsigned char *b = static_cast<unsigned char *>(blob_dev);
+    Params p{};
+    p.blob = b;
+    p.files = reinterpret_cast<const FileDesc *>(b + h->files_off);
+    p.segs = reinterpret_cast<const SegDesc *>(b + h->segs_off);
+    p.tables = reinterpret_cast<const HuffTable *>(b + h->tables_off);
+    p.status = reinterpret_cast<unsigned *>(b + h->status_off);
+    p.coef = static_cast<short *>(workspace_dev);
+    p.planes = static_cast<unsigned char *>(workspace_dev) + h->planes_ws_off;
+    p.nfiles = h->nfiles;
+    p.nsegs = h->nsegs;
+    p.bytes = h->bytes;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const auto grid = [](unsigned items, unsigned per) { return items ? (items + per - 1) / per : 1u; };     // a batch of refused files still launches
+    hipLaunchKernelGGL(jpegdec_entropy, dim3(grid(h->nsegs, 1)), dim3(kWave), 0, st, p);
+    hipLaunchKernelGGL(jpegdec_idct, dim3(grid(h->max_blocks, kIdctThreads), h->nfiles), dim3(kIdctThreads), 0, st, p);
+    hipLaunchKernelGGL(jpegdec_store, dim3(grid(h->max_pixels, kStoreThreads), h->nfiles), dim3(kStoreThreads), 0, st, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(LSPJPEG_DEC_ERR_HIP, std::string("jpeg decode launch: ") + hipGetErrorString(e));
+    return LSPJPEG_DEC_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,448 @@
+// jpegdec_core.h -- the host/device half of the baseline JPEG decoder (include/lspjpegdec.h): the marker parser, the scan walker that finds the
+// restart intervals, the decode tables, and the entropy decode of one restart interval.  Plain C++ with no allocation and no library calls: the
+// planner (jpegdec.hip, host) runs the parser, the device kernel and the stand-alone host checker (jpegdec_check.cpp, built with sanitizers) run
+// the SAME segment decoder, so a stream the checker has walked is a stream the kernel reads within the same bounds.
+//
+// What is decoded (jdhuff.c decode_mcu, jdmarker.c): SOF0, 8 bit, one interleaved scan, 1 component or YCbCr with luma 1x1 / 2x1 / 2x2, DRI,
+// the file's DHT tables or Annex K's where a table is absent.  Everything else is refused with a status, never decoded differently.
+#ifndef LSPJPEGDEC_CORE_H
+#define LSPJPEGDEC_CORE_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __HIPCC__
+#define LSPDEC_HD __host__ __device__
+#else
+#define LSPDEC_HD
+#endif
+
+namespace lspdec {
+
+// status words (include/lspjpegdec.h LSPJPEG_DEC_STATUS_*)
+enum : uint32_t { ST_OK = 0, ST_UNSUPPORTED = 1, ST_CORRUPT = 2, ST_RANGE = 3 };
+
+constexpr int kMaxBlocksPerMcu = 6;                  // 4:2:0: Y0 Y1 Y2 Y3 Cb Cr
+constexpr uint32_t kMcuBytesBound = 2560;            // >= 2 * ceil(6 * 1660 / 8) + 8: no MCU codes more bytes than this (the encoder's bound, stuffed)
+
+// ---- a canonical Huffman table in decode form (Annex C; the layout of jdhuff.c's d_derived_tbl without its pointers)
+struct HuffTable {
+    uint16_t look[256];        // indexed by the next 8 bits: (length << 8) | symbol of the code of <= 8 bits that starts there, 0 when it is longer
+    int32_t maxcode[17];       // [l] the largest code of length l, -1 when the table has none of that length
+    int32_t valoff[17];        // [l] index into vals of the first code of length l, minus that code
+    uint8_t vals[256];
+    uint8_t pad[8];
+};
+static_assert(sizeof(HuffTable) == 912 && sizeof(HuffTable) % 16 == 0, "HuffTable is part of the descriptor block's layout");
+
+// ---- one file of a batch, as the kernels see it
+struct FileDesc {
+    uint32_t status;           // what the parser found (ST_*): a file that is not ST_OK has no segments and is skipped by every stage
+    uint32_t width, height, ncomp;
+    uint32_t hs, vs;           // luma sampling factors (chroma is 1x1)
+    uint32_t mcux, mcuy, bpm;  // MCUs per row and column, blocks per MCU
+    uint32_t nblk;             // mcux * mcuy * bpm
+    uint32_t restart;          // MCUs per restart interval, 0 = none
+    uint32_t table0;           // index of this file's four HuffTables (DC0 AC0 DC1 AC1) in the table area
+    uint32_t seg0, nseg;       // its entries of the segment list
+    uint8_t dc_sel[4], ac_sel[4];   // per component: which DC / AC table
+    uint64_t coef_off;         // first block of the file in the coefficient workspace
+    uint64_t plane_off[3];     // byte offset of each component's block-padded plane in the plane workspace
+    uint32_t plane_w[3], plane_h[3];
+    uint16_t q[3][64];         // per component, natural order
+    uint64_t out_ptr;          // device pointer of the output
+    uint64_t table_ptr;        // device pointer of 256 floats (form 2)
+    int64_t plane_stride;      // elements between the channels of a planar output (form 2)
+    uint32_t form;             // 0: uint8 [H][W][3], 1: uint8 [H][W], 2: float32 planar through the table
+    uint32_t pad;
+};
+static_assert(sizeof(FileDesc) % 8 == 0, "FileDesc is part of the descriptor block's layout");
+
+// ---- one restart interval (a file without DRI is one segment): [begin, end) are offsets into the descriptor block, free of markers
+struct SegDesc {
+    uint32_t file;
+    uint32_t mcu0, nmcu;
+    uint32_t pad;
+    uint64_t begin, end;
+};
+
+// ---- what the marker parser extracts, fixed size (no allocation)
+struct Parsed {
+    uint32_t status;
+    uint32_t width, height, ncomp, hs, vs, restart;
+    uint8_t comp_id[4], comp_q[4], dc_sel[4], ac_sel[4];
+    uint8_t q_seen[4];
+    uint16_t q[4][64];                  // natural order
+    uint8_t huff_seen[2][2];            // [class][id]
+    uint8_t huff_bits[2][2][17];        // [class][id][length 1..16]
+    uint8_t huff_vals[2][2][256];
+    uint64_t scan_begin;                // offset of the first entropy-coded byte
+};
+
+LSPDEC_HD inline int zigzag_to_natural(int k)
+{
+    // jpeg_natural_order; function-local so that host and device code index the same constant
+    constexpr uint8_t t[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                               35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    return t[k];
+}
+
+LSPDEC_HD inline uint32_t be16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The marker parser (jdmarker.c read_markers up to the first SOS).  Every read is checked against n first.
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+LSPDEC_HD inline uint32_t parse_markers(const uint8_t *p, size_t n, uint32_t max_side, Parsed *o)
+{
+    *o = Parsed{};
+    bool sof = false, adobe = false;
+    uint32_t adobe_transform = 0;
+    if (n < 4 || p[0] != 0xff || p[1] != 0xd8) return o->status = ST_CORRUPT;
+    size_t i = 2;
+    for (;;) {
+        if (i + 2 > n) return o->status = ST_CORRUPT;                          // data that ends early
+        if (p[i] != 0xff) return o->status = ST_CORRUPT;
+        while (i + 1 < n && p[i + 1] == 0xff) ++i;                             // fill bytes between segments are legal (B.1.1.2)
+        if (i + 2 > n) return o->status = ST_CORRUPT;
+        const uint32_t m = p[i + 1];
+        i += 2;
+        if (m == 0xd8 || m == 0xd9 || (m >= 0xd0 && m <= 0xd7) || m == 0x01 || m == 0x00) return o->status = ST_CORRUPT;
+        if (i + 2 > n) return o->status = ST_CORRUPT;
+        const size_t len = be16(p + i);
+        if (len < 2 || i + len > n) return o->status = ST_CORRUPT;
+        const uint8_t *s = p + i + 2;
+        const size_t sl = len - 2;
+        if (m == 0xc0) {                                                       // SOF0
+            if (sof) return o->status = ST_CORRUPT;
+            if (sl < 6) return o->status = ST_CORRUPT;
+            const uint32_t nc = s[5];
+            if (sl != 6 + 3 * (size_t)nc) return o->status = ST_CORRUPT;
+            if (s[0] != 8) return o->status = ST_UNSUPPORTED;
+            o->height = be16(s + 1);
+            o->width = be16(s + 3);
+            if (o->width == 0) return o->status = ST_CORRUPT;
+            if (o->height == 0) return o->status = ST_UNSUPPORTED;             // the height comes in a DNL marker
+            if (o->width > max_side || o->height > max_side) return o->status = ST_UNSUPPORTED;
+            if (nc != 1 && nc != 3) return o->status = ST_UNSUPPORTED;
+            o->ncomp = nc;
+            for (uint32_t c = 0; c < nc; ++c) {
+                o->comp_id[c] = s[6 + 3 * c];
+                const uint32_t hv = s[7 + 3 * c], tq = s[8 + 3 * c];
+                if (tq > 3 || (hv >> 4) == 0 || (hv >> 4) > 4 || (hv & 15) == 0 || (hv & 15) > 4) return o->status = ST_CORRUPT;
+                o->comp_q[c] = (uint8_t)tq;
+                if (c == 0) {
+                    o->hs = hv >> 4;
+                    o->vs = hv & 15;
+                } else if (hv != 0x11) {
+                    return o->status = ST_UNSUPPORTED;
+                }
+            }
+            if (nc == 1 ? (o->hs != 1 || o->vs != 1) : !((o->hs == 1 || o->hs == 2) && (o->vs == 1 || (o->vs == 2 && o->hs == 2))))
+                return o->status = ST_UNSUPPORTED;
+            if (nc == 3 && o->comp_id[0] == 'R' && o->comp_id[1] == 'G' && o->comp_id[2] == 'B') return o->status = ST_UNSUPPORTED;
+            sof = true;
+        } else if (m >= 0xc1 && m <= 0xcf && m != 0xc4 && m != 0xc8) {         // extended, progressive, lossless, arithmetic (SOFn, DAC)
+            return o->status = ST_UNSUPPORTED;
+        } else if (m == 0xc4) {                                                // DHT: any number of tables
+            size_t at = 0;
+            while (at < sl) {
+                if (at + 17 > sl) return o->status = ST_CORRUPT;
+                const uint32_t tc = s[at] >> 4, th = s[at] & 15;
+                if (tc > 1 || th > 3) return o->status = ST_CORRUPT;
+                uint32_t count = 0;
+                for (int l = 1; l <= 16; ++l) count += s[at + l];
+                if (count > 256 || at + 17 + count > sl) return o->status = ST_CORRUPT;
+                if (th > 1) return o->status = ST_UNSUPPORTED;                 // baseline has two tables per class
+                o->huff_bits[tc][th][0] = 0;
+                for (int l = 1; l <= 16; ++l) o->huff_bits[tc][th][l] = s[at + l];
+                for (uint32_t k = 0; k < 256; ++k) o->huff_vals[tc][th][k] = k < count ? s[at + 17 + k] : 0;
+                o->huff_seen[tc][th] = 1;
+                at += 17 + count;
+            }
+        } else if (m == 0xdb) {                                                // DQT: any number of tables
+            size_t at = 0;
+            while (at < sl) {
+                const uint32_t pq = s[at] >> 4, tq = s[at] & 15;
+                if (tq > 3) return o->status = ST_CORRUPT;
+                if (pq != 0) return o->status = pq == 1 ? ST_UNSUPPORTED : ST_CORRUPT;     // 16-bit tables
+                if (at + 65 > sl) return o->status = ST_CORRUPT;
+                for (int k = 0; k < 64; ++k) o->q[tq][zigzag_to_natural(k)] = s[at + 1 + k];
+                o->q_seen[tq] = 1;
+                at += 65;
+            }
+        } else if (m == 0xdd) {                                                // DRI
+            if (sl != 2) return o->status = ST_CORRUPT;
+            o->restart = be16(s);
+        } else if (m == 0xee) {                                                // APP14: Adobe's colour transform flag
+            if (sl >= 12 && s[0] == 'A' && s[1] == 'd' && s[2] == 'o' && s[3] == 'b' && s[4] == 'e') {
+                adobe = true;
+                adobe_transform = s[11];
+            }
+        } else if (m == 0xda) {                                                // SOS
+            if (!sof) return o->status = ST_CORRUPT;
+            if (sl < 1) return o->status = ST_CORRUPT;
+            const uint32_t ns = s[0];
+            if (ns < 1 || ns > 4 || sl != 4 + 2 * (size_t)ns) return o->status = ST_CORRUPT;
+            if (ns != o->ncomp) return o->status = ST_UNSUPPORTED;             // several scans
+            for (uint32_t c = 0; c < ns; ++c) {
+                if (s[1 + 2 * c] != o->comp_id[c]) return o->status = ST_UNSUPPORTED;
+                const uint32_t td = s[2 + 2 * c] >> 4, ta = s[2 + 2 * c] & 15;
+                if (td > 3 || ta > 3) return o->status = ST_CORRUPT;
+                if (td > 1 || ta > 1) return o->status = ST_UNSUPPORTED;
+                o->dc_sel[c] = (uint8_t)td;
+                o->ac_sel[c] = (uint8_t)ta;
+            }
+            if (s[1 + 2 * ns] != 0 || s[2 + 2 * ns] != 63 || s[3 + 2 * ns] != 0) return o->status = ST_UNSUPPORTED;
+            if (adobe && adobe_transform == 0 && o->ncomp == 3) return o->status = ST_UNSUPPORTED;    // RGB, not YCbCr
+            for (uint32_t c = 0; c < o->ncomp; ++c)
+                if (!o->q_seen[o->comp_q[c]]) return o->status = ST_CORRUPT;
+            o->scan_begin = i + len;
+            return o->status = ST_OK;
+        }
+        // APPn, COM and the rest carry a length and are skipped
+        i += len;
+    }
+}
+
+LSPDEC_HD inline uint32_t mcu_count(const Parsed &f) { return ((f.width + 8 * f.hs - 1) / (8 * f.hs)) * ((f.height + 8 * f.vs - 1) / (8 * f.vs)); }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The scan walker: finds the restart intervals of the entropy-coded data that starts at f.scan_begin.  segs may be null (count only).  A
+// segment holds data bytes and 0xFF 0x00 pairs only; anything else between them is the expected RSTn, the EOI, or a refusal.
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+LSPDEC_HD inline uint32_t walk_scan(const uint8_t *p, size_t n, const Parsed &f, uint64_t base, uint32_t file, SegDesc *segs, uint32_t cap, uint32_t *nseg,
+                                  uint64_t *scan_end)
+{
+    const uint32_t total = mcu_count(f), ri = f.restart;
+    const uint32_t want = ri ? (total + ri - 1) / ri : 1;
+    size_t pos = f.scan_begin, seg_begin = f.scan_begin;
+    uint32_t k = 0;
+    *nseg = 0;
+    *scan_end = 0;
+    for (;;) {
+        while (pos < n && p[pos] != 0xff) ++pos;
+        if (pos + 1 >= n) return ST_CORRUPT;                                   // no EOI: data that ends early
+        const uint32_t m = p[pos + 1];
+        if (m == 0x00) {
+            pos += 2;
+            continue;
+        }
+        if (m == 0xff) return ST_UNSUPPORTED;                                  // fill bytes inside the scan
+        const bool rst = m >= 0xd0 && m <= 0xd7;
+        if (!rst && m != 0xd9) return ST_UNSUPPORTED;                          // another scan, a table, DNL ...
+        if (rst && ri == 0) return ST_UNSUPPORTED;
+        if (rst && m != 0xd0 + (k & 7)) return ST_CORRUPT;                     // a wrong RSTn
+        if (rst ? k + 1 >= want : k + 1 != want) return ST_CORRUPT;            // one too many, or one missing
+        if (segs) {
+            if (k >= cap) return ST_CORRUPT;
+            SegDesc &s = segs[k];
+            s.file = file;
+            s.mcu0 = ri ? k * ri : 0;
+            s.nmcu = ri ? (total - s.mcu0 < ri ? total - s.mcu0 : ri) : total;
+            s.pad = 0;
+            s.begin = base + seg_begin;
+            s.end = base + pos;
+        }
+        ++k;
+        if (!rst) {
+            *nseg = k;
+            *scan_end = pos;                                                   // the EOI marker
+            return ST_OK;
+        }
+        pos += 2;
+        seg_begin = pos;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// Decode tables.  Annex K's are the default where a file defines none (jdhuff.c std_huff_tables).  Host only: the planner builds them.
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+inline void default_huffman(int cls, int id, uint8_t bits[17], uint8_t vals[256])
+{
+    static const uint8_t kBits[4][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0},
+                                         {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d},
+                                         {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0},
+                                         {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
+    static const uint8_t kAcLuma[162] = {
+        0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1, 0x08,
+        0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28,
+        0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59,
+        0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89,
+        0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6,
+        0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
+        0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+    static const uint8_t kAcChroma[162] = {
+        0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91,
+        0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26,
+        0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58,
+        0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87,
+        0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4,
+        0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
+        0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+    const int t = 2 * id + cls;                                                // DC0 AC0 DC1 AC1
+    bits[0] = 0;
+    for (int l = 0; l < 16; ++l) bits[l + 1] = kBits[t][l];
+    for (int k = 0; k < 256; ++k) vals[k] = 0;
+    if (cls == 0) {
+        for (int k = 0; k < 12; ++k) vals[k] = (uint8_t)k;
+    } else {
+        const uint8_t *v = id == 0 ? kAcLuma : kAcChroma;
+        for (int k = 0; k < 162; ++k) vals[k] = v[k];
+    }
+}
+
+// Annex C codes -> the decode form.  false when the counts describe no prefix code (a length with more codes than it has room for).
+inline bool build_table(const uint8_t bits[17], const uint8_t vals[256], HuffTable *t)
+{
+    for (int k = 0; k < 256; ++k) t->look[k] = 0;
+    for (int k = 0; k < 8; ++k) t->pad[k] = 0;
+    uint32_t code = 0, at = 0;
+    t->maxcode[0] = -1;
+    t->valoff[0] = 0;
+    for (int l = 1; l <= 16; ++l) {
+        const uint32_t nl = bits[l];
+        if (code + nl > (1u << l)) return false;
+        t->valoff[l] = (int32_t)at - (int32_t)code;
+        t->maxcode[l] = nl ? (int32_t)(code + nl - 1) : -1;
+        if (at + nl > 256) return false;
+        for (uint32_t k = 0; k < nl; ++k, ++code, ++at) {
+            if (l <= 8) {
+                const uint32_t first = code << (8 - l);
+                for (uint32_t j = 0; j < (1u << (8 - l)); ++j) t->look[first + j] = (uint16_t)((l << 8) | vals[at]);
+            }
+        }
+        code <<= 1;
+    }
+    for (int k = 0; k < 256; ++k) t->vals[k] = vals[k];
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The entropy decode of one restart interval.  Src is the byte source: `uint8_t at(uint64_t pos) const` for pos in [begin, end) -- plain memory on
+// the host, a window in LDS on the device.  The reader never asks for a byte outside [begin, end).
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+template <class Src>
+struct BitReader {
+    const Src &src;
+    uint64_t pos, end;
+    uint64_t buf;              // the low `left` bits are the unread ones, MSB first
+    int left;
+    uint32_t status;
+
+    LSPDEC_HD BitReader(const Src &s, uint64_t begin, uint64_t end_) : src(s), pos(begin), end(end_), buf(0), left(0), status(ST_OK) {}
+
+    LSPDEC_HD void fill()
+    {
+        while (left <= 48 && pos < end) {
+            const uint32_t b = src.at(pos++);
+            if (b == 0xff) {                                                   // the walker left only 0xFF 0x00 in here; checked all the same
+                if (pos >= end || src.at(pos) != 0) {
+                    status = ST_CORRUPT;
+                    end = pos;
+                    return;
+                }
+                ++pos;
+            }
+            buf = (buf << 8) | b;
+            left += 8;
+        }
+    }
+    // the next 16 bits, zero-padded past the end of the data
+    LSPDEC_HD uint32_t peek16() const { return left >= 16 ? (uint32_t)(buf >> (left - 16)) & 0xffffu : (uint32_t)(buf << (16 - left)) & 0xffffu; }
+    LSPDEC_HD bool skip(int nbits)
+    {
+        if (nbits > left) {
+            status = ST_CORRUPT;                                               // data that ends early
+            return false;
+        }
+        left -= nbits;
+        return true;
+    }
+    LSPDEC_HD int symbol(const HuffTable &t)
+    {
+        if (left < 16) fill();
+        const uint32_t w = peek16();
+        const uint32_t e = t.look[w >> 8];
+        if (e) return skip((int)(e >> 8)) ? (int)(e & 255u) : -1;
+        for (int l = 9; l <= 16; ++l) {
+            const int32_t code = (int32_t)(w >> (16 - l));
+            if (code <= t.maxcode[l]) {
+                const int32_t at = t.valoff[l] + code;
+                if (at < 0 || at > 255) break;
+                return skip(l) ? (int)t.vals[at] : -1;
+            }
+        }
+        status = ST_CORRUPT;                                                   // a code that is in no table
+        return -1;
+    }
+    // s bits, EXTENDed (F.2.2.1); s in 1..16
+    LSPDEC_HD int receive_extend(int s)
+    {
+        if (left < s) fill();
+        if (left < s) {
+            status = ST_CORRUPT;
+            return 0;
+        }
+        left -= s;
+        const int v = (int)((buf >> left) & ((1u << s) - 1u));
+        return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
+    }
+    // after the last MCU: what is left is the padding of the last byte, nothing more
+    LSPDEC_HD bool drained() const { return pos >= end && left < 8; }
+};
+
+// One MCU: `bpm` blocks of 64 int16 in natural order into `out`, which the caller has zeroed.  comp_of[b] is the block's component.
+template <class Src>
+LSPDEC_HD inline uint32_t decode_mcu(BitReader<Src> &br, const HuffTable *tables, const uint8_t *dc_sel, const uint8_t *ac_sel, const uint8_t *comp_of, int bpm,
+                                     int *pred, int16_t *out)
+{
+    for (int b = 0; b < bpm; ++b) {
+        const int c = comp_of[b];
+        const HuffTable &dc = tables[2 * dc_sel[c]], &ac = tables[2 * ac_sel[c] + 1];
+        int16_t *blk = out + 64 * b;
+        int s = br.symbol(dc);
+        if (s < 0) return br.status;
+        if (s > 11) return ST_CORRUPT;
+        const int diff = s ? br.receive_extend(s) : 0;
+        if (br.status) return br.status;
+        pred[c] += diff;
+        if (pred[c] < -32768 || pred[c] > 32767) return ST_RANGE;
+        blk[0] = (int16_t)pred[c];
+        for (int k = 1; k < 64; ++k) {
+            const int rs = br.symbol(ac);
+            if (rs < 0) return br.status;
+            const int r = rs >> 4;
+            s = rs & 15;
+            if (s == 0) {
+                if (r != 15) break;                                            // EOB
+                k += 15;                                                       // ZRL: sixteen zeros with the loop's own step
+                if (k > 63) return ST_CORRUPT;
+                continue;
+            }
+            if (s > 10) return ST_CORRUPT;
+            k += r;
+            if (k > 63) return ST_CORRUPT;                                     // a coefficient index past 63
+            const int v = br.receive_extend(s);
+            if (br.status) return br.status;
+            blk[zigzag_to_natural(k)] = (int16_t)v;
+        }
+    }
+    return ST_OK;
+}
+
+LSPDEC_HD inline void block_components(uint32_t ncomp, uint32_t hs, uint32_t vs, uint8_t comp_of[kMaxBlocksPerMcu], int *bpm)
+{
+    int n = 0;
+    if (ncomp == 1) {
+        comp_of[n++] = 0;
+    } else {
+        for (uint32_t k = 0; k < hs * vs; ++k) comp_of[n++] = 0;
+        comp_of[n++] = 1;
+        comp_of[n++] = 2;
+    }
+    for (int k = n; k < kMaxBlocksPerMcu; ++k) comp_of[k] = 0;
+    *bpm = n;
+}
+
+}  // namespace lspdec
+#endif

@@ -1,0 +1,196 @@
+// jpegdec_plan.h -- the host half of the JPEG decoder behind include/lspjpegdec.h: the planner that lays a batch of files out in one descriptor
+// block, and stage 1 run on the host over that block.  Plain C++ (no HIP, no allocation): jpegdec.hip wraps it in the C ABI, jpegdec_check.cpp
+// builds it with sanitizers and runs it over fixtures, truncations and corruptions.
+#ifndef LSPJPEGDEC_PLAN_H
+#define LSPJPEGDEC_PLAN_H
+
+#include "jpegdec_core.h"
+
+namespace lspdec {
+
+constexpr uint32_t kMagic = 0x4a44534cu;            // "LSDJ"
+
+struct BlobHeader {
+    uint32_t magic, nfiles, nsegs, has_outputs;
+    uint32_t max_blocks, max_pixels, pad0, pad1;
+    uint64_t total_blocks, bytes, workspace_bytes;
+    uint64_t files_off, segs_off, tables_off, status_off, data_off;
+    uint64_t planes_ws_off;                         // the plane area inside the workspace (the coefficients come first)
+    uint64_t pad2;
+};
+static_assert(sizeof(BlobHeader) % 16 == 0, "the areas behind the header stay 16-byte aligned");
+
+inline uint64_t up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
+
+struct OutputDesc {
+    uint64_t ptr, table;
+    int64_t plane_stride;
+    uint32_t form;
+};
+
+inline const BlobHeader *header_of(const void *blob)
+{
+    const BlobHeader *h = static_cast<const BlobHeader *>(blob);
+    return h && h->magic == kMagic ? h : nullptr;
+}
+inline const FileDesc *files_of(const void *blob) { return reinterpret_cast<const FileDesc *>(static_cast<const char *>(blob) + header_of(blob)->files_off); }
+inline const SegDesc *segs_of(const void *blob) { return reinterpret_cast<const SegDesc *>(static_cast<const char *>(blob) + header_of(blob)->segs_off); }
+inline const HuffTable *tables_of(const void *blob) { return reinterpret_cast<const HuffTable *>(static_cast<const char *>(blob) + header_of(blob)->tables_off); }
+
+// parser + scan walker: the status of a whole file, its segment count and where its entropy-coded data ends
+inline uint32_t examine(const uint8_t *p, size_t n, uint32_t max_side, Parsed *f, uint32_t *nseg, uint64_t *scan_end)
+{
+    *nseg = 0;
+    *scan_end = 0;
+    if (parse_markers(p, n, max_side, f) != ST_OK) return f->status;
+    // the Huffman tables the scan uses must describe prefix codes (jdhuff.c jpeg_make_d_derived_tbl refuses the others)
+    for (uint32_t c = 0; c < f->ncomp; ++c)
+        for (int cls = 0; cls < 2; ++cls) {
+            const int id = cls ? f->ac_sel[c] : f->dc_sel[c];
+            if (!f->huff_seen[cls][id]) continue;
+            HuffTable t;
+            if (!build_table(f->huff_bits[cls][id], f->huff_vals[cls][id], &t)) return f->status = ST_CORRUPT;
+        }
+    const uint32_t st = walk_scan(p, n, *f, 0, 0, nullptr, 0, nseg, scan_end);
+    if (st != ST_OK) {
+        *nseg = 0;
+        return f->status = st;
+    }
+    return ST_OK;
+}
+
+// Returns the size of the block; writes it when blob is not null.  -1: an output form that does not fit its file; -2: past 4 GiB / 2^32 segments.
+inline int64_t plan(const uint8_t *const *files, const size_t *lens, const OutputDesc *outs, int n, uint32_t max_side, void *blob)
+{
+    uint64_t nsegs = 0, data = 0;
+    Parsed f;
+    for (int i = 0; i < n; ++i) {
+        uint32_t ns;
+        uint64_t e;
+        if (examine(files[i], lens[i], max_side, &f, &ns, &e) == ST_OK) {
+            nsegs += ns;
+            data += e - f.scan_begin;
+        }
+    }
+    BlobHeader h{};
+    h.magic = kMagic;
+    h.nfiles = (uint32_t)n;
+    h.files_off = sizeof(BlobHeader);
+    h.segs_off = up(h.files_off + (uint64_t)n * sizeof(FileDesc), 16);
+    h.tables_off = up(h.segs_off + nsegs * sizeof(SegDesc), 16);
+    h.status_off = h.tables_off + (uint64_t)n * 4 * sizeof(HuffTable);
+    h.data_off = up(h.status_off + (uint64_t)n * 4, 16);
+    h.bytes = up(h.data_off + data, 16) + 16;                                  // the kernel's 16-byte loads stay inside the block
+    if (h.bytes >> 32 || nsegs >> 32) return -2;
+    h.nsegs = (uint32_t)nsegs;
+    if (!blob) return (int64_t)h.bytes;
+
+    char *b = static_cast<char *>(blob);
+    for (uint64_t k = 0; k < h.bytes; ++k) b[k] = 0;
+    FileDesc *fd = reinterpret_cast<FileDesc *>(b + h.files_off);
+    SegDesc *sd = reinterpret_cast<SegDesc *>(b + h.segs_off);
+    HuffTable *ht = reinterpret_cast<HuffTable *>(b + h.tables_off);
+    uint32_t *status = reinterpret_cast<uint32_t *>(b + h.status_off);
+    uint64_t at = h.data_off, planes = 0;
+    uint32_t seg = 0;
+    h.has_outputs = 1;                                                         // until a decodable file turns up without one
+    for (int i = 0; i < n; ++i) {
+        FileDesc &d = fd[i];
+        uint32_t ns;
+        uint64_t e;
+        d.status = status[i] = examine(files[i], lens[i], max_side, &f, &ns, &e);
+        d.table0 = 4 * (uint32_t)i;
+        d.seg0 = seg;
+        if (d.status != ST_OK) continue;
+        d.width = f.width;
+        d.height = f.height;
+        d.ncomp = f.ncomp;
+        d.hs = f.hs;
+        d.vs = f.vs;
+        d.mcux = (f.width + 8 * f.hs - 1) / (8 * f.hs);
+        d.mcuy = (f.height + 8 * f.vs - 1) / (8 * f.vs);
+        d.bpm = f.ncomp == 1 ? 1 : f.hs * f.vs + 2;
+        d.nblk = d.mcux * d.mcuy * d.bpm;
+        d.restart = f.restart;
+        d.nseg = ns;
+        d.coef_off = h.total_blocks;
+        for (uint32_t c = 0; c < f.ncomp; ++c) {
+            d.dc_sel[c] = f.dc_sel[c];
+            d.ac_sel[c] = f.ac_sel[c];
+            d.plane_w[c] = d.mcux * 8 * (c == 0 ? f.hs : 1);
+            d.plane_h[c] = d.mcuy * 8 * (c == 0 ? f.vs : 1);
+            d.plane_off[c] = planes;
+            planes += up((uint64_t)d.plane_w[c] * d.plane_h[c], 16);
+            for (int k = 0; k < 64; ++k) d.q[c][k] = f.q[f.comp_q[c]][k];
+        }
+        for (int id = 0; id < 2; ++id)
+            for (int cls = 0; cls < 2; ++cls) {
+                uint8_t bits[17], vals[256];
+                if (f.huff_seen[cls][id]) {
+                    for (int l = 0; l < 17; ++l) bits[l] = f.huff_bits[cls][id][l];
+                    for (int k = 0; k < 256; ++k) vals[k] = f.huff_vals[cls][id][k];
+                } else {
+                    default_huffman(cls, id, bits, vals);
+                }
+                if (!build_table(bits, vals, &ht[d.table0 + 2 * id + cls]))    // an unused table of the file may be no prefix code: an empty table
+                    for (int l = 0; l < 17; ++l) ht[d.table0 + 2 * id + cls].maxcode[l] = -1;
+            }
+        // the entropy-coded bytes, and the segments with offsets into the block
+        const uint64_t nbytes = e - f.scan_begin;
+        for (uint64_t k = 0; k < nbytes; ++k) b[at + k] = (char)files[i][f.scan_begin + k];
+        uint32_t got;
+        uint64_t end;
+        walk_scan(files[i], lens[i], f, at - f.scan_begin, (uint32_t)i, sd + seg, ns, &got, &end);
+        seg += ns;
+        at += nbytes;
+        h.total_blocks += d.nblk;
+        if (d.nblk > h.max_blocks) h.max_blocks = d.nblk;
+        if (d.width * d.height > h.max_pixels) h.max_pixels = d.width * d.height;
+        if (outs && outs[i].ptr) {
+            const OutputDesc &o = outs[i];
+            if (o.form > 2 || (o.form == 0 && f.ncomp != 3) || (o.form == 1 && f.ncomp != 1) || (o.form == 2 && (!o.table || o.plane_stride < (int64_t)d.width * d.height)))
+                return -1;
+            d.out_ptr = o.ptr;
+            d.table_ptr = o.table;
+            d.plane_stride = o.plane_stride;
+            d.form = o.form;
+        } else {
+            h.has_outputs = 0;
+        }
+    }
+    h.planes_ws_off = up(h.total_blocks * 64 * sizeof(int16_t), 256);
+    h.workspace_bytes = up(h.planes_ws_off + planes, 256) + 256;
+    *reinterpret_cast<BlobHeader *>(b) = h;
+    return (int64_t)h.bytes;
+}
+
+struct MemSrc {
+    const uint8_t *base;
+    uint8_t at(uint64_t pos) const { return base[pos]; }
+};
+
+// stage 1 of file i on the host: the status the kernel would leave, and (on ST_OK only) the coefficients
+inline uint32_t host_coefficients(const void *blob, int i, int16_t *out)
+{
+    const FileDesc &d = files_of(blob)[i];
+    if (d.status != ST_OK) return d.status;
+    uint8_t comp_of[kMaxBlocksPerMcu];
+    int bpm;
+    block_components(d.ncomp, d.hs, d.vs, comp_of, &bpm);
+    const MemSrc src{static_cast<const uint8_t *>(blob)};
+    for (uint64_t k = 0; k < (uint64_t)d.nblk * 64; ++k) out[k] = 0;
+    for (uint32_t s = 0; s < d.nseg; ++s) {
+        const SegDesc &sg = segs_of(blob)[d.seg0 + s];
+        BitReader<MemSrc> br(src, sg.begin, sg.end);
+        int pred[3] = {0, 0, 0};
+        for (uint32_t m = 0; m < sg.nmcu; ++m) {
+            const uint32_t st = decode_mcu(br, tables_of(blob) + d.table0, d.dc_sel, d.ac_sel, comp_of, bpm, pred, out + (uint64_t)(sg.mcu0 + m) * bpm * 64);
+            if (st != ST_OK) return st;
+        }
+        if (!br.drained()) return ST_CORRUPT;
+    }
+    return ST_OK;
+}
+
+}  // namespace lspdec
+#endif

@@ -13,6 +13,9 @@ Layout (AVI 1.0, little-endian, no OpenDML; see DESIGN.md section 20)::
 of 'movi' from complete JPEG files.  ``DeviceMuxer`` builds the same bytes on the device (include/lspavi.h) behind ``lspjpeg_encode`` and
 brings them over in one copy; ``AviWriter.append_fragment`` takes them.  No player or demuxer can be run where this is built, so the
 container is pinned on the strict parser of tests/avi_parser.py and on Pillow decoding every chunk: it is *player-unpinned*.
+
+``AviReader`` is the way back: a host-side parser of exactly these files, whose ``frames()`` decodes the chunks on the device
+(jpeg.JpegDecoder) to the pixels Pillow returns for them.
 """
 from __future__ import annotations
 
@@ -252,6 +255,122 @@ def write_avi(path: str, jpegs: Sequence[bytes], waveform=None, fps: int = 60, a
                 raise ValueError("%d frames need %d samples, the waveform has %d" % (k + len(part), b, wave.shape[0]))
             out.append_jpegs(part, None if wave is None else wave[a:b])
         return out.nframes
+
+
+class AviError(ValueError):
+    """the file is not an AVI ``AviReader`` reads"""
+
+
+class AviReader:
+    """The way back from the files ``AviWriter`` and the live recorder write: a host-side RIFF parser for AVI 1.0 with 'idx1' (one 'MJPG'
+    video stream, optionally one PCM or float audio stream, no OpenDML) and, through ``frames``, the device decode of its chunks
+    (jpeg.JpegDecoder: the pixels Pillow returns for each chunk).  Anything else is refused with an ``AviError``.  The file is read once,
+    at construction; chunks are handed out by their index entries.  Chunks without DHT segments are fine: the decoder falls back on
+    the standard tables."""
+
+    def __init__(self, path: str):
+        self.path = path
+        with open(path, "rb") as f:
+            b = self._data = f.read()
+        need = self._need
+        need(len(b) >= 12 and b[:4] == b"RIFF" and b[8:12] == b"AVI ", "not a RIFF 'AVI ' file")
+        need(self._u32(4) + 8 == len(b), "the RIFF size does not match the file (truncated, or an OpenDML file continued in further RIFF chunks)")
+        top = self._children(12, len(b))
+        need([c[0] for c in top] == [b"LIST", b"LIST", b"idx1"], "top level is %r, expected LIST hdrl, LIST movi, idx1" % [c[0] for c in top])
+        h0, h1 = self._list(top[0], b"hdrl")
+        hdrl = self._children(h0, h1)
+        need(len(hdrl) >= 2 and hdrl[0][0] == b"avih" and hdrl[0][2] >= 40, "hdrl does not start with avih")
+        streams = [c for c in hdrl[1:] if c[0] == b"LIST" and bytes(b[c[1]:c[1] + 4]) == b"strl"]
+        need(len(streams) in (1, 2) and self._u32(hdrl[0][1] + 24) == len(streams), "one video stream and at most one audio stream are read (the file has %d)" % len(streams))
+        # video
+        strh, strf = self._strl(streams[0])
+        need(bytes(b[strh:strh + 4]) == b"vids", "stream 0 is not the video")
+        need(bytes(b[strf + 16:strf + 20]) == b"MJPG", "video compression %r: only MJPG is read" % bytes(b[strf + 16:strf + 20]))
+        scale, rate = self._u32(strh + 20), self._u32(strh + 24)
+        need(scale >= 1 and rate >= 1 and rate % scale == 0, "a frame rate of %d / %d is no whole number" % (rate, scale))
+        self.fps = rate // scale
+        self.width, self.height = self._u32(strf + 4), self._u32(strf + 8)
+        self.channels = 3 if int.from_bytes(b[strf + 14:strf + 16], "little") == 24 else 1
+        # audio
+        self.audio_rate = self.audio_format = None
+        if len(streams) == 2:
+            strh, strf = self._strl(streams[1])
+            need(bytes(b[strh:strh + 4]) == b"auds", "stream 1 is not audio")
+            tag, nch, bits = (int.from_bytes(b[strf + o:strf + o + 2], "little") for o in (0, 2, 14))
+            fmt = {(3, 32): "f32", (1, 16): "s16"}.get((tag, bits))
+            need(fmt is not None and nch == 1, "audio format tag %d with %d bits and %d channels: mono float32 or int16 PCM is read" % (tag, bits, nch))
+            self.audio_rate, self.audio_format = self._u32(strf + 4), fmt
+        # movi + idx1
+        m0, m1 = self._list(top[1], b"movi")
+        _, i0, n = top[2]
+        need(n % 16 == 0, "idx1 has %d bytes" % n)
+        self._video, self._audio = [], []
+        for k in range(n // 16):
+            ckid, off, length = bytes(b[i0 + 16 * k:i0 + 16 * k + 4]), self._u32(i0 + 16 * k + 8), self._u32(i0 + 16 * k + 12)
+            at = m0 - 4 + off                                  # offsets count from the 'movi' fourcc
+            need(at + 8 + length <= m1 and bytes(b[at:at + 4]) == ckid and self._u32(at + 4) == length, "index entry %d does not point at its chunk" % k)
+            if ckid == b"00dc":
+                self._video.append((at + 8, length))
+            elif ckid == b"01wb" and self.audio_rate is not None:
+                self._audio.append((at + 8, length))
+            else:
+                raise AviError("index entry %d names chunk %r" % (k, ckid))
+        self.nframes = len(self._video)
+
+    # ---- RIFF ---------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _need(cond, what):
+        if not cond:
+            raise AviError(what)
+
+    def _u32(self, at: int) -> int:
+        self._need(at + 4 <= len(self._data), "the file ends inside a 32-bit field at %d" % at)
+        return int.from_bytes(self._data[at:at + 4], "little")
+
+    def _children(self, start: int, end: int):
+        out, at = [], start
+        while at < end:
+            self._need(at + 8 <= end, "a chunk header at %d crosses the end of its list" % at)
+            cc, n = bytes(self._data[at:at + 4]), self._u32(at + 4)
+            self._need(at + 8 + n <= end, "chunk %r at %d crosses the end of its list" % (cc, at))
+            out.append((cc, at + 8, n))
+            at += 8 + n + (n & 1)
+        return out
+
+    def _list(self, child, kind: bytes):
+        cc, at, n = child
+        self._need(cc == b"LIST" and n >= 4 and bytes(self._data[at:at + 4]) == kind, "expected LIST %r" % kind)
+        return at + 4, at + n
+
+    def _strl(self, child):
+        parts = {cc: (at, n) for cc, at, n in self._children(child[1] + 4, child[1] + child[2])}
+        self._need(b"strh" in parts and b"strf" in parts and parts[b"strh"][1] >= 48 and parts[b"strf"][1] >= 16, "a stream list without strh / strf")
+        return parts[b"strh"][0], parts[b"strf"][0]
+
+    # ---- content ------------------------------------------------------------------------------------------------------------
+    def jpeg(self, i: int) -> bytes:
+        """video chunk i: one complete JPEG file"""
+        at, n = self._video[i]
+        return bytes(self._data[at:at + n])
+
+    def audio(self) -> Optional[np.ndarray]:
+        """the audio stream's samples as written (float32 or int16), None without one"""
+        if self.audio_rate is None:
+            return None
+        raw = b"".join(bytes(self._data[at:at + n]) for at, n in self._audio)
+        return np.frombuffer(raw, dtype="<f4" if self.audio_format == "f32" else "<i2")
+
+    def frames(self, start: int = 0, stop: Optional[int] = None, decoder=None, batch: int = 64):
+        """Yields frames start .. stop - 1 as uint8 device tensors ([H, W, 3], or [H, W] for a grayscale file), decoded ``batch`` chunks per
+        call of ``decoder`` (a jpeg.JpegDecoder; by default one on cuda:0 sized for this file).  A chunk the decoder refuses raises
+        jpeg.JpegError."""
+        start, stop, _ = slice(start, stop).indices(self.nframes)
+        if decoder is None:
+            from .jpeg import JpegDecoder
+            decoder = JpegDecoder("cuda:0", max_side=max(self.width, self.height, 1), max_batch=batch)
+        for k in range(start, stop, batch):
+            for frame in decoder.decode([self.jpeg(i) for i in range(k, min(k + batch, stop))]):
+                yield frame
 
 
 class DeviceMuxer:
