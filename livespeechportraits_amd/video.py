@@ -373,34 +373,62 @@ class AviReader:
                 yield frame
 
 
-class DeviceMuxer:
+class _MuxBuffers:
+    """What the two device muxers share: the library, the encoder, the JPEG header on the device (padded to whole dwords), the fragment
+    buffer ``_out``, the workspace ``_ws``, status + index in one tensor ``_meta`` with its pinned mirror, and the pinned mirror of the bytes."""
+
+    def __init__(self, encoder, rate: int, fps: int):
+        from . import _native as N
+        if encoder.max_batch > N.AVI_MAX_BATCH:
+            raise ValueError("the muxer packs at most %d frames per call (encoder.max_batch = %d)" % (N.AVI_MAX_BATCH, encoder.max_batch))
+        self.N, self.lib, self.enc = N, N.load(), encoder
+        self.rate, self.fps, self.device = int(rate), int(fps), encoder.device
+
+    def _allocate(self, capacity: int, ws_bytes: int, meta_rows: int) -> None:
+        """``meta_rows``: rows of 4 words, the status block(s) first, then 2 * max_batch index rows"""
+        import torch
+        self.capacity, self._ws_bytes = int(capacity), int(ws_bytes)
+        if self.capacity == 0 or self._ws_bytes == 0:
+            raise ValueError("lspavi: geometry, batch, rate or fps out of range")
+        dev, header = self.device, self.enc.header
+        self._header = torch.frombuffer(bytearray(header + b"\0" * (-len(header) % 4)), dtype=torch.uint8).to(dev)
+        self._out = torch.empty(self.capacity, dtype=torch.uint8, device=dev)
+        self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=dev)
+        self._meta = torch.empty((meta_rows, 4), dtype=torch.int32, device=dev)
+        self._meta_host = torch.empty((meta_rows, 4), dtype=torch.int32, pin_memory=True)
+        self._host = torch.empty(0, dtype=torch.uint8)
+
+    def _is_wave(self, t) -> bool:
+        """a contiguous 1-D float32 tensor on this device?"""
+        import torch
+        return isinstance(t, torch.Tensor) and t.dim() == 1 and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()
+
+    def _fetch(self, total: int, stream) -> np.ndarray:
+        """exactly the first ``total`` bytes of ``_out`` in one copy on ``stream``, waited for: a view of pinned memory"""
+        import torch
+        if self._host.numel() < total:
+            self._host = torch.empty(max(total, 2 * self._host.numel()), dtype=torch.uint8, pin_memory=True)
+        with torch.cuda.stream(stream):
+            self._host[:total].copy_(self._out[:total], non_blocking=True)
+        stream.synchronize()
+        return self._host.numpy()[:total]
+
+
+class DeviceMuxer(_MuxBuffers):
     """``lspjpeg_encode`` then ``lspavi_pack`` (include/lspavi.h) on the current stream: a batch of uint8 device frames becomes its part of
     the file's 'movi' list on the device -- chunk headers, the JPEG header, the entropy-coded bytes, pad bytes and the interleaved audio -- and
     crosses PCIe in ONE copy with its index entries.  Owns the fragment buffer, workspace, index and status tensors and their pinned mirrors;
     uses ``encoder``'s output slab, so the encoder must not be used on its own while a batch is in flight here."""
 
     def __init__(self, encoder, audio_format: Optional[str] = "f32", rate: int = 16000, fps: int = 60):
-        import torch
-        from . import _native as N
         if audio_format is not None and audio_format not in AUDIO_FORMATS:
             raise ValueError("audio_format must be one of %s or None" % sorted(AUDIO_FORMATS))
-        if encoder.max_batch > N.AVI_MAX_BATCH:
-            raise ValueError("the muxer packs at most %d frames per call (encoder.max_batch = %d)" % (N.AVI_MAX_BATCH, encoder.max_batch))
-        self.N, self.lib, self.enc = N, N.load(), encoder
-        self.audio_format, self.rate, self.fps, self.device = audio_format, int(rate), int(fps), encoder.device
-        B = encoder.max_batch
-        fmt = N.AVI_AUDIO_FORMATS[audio_format]
-        self.capacity = int(self.lib.lspavi_capacity_bytes(len(encoder.header), encoder.capacity, B, fmt, self.rate, self.fps))
-        self._ws_bytes = int(self.lib.lspavi_workspace_bytes(B))
-        if self.capacity == 0 or self._ws_bytes == 0:
-            raise ValueError("lspavi: geometry, batch, rate or fps out of range")
-        dev = self.device
-        self._header = torch.frombuffer(bytearray(encoder.header + b"\0" * (-len(encoder.header) % 4)), dtype=torch.uint8).to(dev)
-        self._out = torch.empty(self.capacity, dtype=torch.uint8, device=dev)
-        self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=dev)
-        self._meta = torch.empty((1 + 2 * B, 4), dtype=torch.int32, device=dev)        # row 0: the status block; then the index
-        self._meta_host = torch.empty((1 + 2 * B, 4), dtype=torch.int32, pin_memory=True)
-        self._host = torch.empty(0, dtype=torch.uint8)
+        super().__init__(encoder, rate, fps)
+        self.audio_format = audio_format
+        B, lib = encoder.max_batch, self.lib
+        fmt = self.N.AVI_AUDIO_FORMATS[audio_format]
+        self._allocate(lib.lspavi_capacity_bytes(len(encoder.header), encoder.capacity, B, fmt, self.rate, self.fps), lib.lspavi_workspace_bytes(B),
+                       1 + 2 * B)                               # row 0: the status block; then the index
         self._pending = None
 
     def submit(self, frames, frame0: int, audio_dev=None) -> None:
@@ -415,9 +443,7 @@ class DeviceMuxer:
         if audio_dev is not None:
             if self.audio_format is None:
                 raise ValueError("this muxer was made without an audio format")
-            ok = isinstance(audio_dev, torch.Tensor) and audio_dev.dim() == 1 and audio_dev.dtype == torch.float32 \
-                and audio_dev.device == self.device and audio_dev.is_contiguous()
-            if not ok:
+            if not self._is_wave(audio_dev):
                 raise ValueError("audio_dev must be a contiguous 1-D float32 tensor on %s" % self.device)
             fmt, wave, nwave = self.N.AVI_AUDIO_FORMATS[self.audio_format], audio_dev.data_ptr(), audio_dev.shape[0]
         b = self.enc.enqueue(frames)
@@ -436,7 +462,6 @@ class DeviceMuxer:
         """Wait for the submitted batch, copy exactly the fragment's bytes in one copy; returns ``(data, index, nframes, nsamples,
         largest_video, largest_audio)``, what AviWriter.append_fragment takes.  ``data`` is a view of pinned memory, valid until the next
         collect()."""
-        import torch
         if self._pending is None:
             raise RuntimeError("nothing submitted")
         b, audio, frame0, stream = self._pending
@@ -446,13 +471,9 @@ class DeviceMuxer:
         total, nchunk, largest_video, largest_audio = (int(v) for v in meta[0])
         if nchunk != (2 * b if audio else b) or not 0 < total <= self.capacity or total & 1:
             raise RuntimeError("lspavi_pack returned %d bytes in %d chunks for %d frames (capacity %d)" % (total, nchunk, b, self.capacity))
-        if self._host.numel() < total:
-            self._host = torch.empty(max(total, 2 * self._host.numel()), dtype=torch.uint8, pin_memory=True)
-        with torch.cuda.stream(stream):
-            self._host[:total].copy_(self._out[:total], non_blocking=True)
-        stream.synchronize()
+        data = self._fetch(total, stream)
         nsamples = frame_sample(frame0 + b, self.rate, self.fps) - frame_sample(frame0, self.rate, self.fps) if audio else 0
-        return self._host.numpy()[:total], meta[1:1 + nchunk].copy(), b, nsamples, largest_video, largest_audio
+        return data, meta[1:1 + nchunk].copy(), b, nsamples, largest_video, largest_audio
 
 
 def clip_audio(video: AviWriter, audio, device):
@@ -594,32 +615,18 @@ class LiveRecording:
             raise AviFull("session %d: the fresh %s file (max_bytes=%d) cannot take %d frames" % (self.sid, self.which, self.writer.max_bytes, count))
 
 
-class DeviceMultiMuxer:
+class DeviceMultiMuxer(_MuxBuffers):
     """``lspjpeg_encode`` then ``lspavi_pack_multi`` (include/lspavi.h): one batch of device frames that belongs to up to 16 files becomes
     one fragment per file on the device, with the audio taken from per-session rings.  One encode, two launches, one copy of status + index
     and one copy of the bytes, whatever the number of files.  Uses ``encoder``'s slab like DeviceMuxer."""
 
     def __init__(self, encoder, rate: int = 16000, fps: int = 60):
-        import torch
-        from . import _native as N
-        if encoder.max_batch > N.AVI_MAX_BATCH:
-            raise ValueError("the muxer packs at most %d frames per call (encoder.max_batch = %d)" % (N.AVI_MAX_BATCH, encoder.max_batch))
-        self.N, self.lib, self.enc = N, N.load(), encoder
-        self.rate, self.fps, self.device = int(rate), int(fps), encoder.device
-        B = encoder.max_batch
+        super().__init__(encoder, rate, fps)
+        B, N, lib = encoder.max_batch, self.N, self.lib
         self.max_runs = R = min(B, N.AVI_MAX_STREAMS)
-        self.capacity = int(self.lib.lspavi_capacity_bytes_multi(len(encoder.header), encoder.capacity, B, R, self.rate, self.fps))
-        self._ws_bytes = int(self.lib.lspavi_workspace_bytes_multi(B))
-        if self.capacity == 0 or self._ws_bytes == 0:
-            raise ValueError("lspavi: geometry, batch, rate or fps out of range")
-        dev = self.device
-        self._header = torch.frombuffer(bytearray(encoder.header + b"\0" * (-len(encoder.header) % 4)), dtype=torch.uint8).to(dev)
-        self._out = torch.empty(self.capacity, dtype=torch.uint8, device=dev)
-        self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=dev)
         self._srows = R * N.AVI_STATUS_WORDS // 4                                     # rows of 4 words the status rows take
-        self._meta = torch.empty((self._srows + 2 * B, 4), dtype=torch.int32, device=dev)  # the status rows, then the index
-        self._meta_host = torch.empty((self._srows + 2 * B, 4), dtype=torch.int32, pin_memory=True)
-        self._host = torch.empty(0, dtype=torch.uint8)
+        self._allocate(lib.lspavi_capacity_bytes_multi(len(encoder.header), encoder.capacity, B, R, self.rate, self.fps),
+                       lib.lspavi_workspace_bytes_multi(B), self._srows + 2 * B)       # the status rows, then the index
         self._table = (N.AviRun * N.AVI_MAX_STREAMS)()
 
     def pack(self, frames, runs):
@@ -634,11 +641,8 @@ class DeviceMultiMuxer:
             raise ValueError("a batch is split into 1..%d runs (got %d)" % (self.N.AVI_MAX_STREAMS, len(runs)))
         first = 0
         for j, (count, frame0, fmt, ring, sample0, begin, end) in enumerate(runs):
-            if fmt is not None:
-                ok = isinstance(ring, torch.Tensor) and ring.dim() == 1 and ring.dtype == torch.float32 and ring.device == self.device \
-                    and ring.is_contiguous()
-                if not ok:
-                    raise ValueError("run %d: the ring must be a contiguous 1-D float32 tensor on %s" % (j, self.device))
+            if fmt is not None and not self._is_wave(ring):
+                raise ValueError("run %d: the ring must be a contiguous 1-D float32 tensor on %s" % (j, self.device))
             t = self._table[j]
             t.first, t.count, t.audio_format, t.reserved, t.frame0 = first, int(count), self.N.AVI_AUDIO_FORMATS[fmt], 0, int(frame0)
             t.ring_dev = ring.data_ptr() if fmt is not None else None
@@ -667,12 +671,7 @@ class DeviceMultiMuxer:
                     j, nbytes, off, nchunk, row0, at, row))
             at, row = (off + nbytes + 15) & ~15, row + nchunk
         total = int(status[-1][0]) + int(status[-1][1])
-        if self._host.numel() < total:
-            self._host = torch.empty(max(total, 2 * self._host.numel()), dtype=torch.uint8, pin_memory=True)
-        with torch.cuda.stream(stream):
-            self._host[:total].copy_(self._out[:total], non_blocking=True)
-        stream.synchronize()
-        host, out = self._host.numpy(), []
+        host, out = self._fetch(total, stream), []
         for j, (count, frame0, fmt, *_rest) in enumerate(runs):
             off, nbytes, nchunk, largest_video, largest_audio, row0 = (int(v) for v in status[j][:6])
             nsamples = frame_sample(int(frame0) + int(count), self.rate, self.fps) - frame_sample(frame0, self.rate, self.fps) if fmt is not None else 0

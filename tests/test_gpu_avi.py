@@ -27,11 +27,11 @@ def wave_of(n, seed=3):
     return x
 
 
-def host_fragment(tmp_path, geom, files, fmt, wave, frame0):
+def host_fragment(tmp_path, geom, files, fmt, wave, frame0, rate=16000, fps=60):
     """the fragment of frames frame0 .. of a file that already holds frame0 frames, built on the host"""
     from livespeechportraits_amd.video import AviWriter
     h, w, ch = GEOMETRIES[geom]
-    out = AviWriter(str(tmp_path / "host.avi"), w, h, ch, audio_rate=None if fmt is None else 16000, audio_format=fmt or "f32")
+    out = AviWriter(str(tmp_path / "host.avi"), w, h, ch, fps=fps, audio_rate=None if fmt is None else rate, audio_format=fmt or "f32")
     if frame0:
         a, b = out.span(0, frame0)
         out.append_jpegs([files[0]] * frame0, None if fmt is None else wave[a:b])
@@ -103,6 +103,109 @@ def test_a_waveform_one_sample_short_is_refused(gpu_device, tmp_path):
     assert out.nframes == 0 and out.nsamples == 0
     out.close()
     assert P.parse(open(tmp_path / "a.avi", "rb").read())["chunks"] == []
+
+
+def _c16_batch(gpu_device, batch=3):
+    """(device frames, their files) of ``batch`` 16x16x3 images"""
+    pixels = images("c16", batch)
+    return torch.from_numpy(pixels).to(gpu_device), [M.encode(p, 75) for p in pixels]
+
+
+def _pack_and_compare(gpu_device, tmp_path, fmt, frame0, wave, rate=16000, fps=60):
+    """one batch of 3 through DeviceMuxer with exactly ``wave`` as the clip's waveform: fragment, index and counts equal the host's"""
+    from livespeechportraits_amd.jpeg import JpegEncoder
+    from livespeechportraits_amd.video import DeviceMuxer
+    frames_dev, files = _c16_batch(gpu_device)
+    enc = JpegEncoder((16, 16), 3, 75, gpu_device, max_batch=3)
+    mux = DeviceMuxer(enc, fmt, rate=rate, fps=fps)
+    want = host_fragment(tmp_path, "c16", files, fmt, wave, frame0, rate, fps)
+    mux._out.fill_(0xA5)
+    mux.submit(frames_dev, frame0, torch.from_numpy(wave).to(gpu_device))
+    data, index, *rest = mux.collect()
+    where = (fmt, frame0, rate, fps)
+    assert tuple(rest) == tuple(want[2:]), where
+    assert index.tobytes() == want[1].tobytes(), where
+    assert data.tobytes() == want[0], where
+    tail = mux._out[len(want[0]):].cpu().numpy()
+    assert tail.size >= 16 and (tail == 0xA5).all(), where
+    enc.close()
+    return want
+
+
+@pytest.mark.parametrize("frame0", [0, 7])
+@pytest.mark.parametrize("fmt", ["f32", "s16"])
+def test_a_waveform_that_ends_where_the_batch_ends(gpu_device, tmp_path, fmt, frame0):
+    """wave_samples == s(frame0 + 3): the batch's last sample is the waveform's last, so the one run's ring is full to its last sample"""
+    n = (frame0 + 3) * 16000 // 60
+    want = _pack_and_compare(gpu_device, tmp_path, fmt, frame0, wave_of(n)[:n])
+    assert want[3] == n - frame0 * 16000 // 60
+
+
+@pytest.mark.parametrize("frame0,n", [(0, 1), (1, 2)])
+@pytest.mark.parametrize("fmt", ["f32", "s16"])
+def test_fewer_samples_than_frames(gpu_device, tmp_path, fmt, frame0, n):
+    """30 samples/s at 60 frames/s: frames carry 0, 1, 0, 1 .. samples, so every other '01wb' chunk is empty and a 16-byte piece can span
+    three chunks; the waveform holds exactly the ``n`` samples frames frame0 .. frame0 + 2 end at"""
+    wave = np.array([0.25, -1.5], np.float32)[:n]
+    want = _pack_and_compare(gpu_device, tmp_path, fmt, frame0, wave, rate=30, fps=60)
+    lengths = [int(n_) for ck, _, _, n_ in want[1] if ck == 0x62773130]
+    bps = 4 if fmt == "f32" else 2
+    assert lengths == [bps * ((frame0 + k) & 1) for k in range(3)]
+
+
+@pytest.mark.parametrize("fmt", [None, "f32"])
+def test_lspavi_pack_writes_what_its_header_says_and_no_more(gpu_device, tmp_path, fmt):
+    """The library called directly, batch 3, every buffer longer than include/lspavi.h asks for and prefilled with 0xA5: status is 4
+    words, the index `chunk count` rows, the workspace lspavi_workspace_bytes(3) bytes, the output the fragment's length.  A refused call
+    (the waveform one sample short) leaves all four exactly as they were."""
+    import ctypes
+    from livespeechportraits_amd import _native as N
+    from livespeechportraits_amd.jpeg import JpegEncoder
+    frames_dev, files = _c16_batch(gpu_device)
+    enc = JpegEncoder((16, 16), 3, 75, gpu_device, max_batch=3)
+    lib, c = N.load(), ctypes.c_void_p
+    frame0 = 7 if fmt else 0
+    need = (frame0 + 3) * 16000 // 60
+    wave = wave_of(need + 40)
+    wave_dev = torch.from_numpy(wave).to(gpu_device)
+    want = host_fragment(tmp_path, "c16", files, fmt, wave, frame0)
+    total, nch = len(want[0]), len(want[1])
+    assert nch == (6 if fmt else 3)
+    code = N.AVI_AUDIO_FORMATS[fmt]
+    capacity = int(lib.lspavi_capacity_bytes(len(enc.header), enc.capacity, 3, code, 16000, 60))
+    ws_bytes = int(lib.lspavi_workspace_bytes(3))
+    assert capacity >= total + 16 and ws_bytes > 0
+    header = torch.frombuffer(bytearray(enc.header + b"\0" * (-len(enc.header) % 4)), dtype=torch.uint8).to(gpu_device)
+    status = torch.full((16,), -1515870811, dtype=torch.int32, device=gpu_device)          # 0xA5A5A5A5
+    index = torch.full((2 * 3 + 4, 4), -1515870811, dtype=torch.int32, device=gpu_device)
+    ws = torch.full((ws_bytes + 256,), 0xA5, dtype=torch.uint8, device=gpu_device)
+    out = torch.full((capacity,), 0xA5, dtype=torch.uint8, device=gpu_device)
+    assert enc.enqueue(frames_dev) == 3
+    dst, sizes = enc.slab
+    stream = torch.cuda.current_stream(gpu_device)
+
+    def pack(nwave):
+        rc = lib.lspavi_pack(c(header.data_ptr()), len(enc.header), c(dst.data_ptr()), enc.capacity, c(sizes.data_ptr()), 3,
+                             c(wave_dev.data_ptr() if fmt else None), nwave if fmt else 0, frame0, 16000, 60, code, c(out.data_ptr()), capacity,
+                             c(index.data_ptr()), c(status.data_ptr()), c(ws.data_ptr()), ws_bytes, c(stream.cuda_stream))
+        torch.cuda.synchronize()
+        return rc, [t.cpu().numpy().copy() for t in (status, index, ws, out)]
+
+    if fmt:
+        rc, got = pack(need - 1)
+        assert rc == -1 and "need %d samples, the waveform has %d" % (need, need - 1) in lib.lspavi_last_error().decode()
+        assert all((g.view(np.uint8) == 0xA5).all() for g in got), "a refused call wrote to a device buffer"
+    rc, (st, ix, w, o) = pack(need)
+    assert rc == 0, lib.lspavi_last_error().decode()
+    st, ix = st.view(np.uint32), ix.view(np.uint32)
+    assert st[:4].tolist() == [total, nch, want[4], want[5]]
+    assert (st[4:] == 0xA5A5A5A5).all()
+    assert ix[:nch].tobytes() == want[1].tobytes()
+    assert (ix[nch:] == 0xA5A5A5A5).all()
+    assert (w[ws_bytes:] == 0xA5).all()
+    assert o[:total].tobytes() == want[0]
+    assert (o[total:] == 0xA5).all()
+    enc.close()
 
 
 def _model(tmp_path, case="normal_s64_b3"):
