@@ -12,13 +12,30 @@
  *   tables     Annex K scaled by jpeg_quality_scaling (q < 50 ? 5000 / q : 200 - 2q; (t * s + 50) / 100 clamped to 1..255);
  *   entropy    zigzag order, DC predicted per component over the whole frame (no restart markers), MCU = Y0 Y1 Y2 Y3 Cb Cr (grayscale: one
  *              block), ZRL / EOB with the four standard tables, 0xFF followed by 0x00, the final byte padded with 1-bits, then EOI.
- * Not supported: 4:4:4, progressive, optimised Huffman tables, restart markers, EXIF / ICC.
+ * With options (lspjpeg_create_opts; Pillow's optimize=True, restart_marker_rows / restart_marker_blocks), still byte for byte Pillow's file:
+ *   restart    jchuff.c emit_restart: after every restart_interval MCUs but the last group the bits are padded to a byte with 1-bits (stuffed
+ *              with 0x00 if that makes 0xFF), FF D0+n follows unstuffed (n = 0..7, wrapping), and every component's DC prediction starts
+ *              again at 0; no marker behind the last interval.  jcmarker.c: DRI (FF DD 00 04 hi lo) between the last DHT and SOS.
+ *   optimize   jchuff.c's two passes per frame: the scan's symbols are counted per table id (12 DC categories, 256 AC run / size symbols
+ *              with ZRL and EOB; id 0 for Y, 1 for Cb and Cr; DC differences under the restart rule), and jpeg_gen_optimal_table builds each
+ *              table (csrc/jpegenc_core.h states it).  The frame's bytes are then DHT DC0, AC0 [, DC1, AC1] (a segment each), [DRI,] SOS, the
+ *              scan, EOI, and lspjpeg_header() ends behind SOF0.  A file is header + frame bytes either way.
+ * Not supported: 4:4:4, progressive, EXIF / ICC.
  *
  * Output bound (per frame, what lspjpeg_capacity_bytes() returns): a block codes at most 11 + 11 bits of DC (longest DC code, 11-bit
  * difference) and at most 63 AC symbols of <= 16 + 10 bits (a nonzero coefficient, a ZRL for 16 zeros or one EOB per block: never more
  * symbols than AC positions), so T <= 1660 bits per block; stuffing at most doubles the ceil(T / 8) bytes; + 2 bytes of EOI:
  *     capacity = 2 * ceil(blocks * 1660 / 8) + 2,   blocks = H * W / 64 * (components == 3 ? 1.5 : 1)
  * Nothing the encoder writes can pass it, so there is no overflow path.
+ * A handle made with options restates the bound from its parts (a handle without keeps the value above exactly):
+ *   bits per block  B = 1660 with the Annex K tables; 1665 with optimize, where a DC code can be 16 bits long: 16 + 11 + 63 * (16 + 10);
+ *   stream bytes    every interval is padded to a byte on its own, at most 7 bits each: P <= ceil(blocks * B / 8) + intervals;
+ *   stuffing        at most doubles them (the padded byte of an interval included): 2 * P;
+ *   markers         2 bytes of RSTn behind every interval but the last, 2 bytes of EOI;
+ *   tables          with optimize the frame's own DHT x 4, DRI, SOS: at most 2 * (21 + 12) + 2 * (21 + 162) + 6 + 14 = 452 bytes (a baseline scan
+ *                   has 12 DC categories and 162 AC symbols: run 0..15 x size 1..10, EOB, ZRL);
+ *     capacity = [452 +] 2 * (ceil(blocks * B / 8) + intervals) + 2 * (intervals - 1) + 2,   intervals = ceil(MCUs / restart_interval) or 1
+ * and again nothing the encoder writes can pass it: every term bounds what one owner writes.
  *
  * Conventions: device pointers, nothing allocated by the library, no synchronisation, enqueued on the given hipStream_t in a fixed number of
  * launches (4) whatever the content; returns 0 or a negative code (lspjpeg_last_error()).  create / header / capacity_bytes / workspace_bytes
@@ -50,22 +67,36 @@ typedef struct lspjpeg_handle lspjpeg_handle;
 /* components 3: frames uint8 [H][W][3] RGB (Engine.forward_image), H and W multiples of 16; components 1: uint8 [H][W] (the edge maps of
  * FeatureMapRasteriser.rasterise(as_uint8=True)), multiples of 8.  quality 1..100.  Builds the quantisation tables and the file header. */
 int lspjpeg_create(int width, int height, int components, int quality, lspjpeg_handle **out);
+
+/* The same with options; abi_version = LSPJPEG_ABI_VERSION.  optimize 0 and restart_interval 0 give what lspjpeg_create gives. */
+#define LSPJPEG_ABI_VERSION 1
+typedef struct lspjpeg_options {
+    int32_t abi_version;
+    int32_t width, height, components, quality;
+    int32_t optimize;           /* 0 / 1: per-frame optimal Huffman tables (libjpeg's optimize_coding) */
+    int32_t restart_interval;   /* MCUs per restart interval, 0 = none, at most 65535 */
+} lspjpeg_options;
+int lspjpeg_create_opts(const lspjpeg_options *o, lspjpeg_handle **out);
 int lspjpeg_destroy(lspjpeg_handle *h);
 const char *lspjpeg_last_error(void);
 
-/* the file's bytes from SOI through SOS (APP0 JFIF 1.01, DQT per table, SOF0, DHT per table, SOS): copied to buf when cap is large
- * enough (buf may be NULL to query); returns the length, or a negative code */
+/* the file's bytes from SOI through SOS (APP0 JFIF 1.01, DQT per table, SOF0, DHT per table, [DRI,] SOS; through SOF0 for a handle with
+ * optimize): copied to buf when cap is large enough (buf may be NULL to query); returns the length, or a negative code */
 int64_t lspjpeg_header(const lspjpeg_handle *h, unsigned char *buf, size_t cap);
-/* bytes reserved per frame in dst (the bound above) */
+/* bytes reserved per frame in dst (the bound above, for the handle's options) */
 size_t lspjpeg_capacity_bytes(const lspjpeg_handle *h);
 size_t lspjpeg_workspace_bytes(const lspjpeg_handle *h, int batch);
 
 /* batch frames:  src_dev    uint8 frames, contiguous, [batch][H][W][components]
- *                dst_dev    uint8 [batch][capacity]: frame i's entropy-coded segment + EOI at dst_dev + i * capacity
+ *                dst_dev    uint8 [batch][capacity]: frame i's [DHT .. SOS with optimize,] entropy-coded segment + EOI at dst_dev + i * capacity
  *                sizes_dev  uint32 [batch]: its byte count (the file is header + those bytes)
  *                workspace  lspjpeg_workspace_bytes(h, batch) bytes; its content on entry is irrelevant */
 int lspjpeg_encode(const lspjpeg_handle *h, const unsigned char *src_dev, int batch, unsigned char *dst_dev, uint32_t *sizes_dev,
                    void *workspace_dev, size_t workspace_bytes, void *hip_stream);
+
+/* jpeg_gen_optimal_table on the host, with the code the kernel runs (csrc/jpegenc_core.h): freq[s] occurrences of symbol s -> bits[1..16]
+ * codes per length (bits[0] = 0), the symbols in code order, and their number.  For the tests. */
+int lspjpeg_host_optimal_table(const uint32_t freq[256], unsigned char bits[17], unsigned char huffval[256], int *nsymbols);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

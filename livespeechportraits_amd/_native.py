@@ -296,9 +296,18 @@ UNET_SIGNATURES = {
     "lspunet_launch_info": (c_int, [c_void_p, c_int, c_int, POINTER(c_char_p), POINTER(c_char_p), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
 }
 
+class JpegEncOptions(ctypes.Structure):
+    """lspjpeg_options"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("abi_version", "width", "height", "components", "quality", "optimize", "restart_interval")]
+
+
+JPEG_ABI_VERSION = 1
+
 # every symbol include/lspjpeg.h declares
 JPEG_SIGNATURES = {
     "lspjpeg_create": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "lspjpeg_create_opts": (c_int, [POINTER(JpegEncOptions), POINTER(c_void_p)]),
+    "lspjpeg_host_optimal_table": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
     "lspjpeg_destroy": (c_int, [c_void_p]),
     "lspjpeg_last_error": (c_char_p, []),
     "lspjpeg_header": (c_int64, [c_void_p, c_void_p, c_size_t]),

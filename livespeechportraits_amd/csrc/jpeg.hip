@@ -11,12 +11,21 @@
 //   4. jpeg_stuff      workgroup per frame: bytes of the stream, the last one padded with 1-bits, 0x00 after every 0xFF (count per
 //                      16-byte chunk, scan, scatter), EOI, and the byte count.
 // No host round trip: the variable sizes travel between the launches in the workspace.
+//
+// A handle with options (lspjpeg_create_opts: optimised Huffman tables, restart intervals) runs instances of its own, four launches as well:
+// jpeg_transform<true> (no AC bit counts: the tables are not known yet), jpeg_tables in place of jpeg_offsets (histograms, the tables of
+// jpegenc_core.h, the frame's DHT .. SOS, bit offsets per block and byte offsets per interval), jpeg_emit<true> (codes from the workspace, every
+// interval padded on its own), jpeg_stuff<true> (RSTn behind every interval but the last).  The options are template parameters: the
+// instances of a plain handle hold none of that code.
 #include "../../include/lspjpeg.h"
 
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
+
+#include "jpegenc_core.h"
 
 namespace lspjpeg {
 
@@ -90,6 +99,16 @@ struct Params {
     unsigned long long cap;
     unsigned short div[2][64];              // qtable << 3, natural order: luma, chroma
 };
+
+// a handle with options (optimised tables, restart intervals) runs instances of its own: the instances of a plain handle see none of this
+struct OptParams : Params {
+    unsigned *codes;                        // [batch][4][256] (length << 16) | code per symbol: DC0 AC0 DC1 AC1 of the frame
+    unsigned *istart;                       // [batch][nint + 1] first byte of every interval in the unstuffed stream; [nint] = all bytes
+    unsigned *prelen;                       // [batch] bytes of the frame's DHT .. SOS in dst (0 without optimize: they are in the header)
+    int restart, nint, ibl, bpm, optimize;  // MCUs per interval (0: none), intervals per frame, blocks per interval and per MCU
+};
+template <bool kOpts>
+using ParamsOf = std::conditional_t<kOpts, OptParams, Params>;
 
 // ---- device helpers ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int nbits(int v)
@@ -178,7 +197,8 @@ __device__ __forceinline__ unsigned block_scan(unsigned v, unsigned *lds, unsign
 }
 
 // ---- 1. transform + quantise + AC bits ----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NT) void jpeg_transform(Params p)
+template <bool kOpts>
+__global__ __launch_bounds__(NT) void jpeg_transform(ParamsOf<kOpts> p)
 {
     const int f = blockIdx.y;
     const int t = blockIdx.x * NT + threadIdx.x;
@@ -267,26 +287,28 @@ __global__ __launch_bounds__(NT) void jpeg_transform(Params p)
         out[k] = make_uint4((zz[0] & 0xffff) | ((unsigned)zz[1] << 16), (zz[2] & 0xffff) | ((unsigned)zz[3] << 16),
                             (zz[4] & 0xffff) | ((unsigned)zz[5] << 16), (zz[6] & 0xffff) | ((unsigned)zz[7] << 16));
     }
-    const Codes &ac = kCodes[2 * tab + 1];
-    const unsigned zrl = ac.v[0xf0] >> 16, eob = ac.v[0x00] >> 16;
-    unsigned bits = 0;
-    int run = 0;
+    if constexpr (!kOpts) {                 // (with options the tables, or the interval the block is in, are not known yet: jpeg_tables)
+        const Codes &ac = kCodes[2 * tab + 1];
+        const unsigned zrl = ac.v[0xf0] >> 16, eob = ac.v[0x00] >> 16;
+        unsigned bits = 0;
+        int run = 0;
 #pragma unroll
-    for (int k = 1; k < 64; ++k) {
-        if (z[k] == 0) {
-            ++run;
-        } else {
-            while (run > 15) {
-                bits += zrl;
-                run -= 16;
+        for (int k = 1; k < 64; ++k) {
+            if (z[k] == 0) {
+                ++run;
+            } else {
+                while (run > 15) {
+                    bits += zrl;
+                    run -= 16;
+                }
+                const int nb = nbits(z[k]);
+                bits += (ac.v[(run << 4) | nb] >> 16) + nb;
+                run = 0;
             }
-            const int nb = nbits(z[k]);
-            bits += (ac.v[(run << 4) | nb] >> 16) + nb;
-            run = 0;
         }
+        if (run) bits += eob;
+        p.acbits[(size_t)f * p.nblk + g] = bits;
     }
-    if (run) bits += eob;
-    p.acbits[(size_t)f * p.nblk + g] = bits;
 }
 
 __device__ __forceinline__ int dc_diff(const Params &p, int f, int g)
@@ -320,6 +342,175 @@ __global__ __launch_bounds__(NS) void jpeg_offsets(Params p)
     for (unsigned i = threadIdx.x; i < nw; i += NS) w[i] = 0u;
 }
 
+// ---- 2'. with options: histograms, tables, DHT .. SOS, bit offsets per block, byte offsets per interval ------------------------------
+__device__ __forceinline__ int dc_diff_opts(const OptParams &p, int f, int g)              // the prediction starts again in every interval
+{
+    const short *c = p.coef + (size_t)f * p.nblk * 64;
+    const int pg = lspenc::pred_block(g, p.ibl, p.bpm);
+    return (int)c[(size_t)g * 64] - (pg >= 0 ? (int)c[(size_t)pg * 64] : 0);
+}
+
+// fn(symbol) for every AC symbol of a block, in scan order: (run << 4) | size, 0xF0 (ZRL), 0x00 (EOB); jchuff.c encode_one_block / htest_one_block
+template <class F>
+__device__ __forceinline__ void for_ac_symbols(const uint4 *in, F &&fn)
+{
+    int run = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const uint4 v4 = in[q];
+        const unsigned wv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if (q == 0 && e == 0) continue;                     // DC
+            const int v = (int)(short)(wv[e >> 1] >> ((e & 1) * 16));
+            if (v == 0) {
+                ++run;
+                continue;
+            }
+            while (run > 15) {
+                fn(0xf0);
+                run -= 16;
+            }
+            fn((run << 4) | nbits(v));
+            run = 0;
+        }
+    }
+    if (run) fn(0);
+}
+
+// the minimum of a 64-bit key over the wave, in every lane
+struct WaveMin {
+    __device__ __forceinline__ uint64_t operator()(uint64_t k) const
+    {
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint64_t y = (uint64_t)__shfl_xor((unsigned long long)k, o, 64);
+            k = y < k ? y : k;
+        }
+        return k;
+    }
+};
+
+// Workgroup per frame.  With optimize: (a) the symbol counts of the scan per table in LDS (a thread keeps its EOB count to itself until the end:
+// nearly every block has one); (b) one wave per table merges (jpegenc_core.h huff_merge), one lane per table lists the symbols and assigns
+// the codes; (c) all threads write DHT per table, DRI, SOS at the start of the frame's bytes.  Without: the Annex K codes.  Then, as jpeg_offsets,
+// (d) the bits of every block and their exclusive scan S, (e) per interval ceil((S[end] - S[begin]) / 8) bytes and their scan, and the zeroed
+// stream words.  jpeg_emit puts block g of interval i at bit 8 * istart[i] + S[g] - S[begin of i].
+__global__ __launch_bounds__(NS) void jpeg_tables(OptParams p)
+{
+    __shared__ unsigned lds[NS / 64 + 1];
+    __shared__ unsigned codes[4][256];
+    __shared__ unsigned hist[4][256];
+    __shared__ uint16_t csize[4][lspenc::kSymbols + 3];
+    __shared__ unsigned char tbits[4][20], tvals[4][256];
+    __shared__ int tn[4];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const int ntab = p.comps == 3 ? 4 : 2;
+    const short *coef = p.coef + (size_t)f * p.nblk * 64;
+    unsigned char *dst = p.dst + (size_t)f * p.cap;
+    if (p.optimize) {
+        for (int i = tid; i < 4 * 256; i += NS) hist[i >> 8][i & 255] = 0u;
+        __syncthreads();
+        unsigned eob[2] = {0u, 0u};
+        for (int g = tid; g < p.nblk; g += NS) {
+            const int tab = table_of(g, p.comps);
+            atomicAdd(&hist[2 * tab][nbits(dc_diff_opts(p, f, g))], 1u);
+            unsigned *h = hist[2 * tab + 1];
+            unsigned e = 0;
+            for_ac_symbols(reinterpret_cast<const uint4 *>(coef + (size_t)g * 64), [&](int s) {
+                if (s)
+                    atomicAdd(h + s, 1u);
+                else
+                    ++e;
+            });
+            eob[tab] += e;
+        }
+        if (eob[0]) atomicAdd(&hist[1][0], eob[0]);
+        if (eob[1]) atomicAdd(&hist[3][0], eob[1]);
+        __syncthreads();
+        if ((tid >> 6) < ntab) lspenc::huff_merge<64>(hist[tid >> 6], tid & 63, csize[tid >> 6], WaveMin());
+        __syncthreads();
+        if (tid < ntab) {
+            tn[tid] = lspenc::huff_finish(csize[tid], tbits[tid], tvals[tid]);
+            lspenc::huff_codes(tbits[tid], tvals[tid], codes[tid]);
+        }
+        __syncthreads();
+        int at = 0;
+        for (int t = 0; t < ntab; ++t) {                        // jcmarker.c emit_dht: DC0, AC0, DC1, AC1, a segment each
+            const int n = tn[t];
+            for (int i = tid; i < 21 + n; i += NS) {
+                const int len = 19 + n;
+                dst[at + i] = i == 0 ? 0xff : i == 1 ? 0xc4 : i == 2 ? (unsigned char)(len >> 8) : i == 3 ? (unsigned char)len
+                            : i == 4 ? (unsigned char)(((t & 1) << 4) | (t >> 1)) : i < 21 ? tbits[t][i - 4] : tvals[t][i - 21];
+            }
+            at += 21 + n;
+        }
+        if (tid == 0) {
+            unsigned char *o = dst + at;
+            if (p.restart > 0) {
+                const unsigned char dri[6] = {0xff, 0xdd, 0, 4, (unsigned char)(p.restart >> 8), (unsigned char)p.restart};
+                for (int i = 0; i < 6; ++i) *o++ = dri[i];
+            }
+            *o++ = 0xff;
+            *o++ = 0xda;
+            *o++ = 0;
+            *o++ = (unsigned char)(6 + 2 * p.comps);
+            *o++ = (unsigned char)p.comps;
+            for (int c = 0; c < p.comps; ++c) {
+                *o++ = (unsigned char)(c + 1);
+                *o++ = c == 0 ? 0x00 : 0x11;
+            }
+            *o++ = 0;
+            *o++ = 63;
+            *o++ = 0;
+            p.prelen[f] = (unsigned)(o - dst);
+        }
+    } else {
+        for (int i = tid; i < ntab * 256; i += NS) codes[i >> 8][i & 255] = kCodes[i >> 8].v[i & 255];
+        if (tid == 0) p.prelen[f] = 0u;
+        __syncthreads();
+    }
+    for (int i = tid; i < ntab * 256; i += NS) p.codes[(size_t)f * 1024 + i] = codes[i >> 8][i & 255];
+    // (d)
+    unsigned *S = p.offsets + (size_t)f * p.nblk;
+    unsigned carry = 0;
+    for (int base = 0; base < p.nblk; base += NS) {
+        const int g = base + tid;
+        unsigned b = 0;
+        if (g < p.nblk) {
+            const int tab = table_of(g, p.comps);
+            const int nb = nbits(dc_diff_opts(p, f, g));
+            b = (codes[2 * tab][nb] >> 16) + nb;
+            const unsigned *ac = codes[2 * tab + 1];
+            for_ac_symbols(reinterpret_cast<const uint4 *>(coef + (size_t)g * 64), [&](int s) { b += (ac[s] >> 16) + (s & 15); });
+        }
+        unsigned tot;
+        const unsigned ex = block_scan(b, lds, &tot);
+        if (g < p.nblk) S[g] = carry + ex;
+        carry += tot;
+    }
+    __syncthreads();                                            // S is read across the workgroup below
+    // (e)
+    unsigned *ist = p.istart + (size_t)f * (p.nint + 1);
+    unsigned bytes = 0;
+    for (int base = 0; base < p.nint; base += NS) {
+        const int i = base + tid;
+        unsigned b = 0;
+        if (i < p.nint) {
+            const int e = lspenc::interval_end(i, p.ibl, p.nblk);
+            b = lspenc::padded_bytes((e == p.nblk ? carry : S[e]) - S[(size_t)i * p.ibl]);
+        }
+        unsigned tot;
+        const unsigned ex = block_scan(b, lds, &tot);
+        if (i < p.nint) ist[i] = bytes + ex;
+        bytes += tot;
+    }
+    if (tid == 0) ist[p.nint] = bytes;
+    unsigned *w = p.words + (size_t)f * p.wcap;
+    const unsigned nw = (bytes + 3) / 4;
+    for (unsigned i = tid; i < nw; i += NS) w[i] = 0u;
+}
+
 // ---- 3. the symbols of every block at its offset ---------------------------------------------------------------------------------
 struct BitWriter {
     unsigned *w;
@@ -344,20 +535,34 @@ struct BitWriter {
 
 __device__ __forceinline__ unsigned value_bits(int v, int nb) { return (unsigned)(v < 0 ? v - 1 : v) & ((1u << nb) - 1u); }
 
-__global__ __launch_bounds__(NT) void jpeg_emit(Params p)
+template <bool kOpts>
+__global__ __launch_bounds__(NT) void jpeg_emit(ParamsOf<kOpts> p)
 {
     const int f = blockIdx.y;
     const int g = blockIdx.x * NT + threadIdx.x;
     if (g >= p.nblk) return;
     const int tab = table_of(g, p.comps);
-    const unsigned off = p.offsets[(size_t)f * p.nblk + g];
+    unsigned off;
+    int diff;
+    const unsigned *dc, *acv;
+    if constexpr (kOpts) {
+        const unsigned *S = p.offsets + (size_t)f * p.nblk;
+        const int i = lspenc::interval_of(g, p.ibl);
+        off = 8u * p.istart[(size_t)f * (p.nint + 1) + i] + S[g] - S[(size_t)i * p.ibl];
+        diff = dc_diff_opts(p, f, g);
+        dc = p.codes + (size_t)f * 1024 + 2 * tab * 256;
+        acv = dc + 256;
+    } else {
+        off = p.offsets[(size_t)f * p.nblk + g];
+        diff = dc_diff(p, f, g);
+        dc = kCodes[2 * tab].v;
+        acv = kCodes[2 * tab + 1].v;
+    }
     BitWriter bw{p.words + (size_t)f * p.wcap, off >> 5, (int)(off & 31), 0ull};
-    const int diff = dc_diff(p, f, g);
     int nb = nbits(diff);
-    unsigned c = kCodes[2 * tab].v[nb];
+    unsigned c = dc[nb];
     bw.put(((c & 0xffffu) << nb) | value_bits(diff, nb), (int)(c >> 16) + nb);
     const uint4 *in = reinterpret_cast<const uint4 *>(p.coef + ((size_t)f * p.nblk + g) * 64);
-    const Codes &ac = kCodes[2 * tab + 1];
     int run = 0;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
@@ -372,34 +577,51 @@ __global__ __launch_bounds__(NT) void jpeg_emit(Params p)
                 continue;
             }
             while (run > 15) {
-                const unsigned z = ac.v[0xf0];
+                const unsigned z = acv[0xf0];
                 bw.put(z & 0xffffu, (int)(z >> 16));
                 run -= 16;
             }
             nb = nbits(v);
-            c = ac.v[(run << 4) | nb];
+            c = acv[(run << 4) | nb];
             bw.put(((c & 0xffffu) << nb) | value_bits(v, nb), (int)(c >> 16) + nb);
             run = 0;
         }
     }
     if (run) {
-        c = ac.v[0x00];
+        c = acv[0x00];
         bw.put(c & 0xffffu, (int)(c >> 16));
+    }
+    if constexpr (kOpts) {                                      // jchuff.c flush_bits: the interval's last byte is filled with 1-bits here
+        if (g + 1 == lspenc::interval_end(lspenc::interval_of(g, p.ibl), p.ibl, p.nblk)) {
+            const unsigned pad = lspenc::pad_bits((unsigned)bw.n);
+            if (pad) bw.put((1u << pad) - 1u, (int)pad);
+        }
     }
     bw.flush();
 }
 
 // ---- 4. bytes, padding, stuffing, EOI ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NS) void jpeg_stuff(Params p)
+// With options the stream arrives padded per interval (jpeg_emit), starts behind the frame's DHT .. SOS, and RSTn follows the last byte of every
+// interval but the last, behind that byte's own stuffing (jchuff.c emit_restart).
+template <bool kOpts>
+__global__ __launch_bounds__(NS) void jpeg_stuff(ParamsOf<kOpts> p)
 {
     __shared__ unsigned lds[NS / 64 + 1];
     const int f = blockIdx.x;
-    const unsigned total = p.totals[f];
-    const int nbytes = (int)((total + 7) / 8);
-    const unsigned pad = (8u - (total & 7u)) & 7u;              // 1-bits that fill the last byte
+    int nbytes;
+    unsigned pad = 0, carry = 0;                                // pad: 1-bits that fill the last byte
+    const unsigned *ist = nullptr;
+    if constexpr (kOpts) {
+        ist = p.istart + (size_t)f * (p.nint + 1);
+        nbytes = (int)ist[p.nint];
+        carry = p.prelen[f];
+    } else {
+        const unsigned total = p.totals[f];
+        nbytes = (int)((total + 7) / 8);
+        pad = (8u - (total & 7u)) & 7u;
+    }
     const unsigned *w = p.words + (size_t)f * p.wcap;
     unsigned char *dst = p.dst + (size_t)f * p.cap;
-    unsigned carry = 0;
     for (int base = 0; base < nbytes; base += NS * 16) {
         const int i0 = base + threadIdx.x * 16;
         const int valid = min(max(nbytes - i0, 0), 16);
@@ -413,13 +635,37 @@ __global__ __launch_bounds__(NS) void jpeg_stuff(Params p)
         }
         unsigned char b[16];
         unsigned cnt = 0;
+        unsigned ends = 0;                                      // bit k: byte k of the chunk is the last of an interval that a marker follows
+        int iv = 0;                                             // the interval of the chunk's first byte
+        if constexpr (kOpts) {
+            if (valid > 0 && p.nint > 1) {
+                int lo = 0, hi = p.nint - 1;                    // the first interval that ends behind byte i0 (no interval is empty)
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (ist[mid + 1] > (unsigned)i0)
+                        hi = mid;
+                    else
+                        lo = mid + 1;
+                }
+                iv = lo;
+                int kk = iv;
+                for (int k = 0; k < valid && kk < p.nint - 1; ++k) {
+                    if (ist[kk + 1] == (unsigned)(i0 + k + 1)) {
+                        ends |= 1u << k;
+                        ++kk;
+                    }
+                }
+            }
+        }
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             unsigned x = (wv[k >> 2] >> (24 - 8 * (k & 3))) & 0xffu;             // the stream is MSB first within each word
-            if (i0 + k == nbytes - 1) x |= (1u << pad) - 1u;
+            if constexpr (!kOpts)
+                if (i0 + k == nbytes - 1) x |= (1u << pad) - 1u;
             b[k] = (unsigned char)x;
             cnt += k < valid ? 1u + (x == 0xffu) : 0u;
         }
+        if constexpr (kOpts) cnt += 2u * (unsigned)__popc(ends);
         unsigned tot;
         const unsigned ex = block_scan(cnt, lds, &tot);
         unsigned char *o = dst + carry + ex;
@@ -428,6 +674,12 @@ __global__ __launch_bounds__(NS) void jpeg_stuff(Params p)
             if (k < valid) {
                 *o++ = b[k];
                 if (b[k] == 0xffu) *o++ = 0;
+                if constexpr (kOpts) {
+                    if ((ends >> k) & 1u) {
+                        *o++ = 0xff;
+                        *o++ = lspenc::rst_marker((unsigned)iv++);
+                    }
+                }
             }
         }
         carry += tot;
@@ -459,6 +711,8 @@ struct lspjpeg_handle {
     size_t cap;
     unsigned short div[2][64];
     std::vector<unsigned char> header;
+    bool opts;                              // made with optimize or a restart interval: the *<true> instances and jpeg_tables
+    int optimize, restart, nint, ibl, bpm;
 };
 
 namespace {
@@ -469,7 +723,8 @@ void put16(std::vector<unsigned char> &v, int x)
     v.push_back((unsigned char)x);
 }
 
-// SOI .. SOS as libjpeg writes them (jcmarker.c): APP0 JFIF 1.01 (units 0, density 1x1), one DQT per table, SOF0, DHT DC0 AC0 [DC1 AC1], SOS
+// SOI .. SOS as libjpeg writes them (jcmarker.c): APP0 JFIF 1.01 (units 0, density 1x1), one DQT per table, SOF0, DHT DC0 AC0 [DC1 AC1], [DRI], SOS;
+// SOI .. SOF0 for a handle with optimize
 void build_header(lspjpeg_handle *h, const unsigned char (&q)[2][64])
 {
     std::vector<unsigned char> &v = h->header;
@@ -495,6 +750,7 @@ void build_header(lspjpeg_handle *h, const unsigned char (&q)[2][64])
         v.push_back(c == 0 && h->comps == 3 ? 0x22 : 0x11);
         v.push_back(c == 0 ? 0 : 1);
     }
+    if (h->optimize) return;                // DHT, DRI and SOS are the frame's own
     const unsigned char *vals[4] = {kDcVals, kAcLumaVals, kDcVals, kAcChromaVals};
     for (int t = 0; t < 2 * ntab; ++t) {
         int n = 0;
@@ -505,6 +761,12 @@ void build_header(lspjpeg_handle *h, const unsigned char (&q)[2][64])
         v.push_back((unsigned char)(((t & 1) << 4) | (t >> 1)));
         v.insert(v.end(), kBits[t], kBits[t] + 16);
         v.insert(v.end(), vals[t], vals[t] + n);
+    }
+    if (h->restart > 0) {                   // jcmarker.c write_scan_header: DRI between the tables and SOS
+        v.push_back(0xff);
+        v.push_back(0xdd);
+        put16(v, 4);
+        put16(v, h->restart);
     }
     v.push_back(0xff);
     v.push_back(0xda);
@@ -525,10 +787,8 @@ extern "C" {
 
 const char *lspjpeg_last_error(void) { return g_err.c_str(); }
 
-int lspjpeg_create(int width, int height, int components, int quality, lspjpeg_handle **out)
+static int create(int width, int height, int components, int quality, int optimize, int restart, lspjpeg_handle **out)
 {
-    if (!out) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "null out");
-    *out = nullptr;
     if (components != 1 && components != 3) return fail(LSPJPEG_ERR_UNSUPPORTED, "components must be 3 (RGB, 4:2:0) or 1 (grayscale)");
     if (quality < 1 || quality > 100) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "quality must be in 1..100");
     const int m = components == 3 ? 16 : 8;
@@ -543,9 +803,21 @@ int lspjpeg_create(int width, int height, int components, int quality, lspjpeg_h
     h->mcux = width / m;
     h->nmcu = h->mcux * (height / m);
     h->nblk = h->nmcu * (components == 3 ? 6 : 1);
-    const size_t bits = (size_t)h->nblk * LSPJPEG_BLOCK_BITS;
-    h->wcap = (int)(((bits + 31) / 32 + 1 + 3) & ~(size_t)3);
-    h->cap = 2 * ((bits + 7) / 8) + 2;
+    h->optimize = optimize;
+    h->restart = restart;
+    h->opts = optimize || restart > 0;
+    h->bpm = components == 3 ? 6 : 1;
+    h->nint = lspenc::interval_count(h->nmcu, restart);
+    h->ibl = lspenc::interval_blocks(h->nmcu, restart, h->bpm);
+    if (h->opts) {
+        const size_t bytes = (size_t)lspenc::stream_bytes_bound((uint64_t)h->nblk, (uint64_t)h->nint, optimize ? lspenc::kBlockBitsOpt : lspenc::kBlockBitsStd);
+        h->wcap = (int)(((bytes + 3) / 4 + 1 + 3) & ~(size_t)3);
+        h->cap = (size_t)lspenc::capacity_bound((uint64_t)h->nblk, (uint64_t)h->nint, optimize);
+    } else {
+        const size_t bits = (size_t)h->nblk * LSPJPEG_BLOCK_BITS;
+        h->wcap = (int)(((bits + 31) / 32 + 1 + 3) & ~(size_t)3);
+        h->cap = 2 * ((bits + 7) / 8) + 2;
+    }
     // jcparam.c jpeg_quality_scaling + jpeg_add_quant_table(force_baseline = TRUE)
     const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
     unsigned char q[2][64];
@@ -560,6 +832,34 @@ int lspjpeg_create(int width, int height, int components, int quality, lspjpeg_h
     }
     build_header(h, q);
     *out = h;
+    return LSPJPEG_OK;
+}
+
+int lspjpeg_create(int width, int height, int components, int quality, lspjpeg_handle **out)
+{
+    if (!out) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    return create(width, height, components, quality, 0, 0, out);
+}
+
+int lspjpeg_create_opts(const lspjpeg_options *o, lspjpeg_handle **out)
+{
+    if (!out) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    if (!o) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "null options");
+    if (o->abi_version != LSPJPEG_ABI_VERSION)
+        return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "lspjpeg_options.abi_version is " + std::to_string(o->abi_version) + ", this library speaks " + std::to_string(LSPJPEG_ABI_VERSION));
+    if (o->optimize != 0 && o->optimize != 1) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "optimize must be 0 or 1");
+    if (o->restart_interval < 0 || o->restart_interval > 65535) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "restart_interval must be in 0..65535 MCUs");
+    return create(o->width, o->height, o->components, o->quality, o->optimize, o->restart_interval, out);
+}
+
+int lspjpeg_host_optimal_table(const uint32_t freq[256], unsigned char bits[17], unsigned char huffval[256], int *nsymbols)
+{
+    if (!freq || !bits || !huffval || !nsymbols) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "null argument");
+    uint16_t codesize[lspenc::kSymbols];
+    lspenc::huff_merge<1>(freq, 0, codesize, lspenc::OneLane());
+    *nsymbols = lspenc::huff_finish(codesize, bits, huffval);
     return LSPJPEG_OK;
 }
 
@@ -581,7 +881,7 @@ int64_t lspjpeg_header(const lspjpeg_handle *h, unsigned char *buf, size_t cap)
 
 size_t lspjpeg_capacity_bytes(const lspjpeg_handle *h) { return h ? h->cap : 0; }
 
-static size_t workspace_layout(const lspjpeg_handle *h, int batch, size_t off[5])
+static size_t workspace_layout(const lspjpeg_handle *h, int batch, size_t off[8])
 {
     const size_t nb = (size_t)batch * h->nblk;
     size_t o = 0;
@@ -590,13 +890,18 @@ static size_t workspace_layout(const lspjpeg_handle *h, int batch, size_t off[5]
     off[2] = o; o = align256(o + nb * sizeof(unsigned));
     off[3] = o; o = align256(o + (size_t)batch * sizeof(unsigned));
     off[4] = o; o = align256(o + (size_t)batch * h->wcap * sizeof(unsigned));
+    if (h->opts) {
+        off[5] = o; o = align256(o + (size_t)batch * 1024 * sizeof(unsigned));
+        off[6] = o; o = align256(o + (size_t)batch * (h->nint + 1) * sizeof(unsigned));
+        off[7] = o; o = align256(o + (size_t)batch * sizeof(unsigned));
+    }
     return o;
 }
 
 size_t lspjpeg_workspace_bytes(const lspjpeg_handle *h, int batch)
 {
     if (!h || batch < 1) return 0;
-    size_t off[5];
+    size_t off[8];
     return workspace_layout(h, batch, off);
 }
 
@@ -607,11 +912,11 @@ int lspjpeg_encode(const lspjpeg_handle *h, const unsigned char *src_dev, int ba
     if (batch < 1 || batch > 65535) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "batch must be in 1..65535");
     if (reinterpret_cast<uintptr_t>(src_dev) % 16 || reinterpret_cast<uintptr_t>(workspace_dev) % 256)
         return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "src_dev must be 16-byte aligned and workspace_dev 256-byte aligned");
-    size_t off[5];
+    size_t off[8];
     const size_t need = workspace_layout(h, batch, off);
     if (workspace_bytes < need) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "workspace needs " + std::to_string(need) + " bytes");
     char *ws = static_cast<char *>(workspace_dev);
-    Params p{};
+    OptParams p{};
     p.src = src_dev;
     p.coef = reinterpret_cast<short *>(ws + off[0]);
     p.acbits = reinterpret_cast<unsigned *>(ws + off[1]);
@@ -632,10 +937,26 @@ int lspjpeg_encode(const lspjpeg_handle *h, const unsigned char *src_dev, int ba
         for (int k = 0; k < 64; ++k) p.div[t][k] = h->div[t][k];
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const dim3 per_block((h->nblk + NT - 1) / NT, batch);
-    hipLaunchKernelGGL(jpeg_transform, per_block, dim3(NT), 0, st, p);
-    hipLaunchKernelGGL(jpeg_offsets, dim3(batch), dim3(NS), 0, st, p);
-    hipLaunchKernelGGL(jpeg_emit, per_block, dim3(NT), 0, st, p);
-    hipLaunchKernelGGL(jpeg_stuff, dim3(batch), dim3(NS), 0, st, p);
+    if (h->opts) {
+        p.codes = reinterpret_cast<unsigned *>(ws + off[5]);
+        p.istart = reinterpret_cast<unsigned *>(ws + off[6]);
+        p.prelen = reinterpret_cast<unsigned *>(ws + off[7]);
+        p.restart = h->restart;
+        p.nint = h->nint;
+        p.ibl = h->ibl;
+        p.bpm = h->bpm;
+        p.optimize = h->optimize;
+        hipLaunchKernelGGL(jpeg_transform<true>, per_block, dim3(NT), 0, st, p);
+        hipLaunchKernelGGL(jpeg_tables, dim3(batch), dim3(NS), 0, st, p);
+        hipLaunchKernelGGL(jpeg_emit<true>, per_block, dim3(NT), 0, st, p);
+        hipLaunchKernelGGL(jpeg_stuff<true>, dim3(batch), dim3(NS), 0, st, p);
+    } else {
+        const Params &q = p;
+        hipLaunchKernelGGL(jpeg_transform<false>, per_block, dim3(NT), 0, st, q);
+        hipLaunchKernelGGL(jpeg_offsets, dim3(batch), dim3(NS), 0, st, q);
+        hipLaunchKernelGGL(jpeg_emit<false>, per_block, dim3(NT), 0, st, q);
+        hipLaunchKernelGGL(jpeg_stuff<false>, dim3(batch), dim3(NS), 0, st, q);
+    }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(LSPJPEG_ERR_HIP, std::string("jpeg launch: ") + hipGetErrorString(e));
     return LSPJPEG_OK;

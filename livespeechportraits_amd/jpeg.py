@@ -6,6 +6,10 @@ files as ``bytes``: for the same pixels they are the bytes Pillow writes with it
 standard Huffman tables, JFIF header).  Only the compressed bytes cross PCIe: the per-frame sizes are copied first, then
 each frame's bytes.  There is no CPU path.
 
+``JpegOptions`` carries Pillow's other two baseline switches, byte for byte Pillow's as well: ``optimize`` (per-frame optimal Huffman
+tables, about a tenth fewer bytes) and ``restart_rows`` / ``restart_blocks`` (restart intervals, which ``JpegDecoder`` decodes in
+parallel).  No default uses them.
+
 The way back is ``JpegDecoder`` (include/lspjpegdec.h): baseline files -- the candidate images of demo.py:88-95, the frames of an
 ``AviWriter`` recording, anything Pillow writes by default -- decoded on the device to the pixels Pillow returns, bit for bit.  The
 host does the marker parsing and the batch layout (``DecodePlan``, no device needed); the compressed bytes cross PCIe once, in one
@@ -33,11 +37,53 @@ def _header_of(lib, h) -> bytes:
     return bytes(buf)
 
 
-def file_header(width: int, height: int, channels: int = 3, quality: int = 75) -> bytes:
-    """The bytes every file of that geometry and quality starts with (SOI .. SOS), built on the host: no device needed."""
-    lib = N.load()
+class JpegOptions(NamedTuple):
+    """What Pillow's ``Image.save(f, "JPEG", quality=, optimize=, restart_marker_rows=, restart_marker_blocks=)`` takes, as one value:
+    accepted wherever a JPEG quality is (``render_frames(jpeg_quality=)``, ``LivePortraitPool.tick(jpeg_quality=)``, ``record_quality=``,
+    ``VideoSink``).  ``optimize``: per-frame optimal Huffman tables; ``restart_rows`` MCU rows or ``restart_blocks`` MCUs per restart
+    interval (not both; 0 = none)."""
+    quality: int = 75
+    optimize: bool = False
+    restart_rows: int = 0
+    restart_blocks: int = 0
+
+    @classmethod
+    def of(cls, value) -> "JpegOptions":
+        """an int (a quality, today's form) or a JpegOptions -> JpegOptions with plain types; the restart keywords are checked here, the
+        quality where it always was (lspjpeg_create: LspjpegError; the pools: ValueError)"""
+        o = value if isinstance(value, cls) else cls(quality=value)
+        o = cls(int(o.quality), bool(o.optimize), int(o.restart_rows), int(o.restart_blocks))
+        if o.restart_rows < 0 or o.restart_blocks < 0:
+            raise ValueError("restart_rows and restart_blocks must be >= 0")
+        if o.restart_rows and o.restart_blocks:
+            raise ValueError("give restart_rows or restart_blocks, not both")
+        return o
+
+    def restart_interval(self, width: int, channels: int) -> int:
+        """MCUs per restart interval: jcmaster.c jinit_c_master_control's rows * MCUs per row capped at 65535; blocks as given"""
+        if self.restart_rows:
+            return min(self.restart_rows * (int(width) // (16 if channels == 3 else 8)), 65535)
+        return self.restart_blocks
+
+
+def _create(lib, width: int, height: int, channels: int, o: JpegOptions) -> ctypes.c_void_p:
+    """lspjpeg_create for plain options (the same handle, the parent's kernels), lspjpeg_create_opts otherwise"""
     h = ctypes.c_void_p()
-    N.check_jpeg(lib.lspjpeg_create(int(width), int(height), int(channels), int(quality), ctypes.byref(h)))
+    if not o.optimize and not o.restart_rows and not o.restart_blocks:
+        N.check_jpeg(lib.lspjpeg_create(int(width), int(height), int(channels), o.quality, ctypes.byref(h)))
+    else:
+        c = N.JpegEncOptions(N.JPEG_ABI_VERSION, int(width), int(height), int(channels), o.quality, int(o.optimize), o.restart_interval(width, channels))
+        N.check_jpeg(lib.lspjpeg_create_opts(ctypes.byref(c), ctypes.byref(h)))
+    return h
+
+
+def file_header(width: int, height: int, channels: int = 3, quality: Union[int, JpegOptions] = 75, optimize: bool = False, restart_rows: int = 0,
+                restart_blocks: int = 0) -> bytes:
+    """The bytes every file of that geometry and those options starts with, built on the host: no device needed.  SOI .. SOS; with
+    ``optimize`` SOI .. SOF0 (the tables, DRI and SOS are then each frame's own)."""
+    lib = N.load()
+    o = quality if isinstance(quality, JpegOptions) else JpegOptions(quality, optimize, restart_rows, restart_blocks)
+    h = _create(lib, width, height, channels, JpegOptions.of(o))
     try:
         return _header_of(lib, h)
     finally:
@@ -48,19 +94,26 @@ class JpegEncoder:
     """Baseline JPEG of ``[B, H, W, 3]`` uint8 RGB frames (``Engine.forward_image``; H, W multiples of 16) or ``[B, H, W]``
     uint8 grayscale frames (``FeatureMapRasteriser.rasterise(..., as_uint8=True)``; multiples of 8), B <= ``max_batch``.
     ``size`` is the side of square frames or (H, W).  The device buffers (output at the documented worst-case bound per
-    frame, sizes, workspace) are allocated once, here."""
+    frame, sizes, workspace) are allocated once, here.  ``quality`` may be a ``JpegOptions``; ``optimize`` / ``restart_rows`` /
+    ``restart_blocks`` are Pillow's ``optimize`` / ``restart_marker_rows`` / ``restart_marker_blocks``, and the files Pillow's with them."""
 
-    def __init__(self, size: Union[int, Sequence[int]], channels: int = 3, quality: int = 75, device="cuda:0", max_batch: int = 8):
+    def __init__(self, size: Union[int, Sequence[int]], channels: int = 3, quality: Union[int, JpegOptions] = 75, device="cuda:0", max_batch: int = 8,
+                 optimize: bool = False, restart_rows: int = 0, restart_blocks: int = 0):
         self.lib = N.load()
         self.height, self.width = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
-        self.channels, self.quality, self.max_batch = int(channels), int(quality), int(max_batch)
+        if isinstance(quality, JpegOptions):
+            if optimize or restart_rows or restart_blocks:
+                raise ValueError("give a JpegOptions or the keywords, not both")
+            self.options = JpegOptions.of(quality)
+        else:
+            self.options = JpegOptions.of(JpegOptions(quality, optimize, restart_rows, restart_blocks))
+        self.channels, self.quality, self.max_batch = int(channels), self.options.quality, int(max_batch)
         if self.max_batch < 1:
             raise ValueError("max_batch must be >= 1")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("the JPEG encoder runs on the MI355X only (no CPU path); the reference's host path is Pillow's Image.save")
-        h = ctypes.c_void_p()
-        N.check_jpeg(self.lib.lspjpeg_create(self.width, self.height, self.channels, self.quality, ctypes.byref(h)))
+        h = _create(self.lib, self.width, self.height, self.channels, self.options)
         self._h = h
         self.header = _header_of(self.lib, h)
         self.capacity = int(self.lib.lspjpeg_capacity_bytes(h))

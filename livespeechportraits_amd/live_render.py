@@ -30,7 +30,7 @@ class LivePortraitPool:
     generator forward.  ``raster_chunk``: frames per rasteriser launch (one launch per tick unless a tick emits more: 1 MiB of map per
     frame).  A tick may bring a session at most ``max_tick_samples`` samples: what the stage's rings (its ``max_push``) can take.
 
-    ``record_quality`` (a JPEG quality) makes the pool able to record: it then keeps every session's last ``ring_samples`` samples on the
+    ``record_quality`` (a JPEG quality or a ``jpeg.JpegOptions``) makes the pool able to record: it then keeps every session's last ``ring_samples`` samples on the
     device, and ``open`` / ``record`` take AviWriters that ``tick`` appends the session's frames and their audio to.  ``record_route``
     "device" (one lspavi_pack_multi per group of frames) or "host" (JpegEncoder + append_jpegs per session); both write the same files.
 
@@ -72,7 +72,7 @@ class LivePortraitPool:
         self.delay = max(audio.ff_mouth, audio.ff_head) + max(stage.future)
         self._maps = torch.empty((self.raster_chunk, 1, self.load_size, self.load_size), dtype=torch.float32, device=self.device)
         self._lm: Dict[int, int] = {}                                              # audio session id -> landmark session id
-        self._jpeg: Dict[int, object] = {}                                         # quality -> JpegEncoder
+        self._jpeg: Dict[object, object] = {}                                      # jpeg.JpegOptions (the whole option set) -> JpegEncoder
         self.last_groups: List[List[Tuple[int, int]]] = []
         self.last_points = None
         self.record_quality = self.record_route = None
@@ -83,14 +83,17 @@ class LivePortraitPool:
                 raise ValueError("record_route needs record_quality")
             return
         from . import video as V
-        if not 1 <= int(record_quality) <= 100:
+        from .jpeg import JpegOptions
+        if isinstance(record_quality, JpegOptions):
+            record_quality = JpegOptions.of(record_quality)
+        if not 1 <= int(JpegOptions.of(record_quality).quality) <= 100:
             raise ValueError("record_quality must be in 1..100")
         self.record_route = record_route or V.DEFAULT_LIVE_RECORD_ROUTE
         if self.record_route not in ("device", "host"):
             raise ValueError("record_route must be 'device' or 'host'")
         if self.max_batch > 64:
             raise ValueError("a recording pool encodes at most 64 frames per group (max_batch = %d)" % self.max_batch)
-        self.record_quality = int(record_quality)
+        self.record_quality = record_quality if isinstance(record_quality, JpegOptions) else int(record_quality)
         # the oldest frame a tick can emit: delay frames behind the audio, or the landmark filters' full radius while max_lookahead holds the first frames back
         lag = max(audio.ff_mouth, audio.ff_head) + max(stage.radii)
         self.ring_samples = V.live_ring_samples(lag, self.max_tick_samples, self.rate, self.fps)
@@ -191,11 +194,11 @@ class LivePortraitPool:
         return sorted(self._lm)
 
     # ---- a tick ------------------------------------------------------------------------------------------------------------------
-    def tick(self, samples=None, finish=(), host: bool = False, jpeg_quality: Optional[int] = None):
+    def tick(self, samples=None, finish=(), host: bool = False, jpeg_quality=None):
         """Push ``samples`` ({session id: float32 16 kHz samples -- or, for a session opened with ``input_rate``, its raw samples: int16 or
         float32, [n] or [n, channels]}) and end the sessions in ``finish`` (closed afterwards).  -> {id:
         (frame_start, frames)} for every session named: the frames that became final, uint8 [k, H, W, 3] on the device (a numpy array with
-        ``host``), or a list of k complete JPEG files (``bytes``) with ``jpeg_quality``.  Nothing is changed when an argument is refused."""
+        ``host``), or a list of k complete JPEG files (``bytes``) with ``jpeg_quality`` (1..100, or a ``jpeg.JpegOptions``).  Nothing is changed when an argument is refused."""
         torch = self.torch
         pairs = list(samples.items()) if hasattr(samples, "items") else list(samples or ())
         finish = list(finish)
@@ -211,8 +214,12 @@ class LivePortraitPool:
             if sid not in self._lm:
                 self.audio.plan.check(sid)                                         # raises what the audio pool raises for a closed / unknown id
                 raise KeyError("unknown session id %r" % (sid,))
-        if jpeg_quality is not None and not 1 <= int(jpeg_quality) <= 100:
-            raise ValueError("jpeg_quality must be in 1..100")
+        if jpeg_quality is not None:
+            from .jpeg import JpegOptions
+            if isinstance(jpeg_quality, JpegOptions):
+                jpeg_quality = JpegOptions.of(jpeg_quality)
+            if not 1 <= int(JpegOptions.of(jpeg_quality).quality) <= 100:
+                raise ValueError("jpeg_quality must be in 1..100")
         lengths = {sid: len(smp) for sid, smp in pairs}
         staged = [sid for sid in dict.fromkeys([s for s, _ in pairs] + finish) if sid in self._in]
         if staged:
@@ -271,7 +278,7 @@ class LivePortraitPool:
                     self.last_groups.append(owner[g0:g1])
             result = {}
             if jpeg_quality is not None:                                           # 5. complete files; only the compressed bytes cross PCIe
-                enc = self._encoder(int(jpeg_quality))
+                enc = self._encoder(jpeg_quality)
                 files: List[bytes] = []
                 for g0 in range(0, total, self.max_batch):
                     files += enc.encode(frames[g0:min(total, g0 + self.max_batch)])
@@ -399,7 +406,9 @@ class LivePortraitPool:
         for sid, (mouth, poses) in self.audio.plan.preview(lengths, set(finish)).items():
             copy.copy(self.stage.sched[self._lm[sid]]).push(mouth, poses, sid in finish)
 
-    def _encoder(self, quality: int):
+    def _encoder(self, quality):
+        from .jpeg import JpegOptions
+        quality = JpegOptions.of(quality)                                          # 75 and JpegOptions(75) are one encoder
         enc = self._jpeg.get(quality)
         if enc is None:
             from .jpeg import JpegEncoder

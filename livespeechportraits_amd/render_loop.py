@@ -28,7 +28,7 @@ def batched(it: Iterable, n: int) -> Iterator[List]:
 def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch.Tensor, batch: int = 8,
                   device: Optional[torch.device] = None,
                   on_frame: Optional[Callable[[int, np.ndarray], None]] = None, streams: int = 2,
-                  jpeg_quality: Optional[int] = None, video=None, audio=None, video_route: Optional[str] = None) -> List[np.ndarray]:
+                  jpeg_quality=None, video=None, audio=None, video_route: Optional[str] = None) -> List[np.ndarray]:
     """``feature_maps`` yields [1,H,W] (or [C,H,W]) CPU/GPU tensors as
     ``facedataset.dataset.get_data_test_mode`` does (demo.py:262); ``cand_image`` is demo.py's
     ``img_candidates`` ([1,12,H,W], already on the device).  Returns (or streams to ``on_frame``) uint8 HWC
@@ -44,7 +44,7 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
     first measurements were not separated from that throttling).
     A model that cannot give a second handle (the `small` U-Net, several gpu_ids, stand-ins) gets one lane on the current stream: enqueue, wait, hand out.
 
-    ``jpeg_quality`` (1..100, Pillow's default is 75): every lane encodes its frames on its own stream right behind the generator (jpeg.JpegEncoder,
+    ``jpeg_quality`` (1..100, Pillow's default is 75; or a ``jpeg.JpegOptions`` with Pillow's ``optimize`` / restart switches): every lane encodes its frames on its own stream right behind the generator (jpeg.JpegEncoder,
     include/lspjpeg.h) and the frames are handed out as complete JPEG files (``bytes``, what demo.py:271's save_images writes as pred_<n>.jpg); only the
     compressed bytes cross PCIe.  There is no host encoder: a model on the host with ``jpeg_quality`` raises.
 
@@ -176,7 +176,7 @@ class _null:
 def render_frames_from_landmarks(model, landmarks: Iterable, shoulders: Iterable, cand_image: torch.Tensor,
                                  pad=None, load_size: int = 512, batch: int = 8,
                                  on_frame: Optional[Callable[[int, np.ndarray], None]] = None,
-                                 jpeg_quality: Optional[int] = None, save_input: bool = False, video=None, audio=None, video_input=None,
+                                 jpeg_quality=None, save_input: bool = False, video=None, audio=None, video_input=None,
                                  video_route: Optional[str] = None) -> List[np.ndarray]:
     """demo.py:260-272 with the edge map drawn on the device: per frame the loop moves the 73 landmarks and the shoulder
     points (~1.5 KB) instead of a host-rasterised 1 MiB feature map.  ``landmarks`` yields [73, 2] arrays (``pred_landmarks[i]``

@@ -240,7 +240,8 @@ def _list(kind: bytes, body: bytes) -> bytes:
 
 def write_avi(path: str, jpegs: Sequence[bytes], waveform=None, fps: int = 60, audio_rate: int = 16000, audio_format: str = "f32",
               batch: int = 64) -> int:
-    """Write files the caller already holds (``render_frames(..., jpeg_quality=75)``) as one AVI; ``waveform``: the clip's float32 samples at
+    """Write files the caller already holds (``render_frames(..., jpeg_quality=75)``, or with a ``jpeg.JpegOptions``: every chunk is a whole file,
+    optimised tables and restart markers included) as one AVI; ``waveform``: the clip's float32 samples at
     ``audio_rate`` (None: no audio stream), at least ``len(jpegs) * audio_rate // fps`` of them.  Returns the frame count."""
     jpegs = list(jpegs)
     if not jpegs:
@@ -495,9 +496,10 @@ def clip_audio(video: AviWriter, audio, device):
 class VideoSink:
     """What one lane of a render loop puts behind its generator when ``video`` is given: submit() a batch of uint8 device frames on the
     current stream, collect() it into the writer.  ``route`` "device": DeviceMuxer + append_fragment (one copy per batch); "host":
-    JpegEncoder.submit / collect + append_jpegs (one copy per frame, the fragment built on the host).  Both write the same bytes."""
+    JpegEncoder.submit / collect + append_jpegs (one copy per frame, the fragment built on the host).  Both write the same bytes.
+    ``quality``: 1..100 or a ``jpeg.JpegOptions`` (optimised tables, restart intervals)."""
 
-    def __init__(self, video: AviWriter, size, quality: int, device, max_batch: int, audio_dev=None, audio_host=None, route: Optional[str] = None):
+    def __init__(self, video: AviWriter, size, quality, device, max_batch: int, audio_dev=None, audio_host=None, route: Optional[str] = None):
         from .jpeg import JpegEncoder
         route = route or DEFAULT_VIDEO_ROUTE
         if route not in ("device", "host"):

@@ -4,7 +4,13 @@
       uint8 edge maps (grayscale), with the bf16 batch-8 forward timed the same way for the 10 % bar;
   (b) Pillow (Image.fromarray(img).save(f, "JPEG", quality=75)) on the same frames with 1 and 16 threads, on this host, if Pillow is installed;
   (c) render_frames frames/s, `normal` bf16, batch 8, without and with jpeg_quality=75, run A-B-A-B.
-    python tools/jpeg_time.py [name] [output directory, default profiles/]"""
+    python tools/jpeg_time.py [name] [output directory, default profiles/]
+With --options instead (default name jpeg_options_time), the encoder's options as arms {default, restart_rows=1, optimize, both}, A-B-A-B:
+  (d) device time of lspjpeg_encode for the same 8 + 8 frames per arm (the default arm runs the kernels of a handle without options), and
+      the bytes per frame of each arm on the generator's own frames;
+  (e) JpegDecoder.decode of 64 such files per arm (host clock, plan + upload + three stages + status): the decoder gives a wave to every
+      restart interval.
+    python tools/jpeg_time.py --options [name] [output directory]"""
 import argparse
 import ctypes
 import io
@@ -27,8 +33,10 @@ from livespeechportraits_amd.jpeg import JpegEncoder  # noqa: E402
 from livespeechportraits_amd.render_loop import render_frames  # noqa: E402
 from livespeechportraits_amd.topology import build_topology  # noqa: E402
 
-name = sys.argv[1] if len(sys.argv) > 1 else "jpeg_time"
-out_dir = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles")
+OPTIONS = "--options" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--options"]
+name = argv[0] if len(argv) > 0 else ("jpeg_options_time" if OPTIONS else "jpeg_time")
+out_dir = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles")
 dev = torch.device("cuda:0")
 B, S, Q = 8, 512, 75
 rec = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "batch": B, "size": S, "quality": Q}
@@ -76,6 +84,55 @@ st = torch.cuda.current_stream(dev)
 def launch(enc, x):
     N.check_jpeg(enc.lib.lspjpeg_encode(enc._h, ctypes.c_void_p(x.data_ptr()), B, ctypes.c_void_p(enc._dst.data_ptr()), ctypes.c_void_p(enc._sizes.data_ptr()),
                                         ctypes.c_void_p(enc._ws.data_ptr()), enc._ws_bytes, ctypes.c_void_p(st.cuda_stream)))
+
+
+def finish():
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, name + ".json"), "w") as fh:
+        json.dump(rec, fh, indent=1)
+    with open(os.path.join(out_dir, name + ".txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if OPTIONS:
+    from livespeechportraits_amd.jpeg import JpegDecoder, probe
+    arms = {"default": {}, "restart_rows=1": dict(restart_rows=1), "optimize": dict(optimize=True), "both": dict(optimize=True, restart_rows=1)}
+    made = {a: {"colour": (JpegEncoder(S, 3, Q, dev, max_batch=B, **kw), u8), "gray": (JpegEncoder(S, 1, Q, dev, max_batch=B, **kw), edges)} for a, kw in arms.items()}
+    rec["d"] = {a: {"colour_us": [], "gray_us": []} for a in arms}
+    for rnd in range(2):                                   # A-B-A-B over the arms
+        for a in arms:
+            for k, (enc, x) in made[a].items():
+                rec["d"][a][k + "_us"].append(round(device_us(lambda: launch(enc, x)), 2))
+    files = {a: {k: enc.encode(x) for k, (enc, x) in made[a].items()} for a in arms}
+    for a in arms:
+        rec["d"][a]["bytes_per_frame"] = {k: int(np.mean([len(f) for f in v])) for k, v in files[a].items()}
+        rec["d"][a]["segments"] = probe(files[a]["colour"][0]).segments
+        say("(d) lspjpeg_encode, %d frames %d^2 q%d, %-14s: colour %s us, gray %s us; mean file: colour %d B, gray %d B; %d restart intervals per colour file" % (
+            B, S, Q, a, rec["d"][a]["colour_us"], rec["d"][a]["gray_us"], rec["d"][a]["bytes_per_frame"]["colour"], rec["d"][a]["bytes_per_frame"]["gray"],
+            rec["d"][a]["segments"]))
+    base = rec["d"]["default"]["bytes_per_frame"]
+    say("(d) bytes against the default arm: " + ", ".join("%s colour %+.1f %% gray %+.1f %%" % (
+        a, 100.0 * (rec["d"][a]["bytes_per_frame"]["colour"] / base["colour"] - 1), 100.0 * (rec["d"][a]["bytes_per_frame"]["gray"] / base["gray"] - 1))
+        for a in arms if a != "default"))
+    dec = JpegDecoder(dev, max_side=S, max_batch=64)
+    want = dec.decode(files["default"]["colour"] * 8)
+    rec["e"] = {a: [] for a in arms}
+    for rnd in range(2):
+        for a in arms:
+            batch = files[a]["colour"] * 8                 # 64 recorded frames
+            got = dec.decode(batch)
+            assert all(torch.equal(g, w) for g, w in zip(got, want)), a
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(10):
+                dec.decode(batch)
+            torch.cuda.synchronize()
+            rec["e"][a].append(round((time.perf_counter() - t0) / 10 * 1e3, 3))
+    for a in arms:
+        say("(e) JpegDecoder.decode of 64 colour files %d^2, %-14s: %s ms per call (host clock; the pixels equal the default arm's)" % (S, a, rec["e"][a]))
+    eng.close()
+    finish()
+    sys.exit(0)
 
 
 rec["a"] = {}
@@ -155,8 +212,4 @@ for arm in ("plain", "jpeg75", "plain", "jpeg75", "plain", "jpeg75"):
     rec["c"][arm + "_fps"].append(round(nframes / dt, 1))
     say("(c) render_frames normal bf16 batch %d, %s: %.1f frames/s (%d frames in %.3f s)" % (B, arm, nframes / dt, nframes, dt))
 eng.close()
-os.makedirs(out_dir, exist_ok=True)
-with open(os.path.join(out_dir, name + ".json"), "w") as fh:
-    json.dump(rec, fh, indent=1)
-with open(os.path.join(out_dir, name + ".txt"), "w") as fh:
-    fh.write("\n".join(lines) + "\n")
+finish()
