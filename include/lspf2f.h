@@ -262,6 +262,35 @@ int lspf2f_conv3x3(const void *src0, const void *src1, const void *w_packed, con
                    int tile_n, int split_k, int k_group, int dtype, void *scratch, size_t scratch_bytes,
                    void *hip_stream);
 
+/* InstanceNorm2d(affine=False, eps=1e-5) as the InstanceNorm plans run it behind a conv, one layer at a time (tests/test_gpu_instnorm_layer.py): the
+ * same launchers with the same parameter derivation as the forward.  x: fp32 NHWC [batch][hw][c], normalised in place:
+ * x = relu?((x - mean[b][c]) * rstd[b][c] + residual?).  splits > 1: the raw tensor is first folded from partial [splits][batch * hw][c] (+ bias [c] or NULL),
+ * as a split-K conv leaves it; x need not be initialised then.  route 0 = "small": one launch, one workgroup per (frame, 32 channels) (the plans take it up to
+ * 1024 pixels per frame; beyond, or with three_pass != 0, its three-pass form runs -- same bits); no scratch, mean_out / rstd_out must be NULL.  route 1 =
+ * "reduce": partial sums of groups of 64 rows -> merge in double -> streaming normalisation; c <= 1024; scratch of lspf2f_instance_norm_scratch_bytes();
+ * mean_out / rstd_out ([batch][c], may be NULL) receive the finalised statistics.  A shape a launcher refuses is LSPF2F_ERR_UNSUPPORTED. */
+size_t lspf2f_instance_norm_scratch_bytes(int batch, int hw, int c, int route);
+int lspf2f_instance_norm(float *x, const float *partial, int splits, const float *bias, const float *residual,
+                         int relu, int batch, int hw, int c, int route, int three_pass,
+                         float *mean_out, float *rstd_out, void *scratch, size_t scratch_bytes, void *hip_stream);
+
+/* One conv followed by InstanceNorm through the statistics route an InstanceNorm plan takes for that kernel: the arguments of lspf2f_conv3x3, with `bias`
+ * ([cout] or NULL: the conv bias, which those plans pass as shift with a scale of 1) in place of scale / shift, and `stats`: a statistics scratch of
+ * lspf2f_conv3x3_instnorm_scratch_bytes() bytes, 16-byte aligned.  residual and relu apply BEHIND the normalisation.  fp32 only.  Exactly the four producers of
+ * statistics the plans have are accepted, selected as in lspf2f_conv3x3; everything else is LSPF2F_ERR_UNSUPPORTED:
+ *   tile 128 | 64 | 32 x 64, k_group >= 0, split_k 1: the implicit GEMM summing in its epilogue, one group per wave (4x as many for upsample == 2, per parity) --
+ *     under the planner's own precondition (>= 1024 pixels per frame of its M space, whole waves per frame) -> finalize -> apply;
+ *   tile 4001 | 4002 | 4003, k_group -1: wino3x3, one group per tile-block of 128 pixels (from its epilogue, or from its split-K combine) -> finalize -> apply;
+ *   tile 5001 | 5002, k_group -1: winoup3x3, one group per 128 output pixels -> finalize -> apply;
+ *   tile 1 x 1: the tiny-M kernel, which normalises (+ residual, ReLU) in its own epilogue. */
+size_t lspf2f_conv3x3_instnorm_scratch_bytes(int batch, int hs, int ws, int c0, int c1, int cout, int stride,
+                                             int upsample, int tile_m, int tile_n, int split_k, int k_group, int dtype);
+int lspf2f_conv3x3_instnorm(const void *src0, const void *src1, const void *w_packed, const float *bias,
+                            const void *residual, void *out, int batch, int hs, int ws, int c0, int c1, int cout,
+                            int stride, int upsample, int relu, int tile_m, int tile_n, int split_k, int k_group,
+                            int dtype, void *scratch, size_t scratch_bytes, void *stats, size_t stats_bytes,
+                            void *hip_stream);
+
 /* Round 6 (tools/probes/wino_pair_probe.py, tests/test_gpu_conv.py): `nlayers` (1..4) consecutive Winograd convs of ONE shape (batch x hs x hs x c -> c, fp32: the convs of one
  * or two ResidualBlocks, models/networks.py:650-675), layer k reading src[k] (= out[k - 1] for k > 0), weights u_packed[k] in the fragment order of tile 4001, optional
  * scale[k] / shift[k] / residual[k] (NULL entries allowed), relu[k].  mode 0: one launch of wino3x3<1> per layer, exactly as the plans run them; mode 1: ONE launch of

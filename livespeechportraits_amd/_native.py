@@ -138,6 +138,10 @@ SIGNATURES = {
                                     POINTER(c_float), POINTER(c_int)]),
     "lspf2f_conv3x3_scratch_bytes": (c_size_t, [c_int] * 13),
     "lspf2f_conv3x3": (c_int, [c_void_p] * 7 + [c_int] * 14 + [c_void_p, c_size_t, c_void_p]),
+    "lspf2f_instance_norm_scratch_bytes": (c_size_t, [c_int] * 4),
+    "lspf2f_instance_norm": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] * 6 + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "lspf2f_conv3x3_instnorm_scratch_bytes": (c_size_t, [c_int] * 13),
+    "lspf2f_conv3x3_instnorm": (c_int, [c_void_p] * 6 + [c_int] * 14 + [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "lspf2f_wino_chain_scratch_bytes": (c_size_t, [c_int] * 5),
     "lspf2f_wino_chain": (c_int, [c_int] + [POINTER(c_void_p)] * 6 + [POINTER(c_int)] + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
     "lspf2f_unet_prepare": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),

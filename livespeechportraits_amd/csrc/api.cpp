@@ -429,6 +429,37 @@ int lspf2f_clock_probe(unsigned long long *out_dev, unsigned duration_us, void *
 
 }  // extern "C"
 
+// ---- InstanceNorm behind a conv: what run_layer and the per-layer entry points (lspf2f_instance_norm, lspf2f_conv3x3_instnorm) share ----
+// statistics scratch of one layer: per-group (sum d, sum d^2, shift) [3][slab][C], then the finalised (mean, rstd) [2][B][C]; slab = B x the groups the scratch holds
+static void in_bind_stats(InstNormParams &q, float *st, size_t slab)
+{
+    q.psum = st; q.psq = st + slab * q.C; q.pshift = st + 2 * slab * q.C;
+    q.mean = st + 3 * slab * q.C; q.rstd = q.mean + (size_t)q.B * q.C;
+}
+// groups a statistics producer leaves per frame: the implicit GEMM's epilogue one per wave (x4 for the sub-pixel up-convs, per parity), the Winograd kernels one per
+// tile-block of 128 output pixels
+static void in_groups_igemm(InstNormParams &q, int bm, bool up4, int rhw)
+{
+    q.rows_per_group = in_fused_wave_rows(bm);
+    q.groups = (up4 ? 4 : 1) * rhw / q.rows_per_group;
+}
+static void in_groups_wino(InstNormParams &q) { q.groups = q.hw / 128; q.rows_per_group = 128; }
+static hipError_t in_finalize_apply(const InstNormParams &q, hipStream_t s)
+{
+    hipError_t r = launch_in_finalize(q, s);
+    if (r == hipSuccess) r = launch_in_apply(q, s);
+    return r;
+}
+// the standalone passes over a complete raw tensor (or over split-K partials + bias): one launch (`small`), or 64-row partial sums -> finalize -> apply
+static hipError_t in_standalone(InstNormParams &q, bool small, float *st, size_t slab, hipStream_t s)
+{
+    if (small) return launch_in_small(q, s);
+    in_bind_stats(q, st, slab);
+    q.groups = (q.hw + 63) / 64; q.rows_per_group = 64;
+    const hipError_t r = launch_in_reduce_stats(q, s);
+    return r == hipSuccess ? in_finalize_apply(q, s) : r;
+}
+
 static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, const float *cand, int cand_batch,
                      float *out, unsigned char *out_u8, int batch, hipStream_t s)
 {
@@ -446,14 +477,7 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
             q.three_pass = h->in_small_regs ? 0 : 1;
         q.x = tptr(l.out); q.residual = tptr(l.res); q.relu = l.relu; q.partial = nullptr; q.splits = 1; q.bias = nullptr;
         q.B = batch; q.hw = l.ho * l.ho; q.C = l.cout;
-        if (l.in_route == kInSmall) return launch_in_small(q, s);
-        q.psum = st; q.psq = st + slab * l.cout; q.pshift = st + 2 * slab * l.cout;
-        q.mean = st + 3 * slab * l.cout; q.rstd = q.mean + (size_t)batch * l.cout;
-        q.groups = (q.hw + 63) / 64; q.rows_per_group = 64;
-        hipError_t r = launch_in_reduce_stats(q, s);
-        if (r == hipSuccess) r = launch_in_finalize(q, s);
-        if (r == hipSuccess) r = launch_in_apply(q, s);
-        return r;
+        return in_standalone(q, l.in_route == kInSmall, st, slab, s);
     };
     if (l.kind == kFirstConv) {
         FirstConvParams p{};
@@ -568,13 +592,11 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
             q.three_pass = h->in_small_regs ? 0 : 1;
             q.x = tptr(l.out); q.residual = tptr(l.res); q.relu = l.relu; q.partial = nullptr; q.splits = 1; q.bias = nullptr;
             q.B = batch; q.hw = l.ho * l.ho; q.C = l.cout;
-            q.psum = st; q.psq = st + slab * l.cout; q.pshift = st + 2 * slab * l.cout;
-            q.mean = st + 3 * slab * l.cout; q.rstd = q.mean + (size_t)batch * l.cout;
-            q.groups = q.hw / 128; q.rows_per_group = 128;
+            in_bind_stats(q, st, slab);
+            in_groups_wino(q);
             p.psum = q.psum; p.psq = q.psq; p.pshift = q.pshift;
             if (h->timing_part & 1) e = launch_winoup(p, l.winoup, s);
-            if (e == hipSuccess) e = launch_in_finalize(q, s);
-            if (e == hipSuccess) e = launch_in_apply(q, s);
+            if (e == hipSuccess) e = in_finalize_apply(q, s);
         } else {
             if (h->timing_part & 1) e = launch_winoup(p, l.winoup, s);
             if (l.inorm) e = in_after_complete_output(e);
@@ -608,13 +630,11 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
             q.three_pass = h->in_small_regs ? 0 : 1;
             q.x = tptr(l.out); q.residual = tptr(l.res); q.relu = l.relu; q.partial = nullptr; q.splits = 1; q.bias = nullptr;
             q.B = batch; q.hw = l.ho * l.ho; q.C = l.cout;
-            q.psum = st; q.psq = st + slab * l.cout; q.pshift = st + 2 * slab * l.cout;
-            q.mean = st + 3 * slab * l.cout; q.rstd = q.mean + (size_t)batch * l.cout;
-            q.groups = q.hw / 128; q.rows_per_group = 128;
+            in_bind_stats(q, st, slab);
+            in_groups_wino(q);
             p.psum = q.psum; p.psq = q.psq; p.pshift = q.pshift;
             if (h->timing_part & 1) e = launch_wino(p, l.wino, s);
-            if (e == hipSuccess) e = launch_in_finalize(q, s);
-            if (e == hipSuccess) e = launch_in_apply(q, s);
+            if (e == hipSuccess) e = in_finalize_apply(q, s);
         } else {
             if (h->timing_part & 1) e = launch_wino(p, l.wino, s);
             if (l.inorm) e = in_after_complete_output(e);
@@ -701,30 +721,19 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
             q.three_pass = h->in_small_regs ? 0 : 1;
             q.x = tptr(l.out); q.residual = tptr(l.res); q.relu = l.relu;
             q.B = batch; q.hw = l.ho * l.ho; q.C = l.cout;
-            q.psum = st; q.psq = st + slab * l.cout; q.pshift = st + 2 * slab * l.cout;
-            q.mean = st + 3 * slab * l.cout; q.rstd = q.mean + (size_t)batch * l.cout;
             p.residual = nullptr; p.relu = 0;
             if (l.in_route == kInFused) {
-                const int rhw = l.up4 ? l.hs * l.hs : l.ho * l.ho;
-                q.rows_per_group = l.bm == 32 ? 32 : l.bm / 2;                  // rows of one wave
-                q.groups = (l.up4 ? 4 : 1) * rhw / q.rows_per_group;
+                in_bind_stats(q, st, slab);
+                in_groups_igemm(q, l.bm, l.up4, l.up4 ? l.hs * l.hs : l.ho * l.ho);      // one group per wave
                 p.psum = q.psum; p.psq = q.psq; p.pshift = q.pshift; p.in_groups = q.groups;
                 e = launch_igemm(p, l.bm, l.bn, l.group, s);
-                if (e == hipSuccess) e = launch_in_finalize(q, s);
-                if (e == hipSuccess) e = launch_in_apply(q, s);
+                if (e == hipSuccess) e = in_finalize_apply(q, s);
             } else {
                 e = launch_igemm(p, l.bm, l.bn, l.group, s);
                 q.splits = l.splits;
                 q.partial = l.splits > 1 ? p.partial : nullptr;
                 q.bias = bptr(l.shift_off);
-                if (l.in_route == kInSmall) {
-                    if (e == hipSuccess) e = launch_in_small(q, s);
-                } else {
-                    q.groups = (q.hw + 63) / 64; q.rows_per_group = 64;
-                    if (e == hipSuccess) e = launch_in_reduce_stats(q, s);
-                    if (e == hipSuccess) e = launch_in_finalize(q, s);
-                    if (e == hipSuccess) e = launch_in_apply(q, s);
-                }
+                if (e == hipSuccess) e = in_standalone(q, l.in_route == kInSmall, st, slab, s);
             }
         } else {
             const bool fused = l.fused_splitk && h->fuse_splitk;
@@ -1040,10 +1049,13 @@ size_t lspf2f_conv3x3_scratch_bytes(int batch, int hs, int ws, int c0, int c1, i
     return sp > 1 ? (size_t)sp * Mout * cout * sizeof(float) : 0;
 }
 
-int lspf2f_conv3x3(const void *src0, const void *src1, const void *w_packed, const float *scale,
-                   const float *shift, const void *residual, void *out, int batch, int hs, int ws, int c0,
-                   int c1, int cout, int stride, int upsample, int relu, int tile_m, int tile_n, int split_k,
-                   int k_group, int dtype, void *scratch, size_t scratch_bytes, void *hip_stream)
+// lspf2f_conv3x3, and with `in` the conv of lspf2f_conv3x3_instnorm: the producer then also leaves the statistics InstanceNorm plans take from it -- per-group sums at
+// in->psum / psq / pshift ([B][in->groups][cout], bound and sized by the caller) from the implicit GEMM and the Winograd kernels, the normalisation itself from the
+// tiny-M kernel.  The caller has checked that (tile, k_group) names one of those producers.
+static int conv3x3_run(const void *src0, const void *src1, const void *w_packed, const float *scale,
+                       const float *shift, const void *residual, void *out, int batch, int hs, int ws, int c0,
+                       int c1, int cout, int stride, int upsample, int relu, int tile_m, int tile_n, int split_k,
+                       int k_group, int dtype, void *scratch, size_t scratch_bytes, void *hip_stream, const InstNormParams *in)
 {
     if (dtype < 0 || dtype > 2) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "dtype must be 0 (fp32), 1 (bf16) or 2 (fp16)");
     const int ktc = dtype ? 64 : 32;
@@ -1072,6 +1084,7 @@ int lspf2f_conv3x3(const void *src0, const void *src1, const void *w_packed, con
         q.B = batch; q.Hs = hs; q.Ws = ws; q.Ho = upsample ? 2 * hs : (stride == 2 ? (hs + 1) / 2 : hs); q.Wo = q.Ho;
         q.Cin = c0; q.Cout = cout; q.stride = stride; q.up = upsample == 1; q.relu = relu; q.M = batch * q.Ho * q.Wo;
         q.dtype = dtype;
+        q.in_fused = in ? 1 : 0;
         const bool want = (tile_m == 1 && tile_n == 1) || (tile_m == 0 && tile_n == 0 && split_k == 0 && k_group != -4);
         if (want && c1 == 0 && upsample != 2 && smallm_supported(q)) {
             e = launch_smallm(q, static_cast<hipStream_t>(hip_stream));
@@ -1106,6 +1119,7 @@ int lspf2f_conv3x3(const void *src0, const void *src1, const void *w_packed, con
                 q.partial = static_cast<float *>(scratch);
                 q.tile_cnt = reinterpret_cast<unsigned *>(static_cast<char *>(scratch) + slab);   // must be zero on entry; every launch leaves it zero
             }
+            if (in) { q.psum = in->psum; q.psq = in->psq; q.pshift = in->pshift; }
             if (dtype != 0 || stride != 1 || !upsample || residual || hs != ws || !winoup_supported(q, nbk))
                 return fail(LSPF2F_ERR_UNSUPPORTED, "the up-conv Winograd kernel does not support this shape");
             e = launch_winoup(q, nbk, static_cast<hipStream_t>(hip_stream));
@@ -1160,6 +1174,7 @@ int lspf2f_conv3x3(const void *src0, const void *src1, const void *w_packed, con
                 if (scratch && scratch_bytes >= used + blocks * 4 * 8 * 8) q.stamps = reinterpret_cast<unsigned long long *>(static_cast<char *>(scratch) + used);
             }
 #endif
+            if (in) { q.psum = in->psum; q.psq = in->psq; q.pshift = in->pshift; }
             if (dtype != 0 || c1 != 0 || stride != 1 || upsample != 0 || hs != ws || !wino_supported(q, tile_m - 4000))
                 return fail(LSPF2F_ERR_UNSUPPORTED, "the Winograd kernel does not support this shape");
             e = launch_wino(q, tile_m - 4000, static_cast<hipStream_t>(hip_stream));
@@ -1297,6 +1312,13 @@ int lspf2f_conv3x3(const void *src0, const void *src1, const void *w_packed, con
     p.ktiles_per_split = (p.ktiles_total + sp - 1) / sp;
     sp = (p.ktiles_total + p.ktiles_per_split - 1) / p.ktiles_per_split;
     p.splits = sp;
+    if (in) {
+        // epilogue sums: the planner's own precondition (a wave's rows inside one frame, one K slice), and the group count the caller sized the statistics for
+        const int rhw = p.up4 ? hs * ws : p.Ho * p.Wo;
+        if (!in_fused_eligible(bm, sp, rhw) || in->groups != (p.up4 ? 4 : 1) * rhw / in_fused_wave_rows(bm))
+            return fail(LSPF2F_ERR_UNSUPPORTED, "the implicit GEMM gathers InstanceNorm statistics in its epilogue only with one K slice, >= 1024 pixels per frame and whole waves per frame");
+        p.psum = in->psum; p.psq = in->psq; p.pshift = in->pshift; p.in_groups = in->groups;
+    }
     if (sp > 1) {
         if (!scratch || scratch_bytes < (size_t)sp * p.Mout * cout * sizeof(float))
             return fail(LSPF2F_ERR_STATE, "split-K scratch missing or too small");
@@ -1312,6 +1334,125 @@ int lspf2f_conv3x3(const void *src0, const void *src1, const void *w_packed, con
     e = launch_igemm(p, bm, bn, grp, s);
     if (e == hipSuccess && sp > 1) e = launch_splitk_reduce(p, s);
     if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 launch");
+    return LSPF2F_OK;
+}
+
+int lspf2f_conv3x3(const void *src0, const void *src1, const void *w_packed, const float *scale,
+                   const float *shift, const void *residual, void *out, int batch, int hs, int ws, int c0,
+                   int c1, int cout, int stride, int upsample, int relu, int tile_m, int tile_n, int split_k,
+                   int k_group, int dtype, void *scratch, size_t scratch_bytes, void *hip_stream)
+{
+    return conv3x3_run(src0, src1, w_packed, scale, shift, residual, out, batch, hs, ws, c0, c1, cout, stride, upsample, relu, tile_m, tile_n, split_k, k_group, dtype,
+                       scratch, scratch_bytes, hip_stream, nullptr);
+}
+
+// ---- InstanceNorm, layer by layer (tests/test_gpu_instnorm_layer.py) ----
+
+static size_t in_route_groups(int hw, int route) { return route == 1 ? (size_t)(hw + 63) / 64 : 0; }
+
+size_t lspf2f_instance_norm_scratch_bytes(int batch, int hw, int c, int route)
+{
+    if (batch < 1 || hw < 1 || c < 1 || route != 1) return 0;                 // the one-launch route keeps nothing in memory
+    return ((size_t)3 * in_route_groups(hw, route) + 2) * batch * c * sizeof(float);
+}
+
+int lspf2f_instance_norm(float *x, const float *partial, int splits, const float *bias, const float *residual, int relu, int batch, int hw, int c, int route,
+                         int three_pass, float *mean_out, float *rstd_out, void *scratch, size_t scratch_bytes, void *hip_stream)
+{
+    if (!x) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "instance_norm: null x");
+    if (route != 0 && route != 1) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "instance_norm: route must be 0 (small) or 1 (reduce)");
+    if (splits < 1 || (splits > 1 && !partial)) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "instance_norm: splits >= 1, and partial slabs when splits > 1");
+    if (route == 0 && (mean_out || rstd_out)) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "instance_norm: the one-launch route keeps its statistics in registers: mean_out / rstd_out must be null");
+    if (batch < 1 || hw < 1) return fail(LSPF2F_ERR_UNSUPPORTED, "instance_norm: batch and hw must be >= 1");
+    if (c < 4 || c % 4) return fail(LSPF2F_ERR_UNSUPPORTED, "instance_norm: the channel count must be a multiple of 4");
+    if (route == 1 && c / 4 > 256) return fail(LSPF2F_ERR_UNSUPPORTED, "instance_norm: the reduce route takes at most 1024 channels (256 channel quads per workgroup)");
+    const size_t need = lspf2f_instance_norm_scratch_bytes(batch, hw, c, route);
+    if (need && (!scratch || scratch_bytes < need)) return fail(LSPF2F_ERR_STATE, "instance_norm: statistics scratch missing or smaller than lspf2f_instance_norm_scratch_bytes()");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    InstNormParams q{};
+    q.three_pass = three_pass ? 1 : 0;
+    q.x = x; q.residual = residual; q.relu = relu; q.partial = splits > 1 ? partial : nullptr; q.splits = splits; q.bias = bias;
+    q.B = batch; q.hw = hw; q.C = c;
+    hipError_t e = in_standalone(q, route == 0, static_cast<float *>(scratch), (size_t)batch * in_route_groups(hw, route), s);
+    if (e == hipErrorInvalidValue) return fail(LSPF2F_ERR_UNSUPPORTED, "instance_norm: the launcher refused this shape");
+    if (e == hipSuccess && mean_out) e = hipMemcpyAsync(mean_out, q.mean, (size_t)batch * c * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && rstd_out) e = hipMemcpyAsync(rstd_out, q.rstd, (size_t)batch * c * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return hipfail(e, "lspf2f_instance_norm launch");
+    return LSPF2F_OK;
+}
+
+// the statistics producer a (tile, k_group) selection of lspf2f_conv3x3 names under InstanceNorm plans
+enum InProducer { kProdNone = 0, kProdIgemm, kProdWino, kProdWinoUp, kProdTiny };
+static InProducer in_producer(int tile_m, int tile_n, int k_group)
+{
+    if (tile_m == 1 && tile_n == 1) return kProdTiny;
+    if ((tile_m == 4001 || tile_m == 4002 || tile_m == 4003) && k_group == -1) return kProdWino;
+    if ((tile_m == 5001 || tile_m == 5002) && k_group == -1) return kProdWinoUp;
+    if ((tile_m == 128 || tile_m == 64 || tile_m == 32) && tile_n == 64 && k_group >= 0) return kProdIgemm;
+    return kProdNone;
+}
+// B, hw, C, groups and rows_per_group of the InstanceNorm behind that conv; "" or why the selection is refused
+static const char *conv3x3_in_shape(int batch, int hs, int ws, int cout, int stride, int upsample, int tile_m, int tile_n, int split_k, int k_group, int dtype,
+                                    InProducer *prod, InstNormParams *q)
+{
+    *prod = in_producer(tile_m, tile_n, k_group);
+    if (*prod == kProdNone) return "conv3x3_instnorm: the statistics producers are the implicit GEMM (tile 128 | 64 | 32 x 64), wino3x3 (4001 .. 4003), winoup3x3 (5001, 5002) and the tiny-M kernel (1 x 1)";
+    if (dtype != 0) return "conv3x3_instnorm: InstanceNorm plans are fp32 only";
+    if (batch < 1 || hs < 1 || hs != ws || cout < 4 || cout % 4 || (stride != 1 && stride != 2) || upsample < 0 || upsample > 2) return "conv3x3_instnorm: bad shape";
+    const int ho = upsample ? 2 * hs : (stride == 2 ? (hs + 1) / 2 : hs);
+    q->B = batch; q->hw = ho * ho; q->C = cout; q->groups = 0; q->rows_per_group = 0;
+    if (*prod == kProdIgemm) {
+        const int rhw = upsample == 2 ? hs * hs : ho * ho;
+        if (split_k != 1 || !in_fused_eligible(tile_m, split_k, rhw))
+            return "conv3x3_instnorm: the implicit GEMM gathers InstanceNorm statistics in its epilogue only with split_k 1, >= 1024 pixels per frame and whole waves per frame";
+        in_groups_igemm(*q, tile_m, upsample == 2, rhw);
+    } else if (*prod != kProdTiny) {
+        if (q->hw % 128) return "conv3x3_instnorm: the Winograd kernels leave one group per tile-block of 128 output pixels";
+        in_groups_wino(*q);
+    }
+    return "";
+}
+// [cout] ones (the scale the conv bias rides on, as the packer writes it for InstanceNorm plans), then the statistics as in_bind_stats lays them out
+size_t lspf2f_conv3x3_instnorm_scratch_bytes(int batch, int hs, int ws, int c0, int c1, int cout, int stride, int upsample, int tile_m, int tile_n, int split_k, int k_group,
+                                             int dtype)
+{
+    (void)c0; (void)c1;
+    InProducer prod;
+    InstNormParams q{};
+    if (*conv3x3_in_shape(batch, hs, ws, cout, stride, upsample, tile_m, tile_n, split_k, k_group, dtype, &prod, &q)) return 0;
+    const size_t stats = prod == kProdTiny ? 0 : ((size_t)3 * q.groups + 2) * batch * cout;
+    return ((size_t)cout + stats) * sizeof(float);
+}
+
+int lspf2f_conv3x3_instnorm(const void *src0, const void *src1, const void *w_packed, const float *bias, const void *residual, void *out, int batch, int hs, int ws,
+                            int c0, int c1, int cout, int stride, int upsample, int relu, int tile_m, int tile_n, int split_k, int k_group, int dtype,
+                            void *scratch, size_t scratch_bytes, void *stats, size_t stats_bytes, void *hip_stream)
+{
+    if (!src0 || !w_packed || !out) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "null argument");
+    InProducer prod;
+    InstNormParams q{};
+    const char *why = conv3x3_in_shape(batch, hs, ws, cout, stride, upsample, tile_m, tile_n, split_k, k_group, dtype, &prod, &q);
+    if (*why) return fail(LSPF2F_ERR_UNSUPPORTED, why);
+    const size_t need = lspf2f_conv3x3_instnorm_scratch_bytes(batch, hs, ws, c0, c1, cout, stride, upsample, tile_m, tile_n, split_k, k_group, dtype);
+    if (!stats || stats_bytes < need || reinterpret_cast<uintptr_t>(stats) % 16)
+        return fail(LSPF2F_ERR_STATE, "conv3x3_instnorm: statistics scratch missing, misaligned or smaller than lspf2f_conv3x3_instnorm_scratch_bytes()");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    float *ones = static_cast<float *>(stats);
+    if (bias) {
+        const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ones), 0x3f800000, (size_t)cout, s);      // 1.0f
+        if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3_instnorm (scale) memset");
+    }
+    q.three_pass = 0;
+    q.x = static_cast<float *>(out); q.residual = static_cast<const float *>(residual); q.relu = relu; q.partial = nullptr; q.splits = 1; q.bias = nullptr;
+    in_bind_stats(q, ones + cout, (size_t)batch * q.groups);
+    // the tiny-M kernel normalises (+ residual, ReLU) in its own epilogue; behind the others the residual add and the ReLU follow the normalisation, in in_apply
+    const bool tiny = prod == kProdTiny;
+    const int rc = conv3x3_run(src0, src1, w_packed, bias ? ones : nullptr, bias, tiny ? residual : nullptr, out, batch, hs, ws, c0, c1, cout, stride, upsample, tiny ? relu : 0,
+                               tile_m, tile_n, split_k, k_group, dtype, scratch, scratch_bytes, hip_stream, &q);
+    if (rc != LSPF2F_OK || tiny) return rc;
+    const hipError_t e = in_finalize_apply(q, s);
+    if (e == hipErrorInvalidValue) return fail(LSPF2F_ERR_UNSUPPORTED, "conv3x3_instnorm: the launcher refused this shape");
+    if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3_instnorm (finalize / apply) launch");
     return LSPF2F_OK;
 }
 

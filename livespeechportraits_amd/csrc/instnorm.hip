@@ -10,9 +10,14 @@
 //   small   H*W <= 1024: in_small, one workgroup per (frame, 32 channels), does fold + statistics + normalisation
 // Numerics: a channel whose H*W values are nearly equal has var << mean^2, and 1/sqrt(var + 1e-5) then amplifies any error in
 // var up to 316x (this is what happens at the 2x2 / 4x4 levels) -- so var is never formed as E[x^2] - mean^2 of raw values.
-// Every group of <= 64 rows sums d = x - c with c = the group's first row (fp32; d is small where it matters), the groups are
-// merged in double with the pairwise update of Chan et al. in a fixed order (bit-reproducible), and the one-launch route makes
-// two passes (mean, then sum (x - mean)^2).  ATen accumulates these statistics in double on the CPU as well.
+// Every group of rows sums d = x - c and d^2 around a shift c, the groups are merged in double with the pairwise update of Chan et al. in a
+// fixed order (bit-reproducible), and the one-launch route makes two passes (mean, then sum (x - mean)^2).  ATen accumulates these
+// statistics in double on the CPU as well.  The conv epilogues take c = the group's first row (fp32 sums; d is small where it matters).  The
+// standalone passes are held, layer by layer, to 4x the floor of ANY fp32 InstanceNorm (tests/test_gpu_instnorm_layer.py), and a
+// first row is not good enough for that: where it is the odd one out of a flat channel -- the corner pixel of a zero-padded conv is -- every d is
+// large and nearly equal, and sum d^2 - (sum d)^2 / n cancels like E[x^2] - mean^2 does; and fp32 partial sums of nearly equal addends round the
+// same way every time.  So in_reduce_stats takes the group's own mean as c (a pass of its own over rows that sit in the cache) and in_small
+// carries the sum behind its mean in double; both round once, to the fp32 the next stage reads.
 // The normalised tensor overwrites the raw one.
 #include "device_common.h"
 #include "kernels.h"
@@ -29,57 +34,93 @@ __device__ __forceinline__ double shfl_xor_d(double v, int o)
     return __builtin_bit_cast(double, u);
 }
 
-__device__ __forceinline__ float4 fold_row(const InstNormParams &p, size_t e)      // element index of a channel quad: raw value
+// element index of a channel quad -> its raw value.  Split-K partials (+ bias) are summed in double, ascending z, and rounded once: the raw tensor is then within
+// half an ulp of what the slices add up to, whatever their magnitudes -- an fp32 sum of partials of size 1 that cancel to 0.1 is off by ulps of 1, and on a flat
+// channel 1 / sqrt(var + eps) makes that 316x ("Numerics" above)
+__device__ __forceinline__ void fold_exact(const InstNormParams &p, size_t e, float4 bias, double (&a)[4])
 {
-    if (p.splits <= 1) return *reinterpret_cast<const float4 *>(p.x + e);
-    const size_t plane = (size_t)p.B * p.hw * p.C;
-    float4 v = *reinterpret_cast<const float4 *>(p.partial + e);
-    for (int z = 1; z < p.splits; ++z) {                       // ascending z: the order of splitk_reduce
-        const float4 t = *reinterpret_cast<const float4 *>(p.partial + (size_t)z * plane + e);
-        v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
+    if (p.splits <= 1) {
+        const float4 v = *reinterpret_cast<const float4 *>(p.x + e);
+        a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
+        return;
     }
-    return v;
+    const size_t plane = (size_t)p.B * p.hw * p.C;
+    const float4 v = *reinterpret_cast<const float4 *>(p.partial + e);
+    a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
+    for (int z = 1; z < p.splits; ++z) {
+        const float4 t = *reinterpret_cast<const float4 *>(p.partial + (size_t)z * plane + e);
+        a[0] += t.x; a[1] += t.y; a[2] += t.z; a[3] += t.w;
+    }
+    a[0] += bias.x; a[1] += bias.y; a[2] += bias.z; a[3] += bias.w;
+}
+__device__ __forceinline__ float4 fold_row(const InstNormParams &p, size_t e, float4 bias)
+{
+    double a[4];
+    fold_exact(p, e, bias, a);
+    return make_float4((float)a[0], (float)a[1], (float)a[2], (float)a[3]);
 }
 
-// grid (ceil(hw / 64), B), 256 threads: thread = (row lane, channel quad); partial sums of 64 rows per workgroup
+// grid (ceil(hw / 64), B), 256 threads: thread = (row lane, channel quad); partial sums of 64 rows per workgroup.  Two passes over the group's rows (the second
+// one re-reads what this thread has just read): the group's own mean, rounded to fp32, is the shift c, so d = x - c is small whatever the first row
+// holds, and the sums are carried in double and rounded once -- see "Numerics" above.
 __global__ __launch_bounds__(256) void in_reduce_stats(const InstNormParams p)
 {
-    __shared__ float4 red[2][256];
+    __shared__ double red[2][256][4];
     const int cq = p.C >> 2;                                   // channel quads; the launcher guarantees cq <= 256
     const int rl_n = 256 / cq, tid = threadIdx.x;
     const int rl = tid / cq, q = tid - rl * cq;
     const int b = blockIdx.y, row0 = blockIdx.x * 64;
-    float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1, c4 = s1;
+    const int nrows = min(64, p.hw - row0), lanes = min(rl_n, 64);      // row lanes past the 64th hold no row
+    const bool live = rl < rl_n;
     float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p.splits > 1 && p.bias && rl < rl_n) bias = *reinterpret_cast<const float4 *>(p.bias + q * 4);
-    if (rl < rl_n) {
-        c4 = fold_row(p, ((size_t)b * p.hw + row0) * p.C + q * 4);          // the shift: this group's first row (every row lane reads it)
-        if (p.splits > 1) { c4.x += bias.x; c4.y += bias.y; c4.z += bias.z; c4.w += bias.w; }
-        for (int r = rl; r < 64 && row0 + r < p.hw; r += rl_n) {
+    if (p.splits > 1 && p.bias && live) bias = *reinterpret_cast<const float4 *>(p.bias + q * 4);
+    // pass 1: fold the split-K partials (+ bias) into x, sum of the raw values
+    double t[4] = {0.0, 0.0, 0.0, 0.0};
+    if (live) {
+        for (int r = rl; r < nrows; r += rl_n) {
             const size_t e = ((size_t)b * p.hw + row0 + r) * p.C + q * 4;
-            float4 v = fold_row(p, e);
-            if (p.splits > 1) {
-                v.x += bias.x; v.y += bias.y; v.z += bias.z; v.w += bias.w;
-                *reinterpret_cast<float4 *>(p.x + e) = v;
-            }
-            const float4 d = make_float4(v.x - c4.x, v.y - c4.y, v.z - c4.z, v.w - c4.w);
-            s1.x += d.x; s1.y += d.y; s1.z += d.z; s1.w += d.w;
-            s2.x += d.x * d.x; s2.y += d.y * d.y; s2.z += d.z * d.z; s2.w += d.w * d.w;
+            double v[4];
+            fold_exact(p, e, bias, v);
+            if (p.splits > 1) *reinterpret_cast<float4 *>(p.x + e) = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+            t[0] += v[0]; t[1] += v[1]; t[2] += v[2]; t[3] += v[3];
         }
     }
-    red[0][tid] = s1;
-    red[1][tid] = s2;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) red[0][tid][k] = t[k];
+    __syncthreads();
+    float c[4] = {0.f, 0.f, 0.f, 0.f};
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            double a = 0.0;
+            for (int j = 0; j < lanes; ++j) a += red[0][j * cq + q][k];     // fixed order, the same in every row lane of the quad
+            c[k] = (float)(a / nrows);
+        }
+    }
+    __syncthreads();                                           // everyone has read pass 1's sums
+    // pass 2: sums of d = x - c and d^2, of the slices' exact sums where x was folded from them (their second read comes from the cache, like x's): the statistics
+    // are then those of the tensor the conv computed, not of its rounding to fp32 -- which on a channel with |mean| >> std moves the variance by parts in 1e5
+    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+    if (live) {
+        for (int r = rl; r < nrows; r += rl_n) {
+            double v[4];
+            fold_exact(p, ((size_t)b * p.hw + row0 + r) * p.C + q * 4, bias, v);
+            const double d[4] = {v[0] - c[0], v[1] - c[1], v[2] - c[2], v[3] - c[3]};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { s1[k] += d[k]; s2[k] += d[k] * d[k]; }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { red[0][tid][k] = s1[k]; red[1][tid][k] = s2[k]; }
     __syncthreads();
     if (rl == 0) {
-        for (int k = 1; k < rl_n; ++k) {                       // fixed order
-            const float4 a = red[0][k * cq + q], c = red[1][k * cq + q];
-            s1.x += a.x; s1.y += a.y; s1.z += a.z; s1.w += a.w;
-            s2.x += c.x; s2.y += c.y; s2.z += c.z; s2.w += c.w;
-        }
+        for (int j = 1; j < lanes; ++j)                        // fixed order
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { s1[k] += red[0][j * cq + q][k]; s2[k] += red[1][j * cq + q][k]; }
         const size_t g = ((size_t)b * p.groups + blockIdx.x) * p.C + q * 4;
-        *reinterpret_cast<float4 *>(p.psum + g) = s1;
-        *reinterpret_cast<float4 *>(p.psq + g) = s2;
-        *reinterpret_cast<float4 *>(p.pshift + g) = c4;
+        *reinterpret_cast<float4 *>(p.psum + g) = make_float4((float)s1[0], (float)s1[1], (float)s1[2], (float)s1[3]);
+        *reinterpret_cast<float4 *>(p.psq + g) = make_float4((float)s2[0], (float)s2[1], (float)s2[2], (float)s2[3]);
+        *reinterpret_cast<float4 *>(p.pshift + g) = make_float4(c[0], c[1], c[2], c[3]);
     }
 }
 
@@ -178,6 +219,7 @@ template <int R>
 __global__ __launch_bounds__(256) void in_small(const InstNormParams p)
 {
     __shared__ float4 red[1][4][8];
+    __shared__ double redd[4][8][4];
     const int tid = threadIdx.x, q = tid & 7, rl = tid >> 3, wave = tid >> 6;
     const int b = blockIdx.y, c0 = blockIdx.x * 32 + q * 4;
     const bool live = c0 < p.C;                                // C % 32 != 0 cannot happen (ngf % 32 == 0), kept for safety
@@ -195,11 +237,25 @@ __global__ __launch_bounds__(256) void in_small(const InstNormParams p)
 #pragma unroll
         for (int w = 0; w < 4; ++w) { const float4 a = red[0][w][q]; out[0] += a.x; out[1] += a.y; out[2] += a.z; out[3] += a.w; }
     };
+    // the same sum for the mean, carried in double from the first addition: a thread's rows in order, the xor tree, the waves in order.  The mean is then the
+    // correctly rounded one (fp32 partial sums of up to 32 equal values drift by ulps that 1 / sqrt(var + eps) amplifies up to 316x; "Numerics" above)
+    auto block_sum_d = [&](double (&v)[4], double (&out)[4]) {
+#pragma unroll
+        for (int o = 8; o < 64; o <<= 1)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] += shfl_xor_d(v[k], o);
+        if ((tid & 63) < 8)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) redd[wave][q][k] = v[k];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) out[k] = ((redd[0][q][k] + redd[1][q][k]) + redd[2][q][k]) + redd[3][q][k];
+    };
     constexpr int RR = R > 0 ? R : 1;
     constexpr bool PRE_RES = R > 0 && R <= 8;                  // the residual rows are requested with the tensor's own (registers allow it up to 8 rows per thread)
     float4 row[RR], resv[PRE_RES ? RR : 1];
     // pass 1: fold the split-K partials (+ bias), mean
-    float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    double s1[4] = {0.0, 0.0, 0.0, 0.0};
     if (live) {
         if constexpr (R > 0) {
 #pragma unroll
@@ -208,31 +264,27 @@ __global__ __launch_bounds__(256) void in_small(const InstNormParams p)
                 row[i] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (r < p.hw) {
                     const size_t e = ((size_t)b * p.hw + r) * p.C + c0;
-                    row[i] = fold_row(p, e);
+                    row[i] = fold_row(p, e, bias);
                     if constexpr (PRE_RES) resv[i] = p.residual ? *reinterpret_cast<const float4 *>(p.residual + e) : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
             }
 #pragma unroll
             for (int i = 0; i < R; ++i)
                 if (rl + 32 * i < p.hw) {
-                    float4 &v = row[i];
-                    if (p.splits > 1) { v.x += bias.x; v.y += bias.y; v.z += bias.z; v.w += bias.w; }
-                    s1.x += v.x; s1.y += v.y; s1.z += v.z; s1.w += v.w;
+                    const float4 v = row[i];
+                    s1[0] += v.x; s1[1] += v.y; s1[2] += v.z; s1[3] += v.w;
                 }
         } else {
             for (int r = rl; r < p.hw; r += 32) {
                 const size_t e = ((size_t)b * p.hw + r) * p.C + c0;
-                float4 v = fold_row(p, e);
-                if (p.splits > 1) {
-                    v.x += bias.x; v.y += bias.y; v.z += bias.z; v.w += bias.w;
-                    *reinterpret_cast<float4 *>(p.x + e) = v;      // re-read below by the SAME thread
-                }
-                s1.x += v.x; s1.y += v.y; s1.z += v.z; s1.w += v.w;
+                const float4 v = fold_row(p, e, bias);
+                if (p.splits > 1) *reinterpret_cast<float4 *>(p.x + e) = v;      // re-read below by the SAME thread
+                s1[0] += v.x; s1[1] += v.y; s1[2] += v.z; s1[3] += v.w;
             }
         }
     }
     double sum[4];
-    block_sum(s1, sum);
+    block_sum_d(s1, sum);
     const float4 m4 = make_float4((float)(sum[0] / p.hw), (float)(sum[1] / p.hw), (float)(sum[2] / p.hw), (float)(sum[3] / p.hw));
     // pass 2: sum of squared deviations from that mean (two-pass variance: no cancellation)
     float4 s2 = make_float4(0.f, 0.f, 0.f, 0.f);

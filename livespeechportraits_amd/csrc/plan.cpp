@@ -587,8 +587,8 @@ BatchLayout layout_for(const Plan &p, int batch, std::vector<size_t> *offsets, s
                 // rows of one wave (32 per 32x32 tile row, bm / 2 waves... = bm / 2 for the 2x2-wave tiles) must stay inside one
                 // frame for the epilogue sums; tiny levels do statistics + normalisation in one workgroup per channel slab
                 const int hw = l.ho * l.ho, rhw = l.up4 ? l.hs * l.hs : hw;
-                const int wave_rows = bm == 32 ? 32 : bm / 2;
-                if (!smallm && !fullk && !wino && !wino4 && !winoup && splits == 1 && rhw >= 1024 && rhw % wave_rows == 0) {
+                const int wave_rows = in_fused_wave_rows(bm);
+                if (!smallm && !fullk && !wino && !wino4 && !winoup && in_fused_eligible(bm, splits, rhw)) {
                     route = kInFused;
                     groups_max = std::max(groups_max, (l.up4 ? 4 : 1) * rhw / wave_rows);
                 } else if ((wino || winoup) && !wino4 && p.in_wino_stats) {

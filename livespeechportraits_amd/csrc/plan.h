@@ -178,6 +178,12 @@ struct Plan {
 
 // tile / split-K heuristic shared by the planner and lspf2f_conv3x3
 void choose_tiling(int M, int N, int ktiles, int par, bool up9, int dtype, int *bm, int *bn, int *splits, int *group);
+// InstanceNorm plans, implicit GEMM with epilogue sums (kInFused): the rows behind one wave's sums (32 per 32x32 tile row; bm / 2 for the
+// 2x2-wave tiles) and the rule that lets a layer take that route -- a wave's rows must stay inside one frame, and the tiny levels do
+// statistics + normalisation in one workgroup per channel slab instead.  rhw = pixels per frame of the GEMM's M space (the LOW-res frame of a
+// sub-pixel up-conv).  Shared by the planner and lspf2f_conv3x3_instnorm.
+inline int in_fused_wave_rows(int bm) { return bm == 32 ? 32 : bm / 2; }
+inline bool in_fused_eligible(int bm, int splits, int rhw) { return splits == 1 && rhw >= 1024 && rhw % in_fused_wave_rows(bm) == 0; }
 // tiny-M kernel eligibility (mirrors smallm_supported() in small_layers.hip)
 inline bool smallm_eligible(int M, int cin, int c1, int cout, size_t in_bytes, int max_kb = 64)
 {
