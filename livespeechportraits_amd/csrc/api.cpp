@@ -310,35 +310,38 @@ int lspf2f_plan_batch(lspf2f_handle *h, int batch)
 
 static const char *kernel_name(const LayerDesc &l, const Plan &P)
 {
-    switch (l.kind) {
-    case kFirstConv: return "first_conv";
-    case kLastConv: return l.wgemm_off >= 0 ? (l.wrl_off >= 0 && P.use_rowlast ? "last_conv (rowlast128 + pixel_shuffle_tanh)" : "last_conv (igemm3x3 + pixel_shuffle_tanh)") : "last_conv";
-    default:
-        if (l.wino4) return l.inorm ? (l.in_route == kInSmall ? "wino4_3x3+in_small" : "wino4_3x3+in_reduce_stats+in_finalize+in_apply")
-                                    : (l.splits > 1 ? "wino4_3x3 (split-K combined in the launch)" : "wino4_3x3");
-        if (l.inorm && (l.wino || l.winoup)) {
-            const bool sm = l.in_route == kInSmall;
-            if (l.winoup && l.in_route == kInWino) return l.winoup == 2 ? "winoup3x3<2>(stats)+in_finalize+in_apply" : "winoup3x3<1>(stats)+in_finalize+in_apply";
-            if (l.winoup) return l.winoup == 2 ? (sm ? "winoup3x3<2>+in_small" : "winoup3x3<2>+in_reduce_stats+in_finalize+in_apply")
-                                               : (sm ? "winoup3x3<1>+in_small" : "winoup3x3<1>+in_reduce_stats+in_finalize+in_apply");
-            if (l.in_route == kInWino) return l.wino == 2 ? "wino3x3<2>(stats)+in_finalize+in_apply" : "wino3x3<1>(stats)+in_finalize+in_apply";
-            return l.wino == 2 ? (sm ? "wino3x3<2>+in_small" : "wino3x3<2>+in_reduce_stats+in_finalize+in_apply")
-                               : (sm ? "wino3x3<1>+in_small" : "wino3x3<1>+in_reduce_stats+in_finalize+in_apply");
-        }
-        if (l.winoup) return l.winoup == 2 ? (l.splits > 1 ? "winoup3x3<2> (split-K combined in the launch)" : "winoup3x3<2>")
-                                           : (l.splits > 1 ? "winoup3x3<1> (split-K combined in the launch)" : "winoup3x3<1>");
-        if (l.wino) return l.wino == 2 ? (l.splits > 1 ? "wino3x3<2> (split-K combined in the launch)" : "wino3x3<2>")
-                                       : (l.splits > 1 ? "wino3x3<1> (split-K combined in the launch)" : "wino3x3<1>");
-        if (l.inorm && l.fullk) return "conv3x3_fullk+in_small";
-        if (l.fullk) return P.dtype ? "conv3x3_fullk16" : "conv3x3_fullk";
-        if (l.rowup) return "rowup256";
-        if (l.patch16) return l.up4 ? "conv3x3_patchup16" : "conv3x3_patch16";
-        if (l.bandconv) return "bandconv512";
-        if (l.rowconv) return l.c0 == 64 ? "rowconv64" : "rowconv128";
-        if (l.inorm) return l.smallm ? (P.in_smallm_fused ? "conv3x3_smallm(in)" : "conv3x3_smallm+in_small") : l.in_route == kInFused ? "igemm3x3(stats)+in_finalize+in_apply"
-                          : l.in_route == kInSmall ? "igemm3x3+in_small" : "igemm3x3+in_reduce_stats+in_finalize+in_apply";
-        return l.smallm ? "conv3x3_smallm" : (l.splits > 1 ? (l.fused_splitk ? "igemm3x3 (split-K combined in the launch)" : "igemm3x3+splitk_reduce") : "igemm3x3");
+    if (l.kind == kFirstConv) return "first_conv";
+    if (l.kind == kLastConv)
+        return l.form_off[kFormGemmLast] < 0 ? "last_conv"
+               : l.form_off[kFormRowLast] >= 0 && P.use_rowlast ? "last_conv (rowlast128 + pixel_shuffle_tanh)" : "last_conv (igemm3x3 + pixel_shuffle_tanh)";
+    const bool two = l.route_arg == 2, split = l.splits > 1, small = l.in_route == kInSmall, stats = l.in_route == kInWino;
+    switch (l.route) {
+    case kRouteSmallM: return !l.inorm ? "conv3x3_smallm" : P.in_smallm_fused ? "conv3x3_smallm(in)" : "conv3x3_smallm+in_small";
+    case kRouteWinoUp:
+        if (!l.inorm) return two ? (split ? "winoup3x3<2> (split-K combined in the launch)" : "winoup3x3<2>") : (split ? "winoup3x3<1> (split-K combined in the launch)" : "winoup3x3<1>");
+        if (stats) return two ? "winoup3x3<2>(stats)+in_finalize+in_apply" : "winoup3x3<1>(stats)+in_finalize+in_apply";
+        return two ? (small ? "winoup3x3<2>+in_small" : "winoup3x3<2>+in_reduce_stats+in_finalize+in_apply")
+                   : (small ? "winoup3x3<1>+in_small" : "winoup3x3<1>+in_reduce_stats+in_finalize+in_apply");
+    case kRouteWino4:
+        if (!l.inorm) return split ? "wino4_3x3 (split-K combined in the launch)" : "wino4_3x3";
+        return small ? "wino4_3x3+in_small" : "wino4_3x3+in_reduce_stats+in_finalize+in_apply";
+    case kRouteWino:
+        if (!l.inorm) return two ? (split ? "wino3x3<2> (split-K combined in the launch)" : "wino3x3<2>") : (split ? "wino3x3<1> (split-K combined in the launch)" : "wino3x3<1>");
+        if (stats) return two ? "wino3x3<2>(stats)+in_finalize+in_apply" : "wino3x3<1>(stats)+in_finalize+in_apply";
+        return two ? (small ? "wino3x3<2>+in_small" : "wino3x3<2>+in_reduce_stats+in_finalize+in_apply")
+                   : (small ? "wino3x3<1>+in_small" : "wino3x3<1>+in_reduce_stats+in_finalize+in_apply");
+    case kRouteRowUp: return "rowup256";
+    case kRoutePatchUp16: return "conv3x3_patchup16";
+    case kRoutePatch16: return "conv3x3_patch16";
+    case kRouteBand: return "bandconv512";
+    case kRouteRowConv: return l.c0 == 64 ? "rowconv64" : "rowconv128";
+    case kRouteFullK16: return "conv3x3_fullk16";
+    case kRouteFullK: return l.inorm ? "conv3x3_fullk+in_small" : "conv3x3_fullk";
+    case kRouteIgemm:
+        if (l.inorm) return l.in_route == kInFused ? "igemm3x3(stats)+in_finalize+in_apply" : small ? "igemm3x3+in_small" : "igemm3x3+in_reduce_stats+in_finalize+in_apply";
+        return !split ? "igemm3x3" : l.fused_splitk ? "igemm3x3 (split-K combined in the launch)" : "igemm3x3+splitk_reduce";
     }
+    return "";
 }
 
 int lspf2f_layer_info_get(const lspf2f_handle *h, int i, lspf2f_layer_info *o)
@@ -352,22 +355,14 @@ int lspf2f_layer_info_get(const lspf2f_handle *h, int i, lspf2f_layer_info *o)
     o->tile_m = l.bm; o->tile_n = l.bn; o->split_k = l.splits; o->k_group = l.group;
     o->flops_per_frame = h->plan.layer_flops(l);
     o->act_bytes_per_frame = h->plan.layer_act_bytes(l);
-    const bool sub = l.up4 || l.kind == kLastConv;   // sub-pixel form: 16/9 weight bytes, 4/9 FLOPs
-    o->weight_bytes = (int64_t)l.cout * l.cin * (sub ? 16 : 9) * (int64_t)(h->plan.layer_weights_typed(l) ? h->plan.elt() : 4);
-    o->exec_flops_per_frame = sub ? o->flops_per_frame * 4 / 9 : o->flops_per_frame;
-    if (l.winoup) {     // up-conv Winograd form: 9 multiplies per 2x2 outputs instead of 36 (16 in the sub-pixel form); 9 transformed taps per (co, ci)
-        o->exec_flops_per_frame = o->flops_per_frame / 4;
-        o->weight_bytes = (int64_t)l.cout * l.cin * 9 * 4;
-    }
-    if (l.wino) {       // Winograd F(2x2, 3x3): 16 multiplies per 2x2 outputs instead of 36; the weights it reads are the 4x4 transformed ones
-        o->exec_flops_per_frame = o->flops_per_frame * 4 / 9;
-        o->weight_bytes = (int64_t)l.cout * l.cin * 16 * 4;
-    }
-    if (l.wino4) {      // Winograd F(4x4, 3x3): 36 multiplies per 4x4 outputs instead of 144; 36 transformed taps per (co, ci)
-        o->exec_flops_per_frame = o->flops_per_frame / 4;
-        o->weight_bytes = (int64_t)l.cout * l.cin * 36 * 4;
-    }
-    o->w_offset = l.w_off; o->scale_offset = l.scale_off; o->shift_offset = l.shift_off;
+    // what the layer's kernel reads and multiplies: the sub-pixel form does 16 multiplies per 2x2 outputs instead of 36, the up-conv Winograd form 9,
+    // Winograd F(2x2, 3x3) 16, F(4x4, 3x3) 36 per 4x4 outputs instead of 144 (first / last conv: their rows, whatever the last conv's route)
+    const bool body = l.kind == kIgemm;
+    o->weight_bytes = (int64_t)h->plan.form_bytes(l, body ? route_form(l) : kFormRows);
+    const bool quarter = body && (l.route == kRouteWinoUp || l.route == kRouteWino4);
+    const bool four_ninths = l.up4 || l.kind == kLastConv || (body && l.route == kRouteWino);
+    o->exec_flops_per_frame = quarter ? o->flops_per_frame / 4 : four_ninths ? o->flops_per_frame * 4 / 9 : o->flops_per_frame;
+    o->w_offset = l.form_off[kFormRows]; o->scale_offset = l.scale_off; o->shift_offset = l.shift_off;
     o->out_offset = l.out >= 0 ? (int64_t)h->plan.tensors[l.out].offset : -1;
     return LSPF2F_OK;
 }
@@ -394,22 +389,8 @@ int lspf2f_pixel_shuffle(const float *g_dev, int batch, int hs, int ws, int cout
 
 int64_t lspf2f_layer_form_offset(const lspf2f_handle *h, int layer, int form)
 {
-    if (!h || layer < 0 || layer >= (int)h->plan.layers.size()) return -1;
-    const LayerDesc &l = h->plan.layers[layer];
-    switch (form) {
-    case 0: return l.w_off;
-    case 1: return l.wfk_off;
-    case 2: return l.wfk2_off;
-    case 3: return l.wwg_off;
-    case 4: return l.ww4_off;
-    case 5: return l.wwu_off;
-    case 6: return l.wru_off;
-    case 7: return l.wbc_off;
-    case 8: return l.wrc_off;
-    case 9: return l.wgemm_off;
-    case 10: return l.wrl_off;
-    default: return -1;
-    }
+    if (!h || layer < 0 || layer >= (int)h->plan.layers.size() || form < 0 || form >= kNumForms) return -1;
+    return h->plan.layers[layer].form_off[form];
 }
 
 int lspf2f_memcpy(void *dst, const void *src, size_t bytes, void *hip_stream)
@@ -467,21 +448,41 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
     auto tptr = [&](int t) -> float * { return t < 0 ? nullptr : reinterpret_cast<float *>(h->ws + P.tensors[t].offset); };
     auto bptr = [&](int64_t off) -> const float * { return off < 0 ? nullptr : reinterpret_cast<const float *>(h->blob + off); };
     hipError_t e = hipSuccess;
-    // InstanceNorm behind a kernel that has written the complete raw conv output (+ bias) itself (the Winograd kernels: their split-K slabs are
-    // combined in the launch): statistics + normalisation (+ residual, ReLU) as separate passes over that tensor
-    auto in_after_complete_output = [&](hipError_t prev) -> hipError_t {
-        if (prev != hipSuccess) return prev;
-        float *st = reinterpret_cast<float *>(h->ws + P.stats_offset);
-        const size_t slab = (size_t)batch * P.stats_groups_max;
+    // InstanceNorm plans: the normalisation of this layer's output (+ residual, ReLU), and the statistics scratch
+    float *const st = reinterpret_cast<float *>(h->ws + P.stats_offset);
+    const size_t slab = (size_t)batch * P.stats_groups_max;            // [B][groups][C] with C <= the plan's widest layer
+    auto in_of_output = [&]() {
         InstNormParams q{};
-            q.three_pass = h->in_small_regs ? 0 : 1;
+        q.three_pass = h->in_small_regs ? 0 : 1;
         q.x = tptr(l.out); q.residual = tptr(l.res); q.relu = l.relu; q.partial = nullptr; q.splits = 1; q.bias = nullptr;
         q.B = batch; q.hw = l.ho * l.ho; q.C = l.cout;
-        return in_standalone(q, l.in_route == kInSmall, st, slab, s);
+        return q;
     };
+    // ... behind a kernel that has written the complete raw conv output (+ bias) itself (the Winograd kernels combine their split-K slabs in the launch; the
+    // tiny-M and full-K kernels have none): statistics + normalisation as separate passes over that tensor -- one launch (`small`), or reduce, finalize, apply
+    auto in_after_complete_output = [&](hipError_t prev, bool small) -> hipError_t {
+        if (prev != hipSuccess) return prev;
+        InstNormParams q = in_of_output();
+        return in_standalone(q, small, st, slab, s);
+    };
+    // ... around a Winograd kernel (`launch` runs it on `p`).  kInWino: its epilogue (or its split-K combine) leaves the sums of every tile-block of 128 output
+    // pixels at the pointers bound here, so only finalize + normalise follow; otherwise the passes above
+    auto wino_with_in = [&](auto &p, auto &&launch) -> hipError_t {
+        if (!l.inorm) return launch();
+        if (l.in_route != kInWino) return in_after_complete_output(launch(), l.in_route == kInSmall);
+        InstNormParams q = in_of_output();
+        in_bind_stats(q, st, slab);
+        in_groups_wino(q);
+        p.psum = q.psum; p.psq = q.psq; p.pshift = q.pshift;
+        const hipError_t r = launch();
+        return r == hipSuccess ? in_finalize_apply(q, s) : r;
+    };
+    // the blob address of the form this layer's route reads
+    const float *const w = l.kind == kIgemm ? bptr(l.form_off[route_form(l)]) : nullptr;
+    const bool main_part = (h->timing_part & 1) != 0;      // lspf2f_subset_timed may leave the main kernel out
     if (l.kind == kFirstConv) {
         FirstConvParams p{};
-        p.feat = feat; p.cand = cand; p.w = bptr(l.w_off); p.out = tptr(l.out);
+        p.feat = feat; p.cand = cand; p.w = bptr(l.form_off[kFormRows]); p.out = tptr(l.out);
         p.B = batch; p.H = l.hs; p.W = l.hs; p.feat_nc = P.feat_nc; p.cand_nc = P.input_nc - P.feat_nc;
         p.cand_batch = cand_batch; p.Cout = l.cout; p.dtype = P.dtype;
         p.ci_begin = 0; p.ci_end = P.input_nc; p.base = nullptr; p.relu = 1;
@@ -513,9 +514,9 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
         }
     } else if (l.kind == kLastConv && P.last_as_gemm(l) && !h->last_direct) {
         // bf16: 3x3 conv on the low-res source with N = 4 parities x cout through the MFMA kernel, then shuffle + tanh
-        if (l.wrl_off >= 0 && P.use_rowlast) {
+        if (l.form_off[kFormRowLast] >= 0 && P.use_rowlast) {
             RowLastParams q{};
-            q.src0 = tptr(l.src0); q.src1 = tptr(l.src1); q.w = h->blob + l.wrl_off;
+            q.src0 = tptr(l.src0); q.src1 = tptr(l.src1); q.w = h->blob + l.form_off[kFormRowLast];
             q.out = reinterpret_cast<float *>(h->ws + P.partial_offset);
             q.B = batch; q.H = l.hs; q.W = l.hs; q.R = rowlast_rows(batch, l.hs, l.hs); q.dtype = P.dtype;
             // fp32 frames only: shuffle + tanh in the kernel's epilogue (no intermediate, no second launch); uint8 rows (tensor2im) keep the two-launch form
@@ -530,7 +531,7 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
             return LSPF2F_OK;
         }
         IgemmParams g{};
-        g.src0 = tptr(l.src0); g.src1 = tptr(l.src1); g.w = h->blob + l.wgemm_off;
+        g.src0 = tptr(l.src0); g.src1 = tptr(l.src1); g.w = h->blob + l.form_off[kFormGemmLast];
         g.out = h->ws + P.partial_offset; g.out_f32 = 1;
         g.B = batch; g.Hs = l.hs; g.Ws = l.hs; g.Ho = l.hs; g.Wo = l.hs;
         g.C0 = l.c0; g.C1 = l.c1; g.Cin = l.cin; g.Cout = 4 * l.cout;
@@ -543,14 +544,15 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
         }
     } else if (l.kind == kLastConv) {
         LastConvParams p{};
-        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = bptr(l.w_off); p.out = out;
+        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = bptr(l.form_off[kFormRows]); p.out = out;
         p.B = batch; p.Hs = l.hs; p.Ws = l.hs; p.C0 = l.c0; p.C1 = l.c1; p.Cout = l.cout; p.apply_tanh = l.tanh_out; p.out_u8 = out_u8; p.dtype = P.dtype;
         p.route = h->last_route;
         p.bias = bptr(l.shift_off);
         e = launch_last_conv(p, s);
-    } else if (l.smallm) {
+    } else switch (l.route) {
+    case kRouteSmallM: {
         SmallMParams p{};
-        p.src = tptr(l.src0); p.w = bptr(l.w_off); p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
+        p.src = tptr(l.src0); p.w = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
         const bool in_fused = l.inorm && P.in_smallm_fused;      // InstanceNorm plans: the workgroup holds every pixel of its channels -> normalisation in the epilogue
         p.residual = (l.inorm && !in_fused) ? nullptr : tptr(l.res); p.out = tptr(l.out);
         p.B = batch; p.Hs = l.hs; p.Ws = l.hs; p.Ho = l.ho; p.Wo = l.ho; p.Cin = l.cin; p.Cout = l.cout;
@@ -558,25 +560,21 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
         p.in_fused = in_fused ? 1 : 0;
         p.stage_regs = h->smallm_dma ? 0 : 1;
         if (h->prefetch && P.dtype == 0 && !l.inorm) {
-            // the next launch, if it is another weight-streaming layer: its weights are requested from inside this one
+            // the next launch, if it is another weight-streaming layer: its weights (in the form its route reads) are requested from inside this one
             const size_t li = (size_t)(&l - P.layers.data());
             if (li + 1 < P.layers.size()) {
                 const LayerDesc &n = P.layers[li + 1];
-                const int64_t off = n.smallm ? n.w_off : n.fullk ? ((n.splits == 2 && !n.c1) ? n.wfk2_off : n.wfk_off) : -1;
-                if (off >= 0 && n.kind == kIgemm) { p.pf = h->blob + off; p.pf_bytes = (unsigned)((size_t)n.cout * 9 * n.cin * sizeof(float)); }
+                const int64_t off = n.kind == kIgemm && (n.route == kRouteSmallM || n.route == kRouteFullK) ? n.form_off[route_form(n)] : -1;
+                if (off >= 0) { p.pf = h->blob + off; p.pf_bytes = (unsigned)((size_t)n.cout * 9 * n.cin * sizeof(float)); }
             }
         }
         e = launch_smallm(p, s);
-        if (e == hipSuccess && l.inorm && !in_fused) {          // raw conv output (+ bias) -> statistics + normalisation (+ residual, ReLU) in one launch
-            InstNormParams q{};
-            q.three_pass = h->in_small_regs ? 0 : 1;
-            q.x = tptr(l.out); q.partial = nullptr; q.splits = 1; q.bias = nullptr; q.residual = tptr(l.res); q.relu = l.relu;
-            q.B = batch; q.hw = l.ho * l.ho; q.C = l.cout;
-            e = launch_in_small(q, s);
-        }
-    } else if (l.winoup) {
+        if (l.inorm && !in_fused) e = in_after_complete_output(e, true);          // raw conv output (+ bias) -> statistics + normalisation (+ residual, ReLU) in one launch
+        break;
+    }
+    case kRouteWinoUp: {
         WinoUpParams p{};
-        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.u = bptr(l.wwu_off); p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
+        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.u = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
         p.out = tptr(l.out);
         p.B = batch; p.Hs = l.hs; p.Ws = l.hs; p.C0 = l.c0; p.C1 = l.c1; p.N = l.cout; p.relu = l.inorm ? 0 : l.relu; p.splits = l.splits;
         p.out_wt = P.out_wt; p.prio = P.wino_prio;
@@ -584,122 +582,95 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
             p.partial = reinterpret_cast<float *>(h->ws + P.partial_offset);
             p.tile_cnt = reinterpret_cast<unsigned *>(h->ws + P.counters_offset());
         }
-        if (l.inorm && l.in_route == kInWino) {
-            // the kernel's epilogue (or its split-K combine) leaves the sums of every tile-block of 128 output pixels: finalize + normalise only
-            float *st = reinterpret_cast<float *>(h->ws + P.stats_offset);
-            const size_t slab = (size_t)batch * P.stats_groups_max;
-            InstNormParams q{};
-            q.three_pass = h->in_small_regs ? 0 : 1;
-            q.x = tptr(l.out); q.residual = tptr(l.res); q.relu = l.relu; q.partial = nullptr; q.splits = 1; q.bias = nullptr;
-            q.B = batch; q.hw = l.ho * l.ho; q.C = l.cout;
-            in_bind_stats(q, st, slab);
-            in_groups_wino(q);
-            p.psum = q.psum; p.psq = q.psq; p.pshift = q.pshift;
-            if (h->timing_part & 1) e = launch_winoup(p, l.winoup, s);
-            if (e == hipSuccess) e = in_finalize_apply(q, s);
-        } else {
-            if (h->timing_part & 1) e = launch_winoup(p, l.winoup, s);
-            if (l.inorm) e = in_after_complete_output(e);
-        }
-    } else if (l.wino4) {
+        e = wino_with_in(p, [&] { return main_part ? launch_winoup(p, l.route_arg, s) : hipSuccess; });
+        break;
+    }
+    case kRouteWino4:
+    case kRouteWino: {
         WinoParams p{};
-        p.src = tptr(l.src0); p.u = bptr(l.ww4_off); p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
+        p.src = tptr(l.src0); p.u = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
         p.residual = l.inorm ? nullptr : tptr(l.res); p.out = tptr(l.out);
         p.B = batch; p.H = l.ho; p.W = l.ho; p.C = l.cin; p.N = l.cout; p.relu = l.inorm ? 0 : l.relu; p.splits = l.splits;
         if (l.splits > 1) {
             p.partial = reinterpret_cast<float *>(h->ws + P.partial_offset);
             p.tile_cnt = reinterpret_cast<unsigned *>(h->ws + P.counters_offset());
         }
-        if (h->timing_part & 1) e = launch_wino4(p, s);
-        if (l.inorm) e = in_after_complete_output(e);
-    } else if (l.wino) {
-        WinoParams p{};
-        p.src = tptr(l.src0); p.u = bptr(l.wwg_off); p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
-        p.residual = l.inorm ? nullptr : tptr(l.res); p.out = tptr(l.out);
-        p.B = batch; p.H = l.ho; p.W = l.ho; p.C = l.cin; p.N = l.cout; p.relu = l.inorm ? 0 : l.relu; p.splits = l.splits;
-        if (l.splits > 1) {
-            p.partial = reinterpret_cast<float *>(h->ws + P.partial_offset);
-            p.tile_cnt = reinterpret_cast<unsigned *>(h->ws + P.counters_offset());
+        if (l.route == kRouteWino4) {          // (never kInWino: F(4x4,3x3) leaves no epilogue sums)
+            e = wino_with_in(p, [&] { return main_part ? launch_wino4(p, s) : hipSuccess; });
+            break;
         }
         p.nopre = P.wino_pre ? 0 : 1; p.xcd_force = P.wino_xcd + 1; p.no_il = P.wino_il ? 0 : 1; p.no_rot = P.wino_rot ? 0 : 1; p.ureg = P.wino_ureg; p.out_wt = P.out_wt; p.prio = P.wino_prio;
-        if (l.inorm && l.in_route == kInWino) {
-            // the kernel's epilogue (or its split-K combine) leaves the sums of every tile-block of 128 pixels: finalize + normalise only
-            float *st = reinterpret_cast<float *>(h->ws + P.stats_offset);
-            const size_t slab = (size_t)batch * P.stats_groups_max;
-            InstNormParams q{};
-            q.three_pass = h->in_small_regs ? 0 : 1;
-            q.x = tptr(l.out); q.residual = tptr(l.res); q.relu = l.relu; q.partial = nullptr; q.splits = 1; q.bias = nullptr;
-            q.B = batch; q.hw = l.ho * l.ho; q.C = l.cout;
-            in_bind_stats(q, st, slab);
-            in_groups_wino(q);
-            p.psum = q.psum; p.psq = q.psq; p.pshift = q.pshift;
-            if (h->timing_part & 1) e = launch_wino(p, l.wino, s);
-            if (e == hipSuccess) e = in_finalize_apply(q, s);
-        } else {
-            if (h->timing_part & 1) e = launch_wino(p, l.wino, s);
-            if (l.inorm) e = in_after_complete_output(e);
-        }
-    } else if (l.rowup) {
+        e = wino_with_in(p, [&] { return main_part ? launch_wino(p, l.route_arg, s) : hipSuccess; });
+        break;
+    }
+    case kRouteRowUp: {
         RowUpParams p{};
-        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = bptr(l.wru_off); p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
+        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
         p.out = tptr(l.out);
-        p.B = batch; p.H = l.hs; p.W = l.hs; p.R = l.rowup; p.relu = l.relu; p.dtype = P.dtype;
+        p.B = batch; p.H = l.hs; p.W = l.hs; p.R = l.route_arg; p.relu = l.relu; p.dtype = P.dtype;
         e = launch_rowup(p, s);
-    } else if (l.patch16 && l.up4) {
+        break;
+    }
+    case kRoutePatchUp16: {
         PatchConvParams p{};
-        p.src = tptr(l.src0); p.src1 = tptr(l.src1); p.w = bptr(l.w_off); p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
+        p.src = tptr(l.src0); p.src1 = tptr(l.src1); p.w = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
         p.residual = tptr(l.res); p.out = tptr(l.out);
         p.B = batch; p.H = l.hs; p.W = l.hs; p.C = l.c0; p.C1 = l.c1; p.Cout = l.cout; p.relu = l.relu; p.dtype = P.dtype;
-        e = launch_patchup16(p, l.patch16, l.bn, s);
-    } else if (l.patch16) {
+        e = launch_patchup16(p, l.route_arg, l.bn, s);
+        break;
+    }
+    case kRoutePatch16: {
         PatchConvParams p{};
-        p.src = tptr(l.src0); p.w = bptr(l.w_off); p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
+        p.src = tptr(l.src0); p.w = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
         p.residual = tptr(l.res); p.out = tptr(l.out);
         p.B = batch; p.H = l.ho; p.W = l.ho; p.C = l.c0; p.Cout = l.cout; p.relu = l.relu; p.dtype = P.dtype;
         p.deep = P.patch16_deep;
-        e = launch_patch16(p, l.patch16, l.bn, s);
-    } else if (l.bandconv) {
+        e = launch_patch16(p, l.route_arg, l.bn, s);
+        break;
+    }
+    case kRouteBand: {
         BandConvParams p{};
-        p.src = tptr(l.src0); p.w = bptr(l.wbc_off); p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
+        p.src = tptr(l.src0); p.w = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
         p.residual = tptr(l.res); p.out = tptr(l.out);
         p.B = batch; p.W = l.ho; p.Cout = l.cout; p.relu = l.relu; p.dtype = P.dtype;
         e = launch_bandconv(p, s);
-    } else if (l.rowconv) {
+        break;
+    }
+    case kRouteRowConv: {
         RowConvParams p{};
-        p.src = tptr(l.src0); p.w = bptr(l.wrc_off); p.wfrag = 1; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
+        p.src = tptr(l.src0); p.w = w; p.wfrag = 1; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
         p.residual = tptr(l.res); p.out = tptr(l.out);
-        p.B = batch; p.H = l.ho; p.W = l.ho; p.C = l.c0; p.R = l.rowconv; p.relu = l.relu; p.dtype = P.dtype;
+        p.B = batch; p.H = l.ho; p.W = l.ho; p.C = l.c0; p.R = l.route_arg; p.relu = l.relu; p.dtype = P.dtype;
         e = launch_rowconv(p, s);
-    } else if (l.fullk && P.dtype != 0) {
+        break;
+    }
+    case kRouteFullK16: {
         FullK16Params p{};
-        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = bptr(l.wfk_off); p.wtile = 1; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
+        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = w; p.wtile = 1; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
         p.residual = tptr(l.res); p.out = tptr(l.out);
         p.B = batch; p.Hs = l.hs; p.Ws = l.hs; p.Ho = l.ho; p.Wo = l.ho; p.C0 = l.c0; p.C1 = l.c1; p.Cout = l.cout;
         p.up = l.up; p.relu = l.relu; p.stride = l.stride; p.dtype = P.dtype;
-        e = launch_fullk16(p, l.fullk, s);
-    } else if (l.fullk) {
+        e = launch_fullk16(p, l.route_arg, s);
+        break;
+    }
+    case kRouteFullK: {
         FullKParams p{};
-        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = bptr(l.wfk_off); p.wtile = 1; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
+        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = w; p.wtile = 1; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
         p.residual = l.inorm ? nullptr : tptr(l.res); p.out = tptr(l.out);
         p.B = batch; p.Hs = l.hs; p.Ws = l.hs; p.Ho = l.ho; p.Wo = l.ho; p.C0 = l.c0; p.C1 = l.c1; p.Cout = l.cout;
         p.up = l.up; p.relu = l.inorm ? 0 : l.relu; p.stride = l.stride;
-        if (l.splits == 2) {                       // K in two halves, combined in the launch
+        if (l.splits == 2) {                       // K in two halves, combined in the launch (a single source read as two half-sources: route_form)
             p.split = 2;
-            if (!l.c1) p.w = bptr(l.wfk2_off);     // a single source read as two half-sources
             p.partial = reinterpret_cast<float *>(h->ws + P.partial_offset);
             p.tile_cnt = reinterpret_cast<unsigned *>(h->ws + P.counters_offset());
         }
-        e = launch_fullk(p, l.fullk, s);
-        if (e == hipSuccess && l.inorm) {          // InstanceNorm plans: H*W <= 256 here, the one-launch statistics route
-            InstNormParams q{};
-            q.three_pass = h->in_small_regs ? 0 : 1;
-            q.x = tptr(l.out); q.partial = nullptr; q.splits = 1; q.bias = nullptr; q.residual = tptr(l.res); q.relu = l.relu;
-            q.B = batch; q.hw = l.ho * l.ho; q.C = l.cout;
-            e = launch_in_small(q, s);
-        }
-    } else {
+        e = launch_fullk(p, l.route_arg, s);
+        if (l.inorm) e = in_after_complete_output(e, true);          // InstanceNorm plans: H*W <= 256 here, the one-launch statistics route
+        break;
+    }
+    case kRouteIgemm: {
         IgemmParams p{};
-        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = bptr(l.w_off);
+        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = w;
         p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
         p.residual = tptr(l.res); p.out = tptr(l.out);
         p.partial = reinterpret_cast<float *>(h->ws + P.partial_offset);
@@ -715,12 +686,7 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
         p.ktiles_per_split = (p.ktiles_total + l.splits - 1) / l.splits;
         if (l.inorm) {
             // InstanceNorm follows: the conv writes its raw output (+ bias); residual add and ReLU move behind the normalisation
-            float *st = reinterpret_cast<float *>(h->ws + P.stats_offset);
-            const size_t slab = (size_t)batch * P.stats_groups_max;            // [B][groups][C] with C <= the plan's widest layer
-            InstNormParams q{};
-            q.three_pass = h->in_small_regs ? 0 : 1;
-            q.x = tptr(l.out); q.residual = tptr(l.res); q.relu = l.relu;
-            q.B = batch; q.hw = l.ho * l.ho; q.C = l.cout;
+            InstNormParams q = in_of_output();
             p.residual = nullptr; p.relu = 0;
             if (l.in_route == kInFused) {
                 in_bind_stats(q, st, slab);
@@ -742,9 +708,11 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
                 p.slab_bytes = (size_t)l.splits * p.Mout * l.cout * sizeof(float);
             }
             p.xcd_force = P.igemm_xcd + 1;
-            if (h->timing_part & 1) e = launch_igemm(p, l.bm, l.bn, l.group, s);
+            if (main_part) e = launch_igemm(p, l.bm, l.bn, l.group, s);
             if (e == hipSuccess && l.splits > 1 && !fused && (h->timing_part & 2)) e = launch_splitk_reduce(p, s);
         }
+        break;
+    }
     }
     if (e != hipSuccess) return hipfail(e, ("launch " + l.name).c_str());
     return LSPF2F_OK;
@@ -835,7 +803,8 @@ int lspf2f_forward_ex(lspf2f_handle *h, const float *feat_dev, const float *cand
             for (const auto &l : h->plan.layers) {
                 if (l.kind != kIgemm || l.ho > 16) continue;
                 const size_t wb = (size_t)(l.up4 ? 16 : 9) * l.cin * l.cout * h->plan.elt();
-                const int64_t off = l.fullk ? ((h->plan.dtype == 0 && (l.stride == 2 || (l.splits == 2 && !l.c1))) ? l.wfk2_off : l.wfk_off) : l.bandconv ? l.wbc_off : l.w_off;
+                const bool own = l.route == kRouteFullK || l.route == kRouteFullK16 || l.route == kRouteBand;      // (the other routes: their rows, when the blob carries them)
+                const int64_t off = l.form_off[own ? route_form(l) : kFormRows];
                 if (off < 0) continue;
                 const char *lo = h->blob + off, *hi = lo + wb;
                 if (!tp_lo || lo < tp_lo) tp_lo = lo;
@@ -914,7 +883,7 @@ int lspf2f_set_candidates(lspf2f_handle *h, const float *cand_dev, void *hip_str
     if (h->ws_size < P.cand_cache_bytes()) return fail(LSPF2F_ERR_STATE, "workspace too small");
     const LayerDesc &l = P.layers[0];
     FirstConvParams c{};
-    c.feat = nullptr; c.cand = cand_dev; c.w = reinterpret_cast<const float *>(h->blob + l.w_off);
+    c.feat = nullptr; c.cand = cand_dev; c.w = reinterpret_cast<const float *>(h->blob + l.form_off[kFormRows]);
     c.out = reinterpret_cast<float *>(h->ws);
     c.B = 1; c.H = l.hs; c.W = l.hs; c.feat_nc = P.feat_nc; c.cand_nc = P.input_nc - P.feat_nc; c.cand_batch = 1;
     c.Cout = l.cout; c.ci_begin = P.feat_nc; c.ci_end = P.input_nc; c.base = nullptr; c.relu = 0;
@@ -1049,6 +1018,15 @@ size_t lspf2f_conv3x3_scratch_bytes(int batch, int hs, int ws, int c0, int c1, i
     return sp > 1 ? (size_t)sp * Mout * cout * sizeof(float) : 0;
 }
 
+// the layer lspf2f_conv3x3's arguments describe, for the planner's predicates (upsample 1 = nearest x2 in front of the 9 taps, 2 = the sub-pixel form)
+static LayerDesc conv3x3_layer(int hs, int c0, int c1, int cout, int stride, int upsample)
+{
+    LayerDesc l;
+    l.hs = hs; l.ho = upsample ? 2 * hs : (stride == 2 ? (hs + 1) / 2 : hs);
+    l.c0 = c0; l.c1 = c1; l.cin = c0 + c1; l.cout = cout; l.stride = stride; l.up = upsample == 1; l.up4 = upsample == 2;
+    return l;
+}
+
 // lspf2f_conv3x3, and with `in` the conv of lspf2f_conv3x3_instnorm: the producer then also leaves the statistics InstanceNorm plans take from it -- per-group sums at
 // in->psum / psq / pshift ([B][in->groups][cout], bound and sized by the caller) from the implicit GEMM and the Winograd kernels, the normalisation itself from the
 // tiny-M kernel.  The caller has checked that (tile, k_group) names one of those producers.
@@ -1076,6 +1054,7 @@ static int conv3x3_run(const void *src0, const void *src1, const void *w_packed,
         const bool gemm_tile = (tile_m == 0 && tile_n == 0) || ((tile_m == 32 || tile_m == 64 || tile_m == 128) && (tile_n == 64 || tile_n == 128));
         if (!gemm_tile) return fail(LSPF2F_ERR_UNSUPPORTED, "k_group -4 runs on the implicit GEMM only: tile 0x0 (planner's choice) or one of its tiles");
     }
+    const LayerDesc L = conv3x3_layer(hs, c0, c1, cout, stride, upsample);
     hipError_t e = hipSuccess;
     {
         // tile 1x1 forces the tiny-M single-launch kernel; tile 0x0 lets the planner's rule pick it
@@ -1095,12 +1074,12 @@ static int conv3x3_run(const void *src0, const void *src1, const void *w_packed,
     }
     {
         // tile (16 | 32) x 16 forces the full-K single-launch kernel; tile 0x0 + split 0 lets the planner's rule pick it
-        const int ho_ = upsample ? 2 * hs : (stride == 2 ? (hs + 1) / 2 : hs);
+        const int ho_ = L.ho;
         if (tile_m > 3000 && tile_n == 64 && k_group == -1) {     // 3000 + R: the sub-pixel up-conv row kernel, weights in its fragment order
             RowUpParams q{};
             q.src0 = src0; q.src1 = src1; q.w = w_packed; q.scale = scale; q.shift = shift; q.out = out;
             q.B = batch; q.H = hs; q.W = ws; q.R = tile_m - 3000; q.relu = relu; q.dtype = dtype;
-            if (!rowup_layer(hs, c0, c1, cout, upsample == 2, dtype, false) || residual || hs != ws || !rowup_supported(q) || (q.R & 1))
+            if (!rowup_layer(L, dtype) || residual || hs != ws || !rowup_supported(q) || (q.R & 1))
                 return fail(LSPF2F_ERR_UNSUPPORTED, "the bf16 up-conv row kernel does not support this shape");
             e = launch_rowup(q, static_cast<hipStream_t>(hip_stream));
             if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (rowup) launch");
@@ -1213,7 +1192,7 @@ static int conv3x3_run(const void *src0, const void *src1, const void *w_packed,
             BandConvParams q{};
             q.src = src0; q.w = w_packed; q.scale = scale; q.shift = shift; q.residual = residual; q.out = out;
             q.B = batch; q.W = hs; q.Cout = cout; q.relu = relu; q.dtype = dtype;
-            if (!bandconv_layer(hs, c0, c1, cout, stride, upsample == 1, upsample == 2, dtype, false) || hs != ws || !bandconv_supported(q))
+            if (!bandconv_layer(L, dtype) || hs != ws || !bandconv_supported(q))
                 return fail(LSPF2F_ERR_UNSUPPORTED, "the bf16 band kernel does not support this shape");
             e = launch_bandconv(q, static_cast<hipStream_t>(hip_stream));
             if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (bandconv) launch");
@@ -1224,7 +1203,7 @@ static int conv3x3_run(const void *src0, const void *src1, const void *w_packed,
             q.src = src0; q.w = w_packed; q.scale = scale; q.shift = shift; q.residual = residual; q.out = out;
             q.B = batch; q.H = hs; q.W = ws; q.C = tile_n; q.R = tile_m - 1000; q.relu = relu; q.dtype = dtype;
             q.wfrag = k_group == -1 ? 1 : 0;     // -1: w_packed is already in the row kernel's fragment order
-            if (!rowconv_layer(hs, c0, c1, cout, stride, upsample == 1, upsample == 2, dtype, false) || c0 != tile_n || hs != ws || !rowconv_supported(q))
+            if (!rowconv_layer(L, dtype) || c0 != tile_n || hs != ws || !rowconv_supported(q))
                 return fail(LSPF2F_ERR_UNSUPPORTED, "the bf16 row kernel does not support this shape");
             e = launch_rowconv(q, static_cast<hipStream_t>(hip_stream));
             if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (rowconv) launch");
@@ -1243,7 +1222,7 @@ static int conv3x3_run(const void *src0, const void *src1, const void *w_packed,
         int pb = 0;
         if ((tile_m == 16 || tile_m == 32) && tile_n == 16) pb = tile_m / 16;
         else if (tile_m == 0 && tile_n == 0 && split_k == 0 && k_group != -4)
-            pb = fullk_choice(batch, hs, ho_, c0, c1, cout, stride, upsample == 1, upsample == 2, dtype);
+            pb = fullk_choice(L, batch, dtype);
         if (pb) {
             FullKParams q{};
             q.src0 = static_cast<const float *>(src0); q.src1 = c1 ? static_cast<const float *>(src1) : nullptr;

@@ -87,8 +87,18 @@ void choose_tiling(int M, int N, int ktiles, int par, bool up9, int dtype, int *
     *group_out = group;
 }
 
-int wino_choice(int batch, int ho, int cin, int cout, int *splits_out)
+// K slices of a Winograd launch of `wgs` workgroups that aims at `target`: at most 8, each of >= `min_steps` of the `steps` eight-channel K steps, none empty
+static int wino_k_splits(long wgs, int target, int steps, int min_steps)
 {
+    const int splits = std::min((int)((target + wgs - 1) / wgs), std::min(8, std::max(1, steps / min_steps)));
+    const int per = (steps + splits - 1) / splits;
+    return (steps + per - 1) / per;
+}
+// The three Winograd kernels, per batch: 32-channel blocks per wave (0 = not this kernel) and the K splits.  Each ends by asking the kernel's own
+// *_supported() (2-GiB buffer offsets, extents): a shape the launch would refuse falls through to the next candidate instead of failing during graph capture.
+static int wino_choice(const LayerDesc &l, int batch, int *splits_out)
+{
+    const int ho = l.ho, cin = l.cin, cout = l.cout;
     // A workgroup = 32 Winograd tiles (8 x 16 output pixels) x 32 nb channels over the whole K (or a slice).  Two channel blocks per wave halve
     // the fragment reads per MFMA but cost half the workgroups: used when that still leaves two workgroups per CU.  Below ~1.5 workgroups
     // per CU the input channels are split (combined inside the launch), keeping >= 4 eight-channel steps per slice.
@@ -98,14 +108,7 @@ int wino_choice(int batch, int ho, int cin, int cout, int *splits_out)
     if (ho < 32 && ntb * (cout / 32) < 128) return 0;
     int nb = (cout % 64 == 0 && ntb * (cout / 64) >= 512) ? 2 : 1;
     const long wgs = ntb * (cout / (32 * nb));
-    const int steps = cin / 8;
-    int splits = 1;
-    if (wgs < 384) {
-        splits = (int)((512 + wgs - 1) / wgs);
-        splits = std::min(splits, std::min(8, std::max(1, steps / 4)));
-        const int per = (steps + splits - 1) / splits;
-        splits = (steps + per - 1) / per;                  // every slice non-empty
-    }
+    const int splits = wgs < 384 ? wino_k_splits(wgs, 512, cin / 8, 4) : 1;
     WinoParams q{};
     q.B = batch; q.H = ho; q.W = ho; q.C = cin; q.N = cout; q.splits = 1;
     if (!wino_supported(q, nb)) return 0;
@@ -114,19 +117,13 @@ int wino_choice(int batch, int ho, int cin, int cout, int *splits_out)
     return nb;
 }
 
-int wino4_choice(int batch, int ho, int cin, int cout, int *splits_out)
+static int wino4_choice(const LayerDesc &l, int batch, int *splits_out)
 {
+    const int ho = l.ho, cin = l.cin, cout = l.cout;
     // A workgroup = 32 tiles of 4 x 4 outputs (16 x 32 pixels) x 32 channels, ONE per CU (its ring slots take 112 KB of LDS): below ~one
     // workgroup per CU the input channels are split (combined inside the launch), keeping >= 4 eight-channel steps per slice.
     const long wgs = (long)batch * (ho / 16) * (ho / 32) * (cout / 32);
-    const int steps = cin / 8;
-    int splits = 1;
-    if (wgs < 192) {
-        splits = (int)((256 + wgs - 1) / wgs);
-        splits = std::min(splits, std::min(8, std::max(1, steps / 4)));
-        const int per = (steps + splits - 1) / splits;
-        splits = (steps + per - 1) / per;                  // every slice non-empty
-    }
+    const int splits = wgs < 192 ? wino_k_splits(wgs, 256, cin / 8, 4) : 1;
     WinoParams q{};
     q.B = batch; q.H = ho; q.W = ho; q.C = cin; q.N = cout; q.splits = 1;
     if (!wino4_supported(q)) return 0;
@@ -135,8 +132,10 @@ int wino4_choice(int batch, int ho, int cin, int cout, int *splits_out)
     return 1;
 }
 
-int winoup_choice(int batch, int hs, int cin, int cout, int *splits_out, int force_nb, int target, bool small_level)
+static int winoup_choice(const Plan &P, const LayerDesc &l, int batch, int *splits_out)
 {
+    const int hs = l.hs, cin = l.cin, cout = l.cout, force_nb = P.winoup_nb, target = P.winoup_target;
+    const bool small_level = !l.up4;      // an up-conv below the sub-pixel extent (kUp4MinExtent): the one that writes 16 x 16
     // the up-conv that writes 16 x 16 (1024 -> 512 from 8 x 8) runs here from two frames up (tools/time_conv.py, per layer): 28.3 against 47.8 us for the full-K kernel at
     // two frames, 39.2 against 93.6 (implicit GEMM over the upsampled 9 taps) at four, 58.1 against 170.3 at eight.  One frame keeps the full-K kernel: 21.3 against 25.1 us
     // when timed alone, but the whole forward is 0.6 % SLOWER with it (653.2 vs 657.0 frames/s, A-B-A-B of two libraries: profiles/r04_fullk_small_levels_batch.txt)
@@ -150,22 +149,246 @@ int winoup_choice(int batch, int hs, int cin, int cout, int *splits_out, int for
     if ((nb != 1 && nb != 2) || cout % (32 * nb)) return 0;     // a forced nb the shape cannot take: the implicit GEMM keeps the layer
     const long wgs = ntb * (cout / (32 * nb));
     if (wgs <= 0) return 0;
-    {   // the kernel's own shape limits (2-GiB buffer offsets, extents), like wino_choice: an unsupported shape falls back instead of failing at launch
+    {
         WinoUpParams q{};
         q.B = batch; q.Hs = hs; q.Ws = hs; q.C0 = cin; q.C1 = 0; q.N = cout; q.splits = 1;
         if (!winoup_supported(q, nb)) return 0;
     }
-    const int steps = cin / 8;
-    int splits = 1;
-    if (wgs < target * 3 / 4) {
-        splits = (int)((target + wgs - 1) / wgs);
-        splits = std::min(splits, std::min(8, std::max(1, steps / 8)));
-        const int per = (steps + splits - 1) / splits;
-        splits = (steps + per - 1) / per;
-    }
+    const int splits = wgs < target * 3 / 4 ? wino_k_splits(wgs, target, cin / 8, 8) : 1;
     if (splits > 1 && wgs > (long)Plan::kTileCounters) return 0;
     *splits_out = splits;
     return nb;
+}
+
+// ---- who gets a weight form (plan.h): policy here, limits from the kernel asked for one frame ----
+bool fullk_layer(const LayerDesc &l, int dtype)
+{
+    if (dtype != 0 || l.stride != 1 || l.up4) return false;
+    if (l.ho != 2 && l.ho != 4 && l.ho != 8 && l.ho != 16) return false;     // (4x4 / 2x2 belong to the tiny-M kernel while the batch has <= 16 output pixels: fullk_choice)
+    if (l.up ? 2 * l.hs != l.ho : l.hs != l.ho) return false;
+    return (l.c0 == 128 || l.c0 == 256 || l.c0 == 512) && (l.c1 == 0 || l.c1 == l.c0) && l.cout % 128 == 0;
+}
+bool fullk_s2_layer(const LayerDesc &l, int dtype)
+{
+    return dtype == 0 && l.stride == 2 && !l.up && !l.up4 && !l.inorm && l.c1 == 0 && (l.c0 == 256 || l.c0 == 512) && l.cout % 128 == 0 &&
+           (l.ho == 16 || l.ho == 8 || l.ho == 4) && l.hs == 2 * l.ho;
+}
+bool fullk16_layer(const LayerDesc &l, int dtype)
+{
+    if (dtype == 0 || l.up4 || l.inorm) return false;
+    if (l.ho != 2 && l.ho != 4 && l.ho != 8) return false;
+    if (l.up) { if (l.stride != 1 || 2 * l.hs != l.ho) return false; }
+    else if (l.stride == 2) { if (l.hs != 2 * l.ho || l.c1 != 0) return false; }
+    else if (l.stride != 1 || l.hs != l.ho) return false;
+    return (l.c0 == 256 || l.c0 == 512) && (l.c1 == 0 || l.c1 == l.c0) && l.cout % 128 == 0;
+}
+bool wino_layer(const LayerDesc &l, int dtype)
+{
+    // InstanceNorm plans too: the kernel then writes the raw conv output (+ bias) and the statistics come from its epilogue or the separate passes
+    return dtype == 0 && l.stride == 1 && !l.up && !l.up4 && l.c1 == 0 && l.hs == l.ho && l.ho >= kWinoMinExtent && l.ho % 16 == 0 &&
+           l.c0 % 8 == 0 && l.cout % 32 == 0;
+}
+bool wino4_layer(const LayerDesc &l, int dtype) { return wino_layer(l, dtype) && l.ho >= 32 && l.ho % 32 == 0; }
+// (any Upsample + Conv3x3 layer: those below kUp4MinExtent keep their 9-tap rows for the full-K kernel / implicit GEMM and take this kernel from the batch where it wins)
+bool winoup_layer(const LayerDesc &l, int dtype)
+{
+    return dtype == 0 && (l.up4 || l.up) && (l.c1 == l.c0 || l.c1 == 0) && l.c0 % 8 == 0 && l.cout % 32 == 0 && l.hs % 8 == 0;
+}
+bool rowup_layer(const LayerDesc &l, int dtype)
+{
+    if (dtype == 0 || !l.up4 || l.c0 != 128 || l.c1 != 128 || l.cout != 64 || l.inorm) return false;
+    RowUpParams q{};
+    q.B = 1; q.H = q.W = l.hs; q.R = 2;
+    return rowup_supported(q);
+}
+bool rowconv_layer(const LayerDesc &l, int dtype)
+{
+    if (dtype == 0 || l.c1 != 0 || l.cout != l.c0 || l.stride != 1 || l.up || l.up4 || l.inorm) return false;
+    RowConvParams q{};
+    q.B = 1; q.H = q.W = l.ho; q.C = l.c0; q.R = 1;
+    return rowconv_supported(q);
+}
+bool bandconv_layer(const LayerDesc &l, int dtype)
+{
+    if (dtype == 0 || l.c0 != 512 || l.c1 != 0 || l.stride != 1 || l.up || l.up4 || l.inorm) return false;
+    BandConvParams q{};
+    q.B = 1; q.W = l.ho; q.Cout = l.cout;
+    return bandconv_supported(q);
+}
+
+// ---- per batch: the full-K kernels and the patch-staged kernels (pixel blocks per tile / tile width, 0 = not this kernel) ----
+// fullk_supported() for the layer with `pb` pixel blocks per tile (its LDS band: the source rows behind a tile in 150 KB); split 2 = the K-split form
+static bool fullk_fits(const LayerDesc &l, int batch, int pb, int split)
+{
+    FullKParams q{};
+    q.B = batch; q.Hs = q.Ws = l.hs; q.Ho = q.Wo = l.ho; q.C0 = l.c0; q.C1 = l.c1; q.Cout = l.cout; q.up = l.up; q.stride = l.stride; q.split = split;
+    float present = 0.f;
+    unsigned present_cnt = 0;
+    if (split > 1) { q.partial = &present; q.tile_cnt = &present_cnt; }      // (only tested for presence)
+    return fullk_supported(q, pb);
+}
+int fullk_choice(const LayerDesc &l, int batch, int dtype)
+{
+    if (!fullk_layer(l, dtype)) return 0;
+    const int ho = l.ho, ntn = l.cout / 16;
+    // 4x4 / 2x2 frames (a tile = one whole frame, 16 / 4 of its 16 rows used): from the batch the tiny-M kernel stops taking (> 16 output pixels) up.  Measured per layer,
+    // 512 -> 512 (tools/time_conv.py): 4x4 at 2 / 4 / 8 frames 9.1 / 8.9 / 9.3 us against 13.5 / 15.1 / 20.1 for igemm + reduce; 2x2 at 8 frames 8.7 against 13.7
+    if (ho <= 4 && (long)batch * ho * ho <= 16) return 0;
+    // whole tiles must fit one dispatch wave of the chip with room to spare: <= 512 workgroups (2 per CU on 256 CUs)
+    for (int pb = 1; pb <= (ho == 16 ? 2 : 1); ++pb) {
+        const int nr = pb * (16 / ho);
+        const long tiles = (long)batch * ((ho + nr - 1) / nr) * ntn;
+        // 8x8 frames: up to four rounds of workgroups still beat the split-K implicit GEMM (8 frames: 28.1 against 35.6 us)
+        if (ho == 8 && tiles > 512 && tiles <= 1024) return 1;
+        if (!fullk_fits(l, batch, pb, 0)) continue;      // 133 KB for the widest shape the generators build (4 rows x 16 px x 512 ch)
+        if (tiles <= 256 || (pb == (ho == 16 ? 2 : 1) && tiles <= 512)) return pb;
+    }
+    return 0;
+}
+// K split of the full-K kernel: when its tiles fill at most half the chip (8x8 outputs at batch 1: 4 x cout / 16 = 128 tiles on 256 CUs) and the input
+// has two sources or one of >= 256 channels to halve
+static bool fullk_split(const Plan &P, const LayerDesc &l, int batch, int pb)
+{
+    if (!P.use_fullk_split || (l.ho != 8 && l.ho != 16)) return false;
+    const int nr = pb * (16 / l.ho);
+    const long tiles = (long)batch * (l.ho / nr) * (l.cout / 16);
+    return tiles <= P.fullk_split_max_tiles && (l.c1 == l.c0 || (l.c1 == 0 && l.c0 >= 256));
+}
+// a fullk_s2_layer on the K-split full-K kernel (half the channels of its 5-row band fit LDS): `use_fullk_s2` 1 = L4 / L5 / L6.down, 2 = only those writing <= 8x8
+static int fullk_s2_choice(const Plan &P, const LayerDesc &l, int batch)
+{
+    if (P.use_fullk_s2 == 2 && l.ho > 8) return 0;
+    if (batch != 1) return 0;                                 // measured at batch 1 only; from 2 frames up the implicit GEMM has rows enough
+    const int nr = 16 / l.ho;                                 // one 16-pixel block per tile
+    const long tiles = (long)batch * ((l.ho + nr - 1) / nr) * (l.cout / 16);
+    if (!fullk_fits(l, batch, 1, 2)) return 0;
+    return tiles <= 512 ? 1 : 0;                              // 2 x tiles workgroups, one per CU at a time: up to four rounds
+}
+// The 16-bit twin (fullk16.hip): the 8x8 / 4x4 / 2x2 levels of the bf16 / fp16 plans from `fullk16_min_frames` (2) frames up.  `fullk16_levels` (tune key `fullk16`):
+// bit 0 = the 4x4 / 2x2 levels, bit 1 = the stride-2 / upsampling convs that WRITE 8x8 (igemm + splitk_reduce otherwise), bit 2 = the stride-1 single-source 8x8
+// layers (bandconv512 otherwise).
+static int fullk16_choice(const Plan &P, const LayerDesc &l, int batch)
+{
+    if (!fullk16_layer(l, P.dtype) || batch < P.fullk16_min_frames) return 0;
+    const int bit = l.ho <= 4 ? 1 : (l.up || l.stride == 2) ? 2 : 4;
+    if (!(P.fullk16_levels & bit)) return 0;
+    const int nr = 16 / l.ho;                                 // output rows per 16-pixel block (a 4x4 / 2x2 frame is one block)
+    const long tiles = (long)batch * ((l.ho + nr - 1) / nr) * (l.cout / 16);
+    FullK16Params q{};
+    q.B = batch; q.Hs = q.Ws = l.hs; q.Ho = q.Wo = l.ho; q.C0 = l.c0; q.C1 = l.c1; q.Cout = l.cout; q.up = l.up; q.stride = l.stride; q.dtype = P.dtype;
+    if (!fullk16_supported(q, 1)) return 0;
+    return tiles <= 1024 ? 1 : 0;                             // up to four rounds of workgroups (8x8 at 8 frames), like the fp32 kernel
+}
+// patch-staged 16-bit kernel (patch16.hip): stride-1 single-source convs of >= 128 channels at 64x64 (tiles of 4 rows x 64 pixels) and 32x32 (8 rows x 32);
+// returns the tile width and the channels per workgroup: 128 when that still fills the chip, else 64
+static int patch16_choice(const Plan &P, const LayerDesc &l, int batch, int *bn)
+{
+    if (P.dtype == 0 || l.c1 != 0 || l.stride != 1 || l.up || l.up4 || l.inorm) return 0;
+    if ((l.ho != 64 && l.ho != 32) || l.c0 % 64 || l.c0 < 128 || l.cout % 64) return 0;
+    const long mtiles = (long)batch * l.ho * l.ho / 256;
+    const int tw = l.ho == 64 ? 64 : 32;
+    if (l.cout % 128 == 0 && mtiles * (l.cout / 128) >= P.patch16_min_blocks) *bn = 128;
+    else if (mtiles * (l.cout / 64) >= P.patch16_min_blocks) *bn = 64;
+    else return 0;
+    PatchConvParams q{};
+    q.B = batch; q.H = q.W = l.ho; q.C = l.c0; q.Cout = l.cout; q.dtype = P.dtype;
+    return patch16_supported(q, tw, *bn) ? tw : 0;
+}
+// its sub-pixel up-conv form (conv3x3_patchup16): up4 layers over one source or two equally wide ones at a 64x64 / 32x32 / 16x16 LOW-res extent
+static int patchup16_choice(const Plan &P, const LayerDesc &l, int batch, int *bn)
+{
+    if (P.dtype == 0 || !l.up4 || l.inorm || (l.c1 != 0 && l.c1 != l.c0)) return 0;
+    if ((l.hs != 64 && l.hs != 32 && l.hs != 16) || l.c0 % 64 || l.c0 + l.c1 < 128 || l.cout % 64) return 0;
+    const long mtiles = (long)batch * l.hs * l.hs / 256 * 4;
+    int tw;
+    if (l.hs >= 32 && l.cout % 128 == 0 && mtiles * (l.cout / 128) >= P.patch16_min_blocks) { *bn = 128; tw = l.hs == 64 ? 64 : 32; }
+    else if (mtiles * (l.cout / 64) >= P.patch16_min_blocks) { *bn = 64; tw = l.hs == 64 ? 64 : l.hs; }      // (16x16 sources: a tile = one whole low-res frame, 64 channels per workgroup only)
+    else return 0;
+    PatchConvParams q{};
+    q.B = batch; q.H = q.W = l.hs; q.C = l.c0; q.C1 = l.c1; q.Cout = l.cout; q.dtype = P.dtype;
+    q.src1 = l.c1 ? &q : nullptr;        // (only tested for presence)
+    return patchup16_supported(q, tw, *bn) ? tw : 0;
+}
+
+// Which kernel runs a body layer at a batch.  An ordered list: the first candidate that takes the layer wins, and ITS tile / splits / group are the plan's.
+// A candidate looks only at the switch of its family, at the offset of the weight form IT reads (the blob of a handle carries just the forms its batch
+// range uses, Plan::build) and at its own per-batch rule, which ends by asking the kernel's *_supported().  No candidate names another one: precedence is
+// the order below, and the comment on each says why it sits there.
+RouteChoice choose_route(const Plan &p, const LayerDesc &l, int batch)
+{
+    const int Mout = batch * l.ho * l.ho, M = l.up4 ? batch * l.hs * l.hs : Mout;
+    auto carried = [&](WeightForm f) { return l.form_off[f] >= 0; };
+    int splits = 1, bn = 0;
+
+    // 1. tiny-M kernel: <= 16 output pixels, one launch, no split-K.  First, because nothing else is built for M this small -- the full-K kernels leave the 4x4 / 2x2
+    //    levels to it while it takes them (fullk_choice), the Winograd and row kernels need extents it never sees.  `smallm_kb` (fp32 plans) is the planner's bound
+    //    on the input tensor where it is tighter than the kernel's; the rest is smallm_supported().
+    if (!l.up4 && l.c1 == 0) {
+        SmallMParams q{};
+        q.B = batch; q.Hs = q.Ws = l.hs; q.Ho = q.Wo = l.ho; q.Cin = l.cin; q.Cout = l.cout; q.stride = l.stride; q.up = l.up; q.M = M; q.dtype = p.dtype;
+        const size_t in_bytes = (size_t)batch * l.hs * l.hs * l.cin * 4;
+        if ((p.dtype != 0 || in_bytes <= (size_t)p.smallm_kb * 1024) && smallm_supported(q)) return {kRouteSmallM, 1, 1, 1, 1, 1};
+    }
+    // 2. up-conv Winograd kernel (fp32 up-convs).  Ahead of the full-K kernel: the up-conv that writes 16x16 (L5.up of the 512x512 nets) is a fullk_layer too, and from
+    //    two frames up BOTH rules accept it -- this one wins there (28.3 against 47.8 us at two frames, winoup_choice), the full-K kernel keeps one frame because
+    //    winoup_choice declines it.  No other candidate takes an fp32 up-conv.
+    if (p.use_wino && p.use_winoup && carried(kFormWinoUp))
+        if (const int nb = winoup_choice(p, l, batch, &splits)) return {kRouteWinoUp, nb, 32, 32 * nb, splits, 1};
+    // 3. Winograd F(4x4,3x3), opt-in (LSPF2F_FLAG_WINO4): ahead of F(2x2,3x3) because every layer it takes is one of that kernel's too -- switching it on is asking for it
+    if (p.use_wino && p.use_wino4 && carried(kFormWino4))
+        if (wino4_choice(l, batch, &splits)) return {kRouteWino4, 1, 32, 32, splits, 1};
+    // 4. Winograd F(2x2,3x3): fp32 stride-1 convs at >= 32x32, and 16x16 from four frames up.  Ahead of the full-K kernel, whose 16x16 layers these also are: wino_choice
+    //    declines them below 128 workgroups (<= 3 frames of 512 channels), where fullk_choice takes up to two frames -- the two rules do not meet today, the order says
+    //    who wins if a threshold moves
+    if (p.use_wino && carried(kFormWino))
+        if (const int nb = wino_choice(l, batch, &splits)) return {kRouteWino, nb, 32, 32 * nb, splits, 1};
+    // 5. rowup256 (16-bit L1.up: 128 + 128 -> 64 sub-pixel up-conv).  Ahead of the patch-staged up-conv form, which accepts the same layer: the row kernel is the
+    //    faster one from the strip length at which it runs at all.  Short strips (1 frame: 4 rows + 2 halo steps) do not beat the implicit GEMM: 22.4 vs 22.9 us
+    if (p.use_rowup && carried(kFormRowUp)) {
+        RowUpParams q{};
+        q.B = batch; q.H = q.W = l.hs; q.R = rowup_rows(batch, l.hs, l.hs);
+        if (q.R >= 8 && rowup_supported(q)) return {kRouteRowUp, q.R, 32 * q.R, 32, 1, 1};
+    }
+    // 6. patch-staged kernel, sub-pixel up-conv form (16-bit up4 layers over 64x64 / 32x32 / 16x16 sources): the only other kernel for them besides the implicit GEMM
+    if (p.use_patch16 && p.use_patchup16)
+        if (const int tw = patchup16_choice(p, l, batch, &bn)) return {kRoutePatchUp16, tw, 256, bn, 1, 1};
+    // 7. weights-stationary row kernels (16-bit 64 -> 64 and 128 -> 128).  Ahead of the patch-staged kernel: the 128 -> 128 layers at 64x64 / 32x32 are patch16 shapes too,
+    //    and the row kernel keeps them
+    if (p.use_rowconv && carried(kFormRow)) {
+        RowConvParams q{};
+        q.B = batch; q.H = q.W = l.ho; q.C = l.c0; q.R = rowconv_rows(batch, l.ho, l.ho, l.c0);
+        if (rowconv_supported(q)) return {kRouteRowConv, q.R, (l.c0 == 64 ? 64 : 32) * q.R, l.c0, 1, 1};
+    }
+    // 8. patch-staged kernel (16-bit stride-1 convs of >= 128 channels at 64x64 / 32x32) from `patch16_min_blocks` workgroups up; no later candidate takes these extents
+    if (p.use_patch16)
+        if (const int tw = patch16_choice(p, l, batch, &bn)) return {kRoutePatch16, tw, 256, bn, 1, 1};
+    // 9. 16-bit full-K kernel (8x8 / 4x4 / 2x2 levels from two frames up): the single-launch structure of the fp32 kernel, whole K per workgroup, no split.  Ahead of
+    //    the band kernel: where `fullk16_levels` gives it the stride-1 512-channel layers (bit 0: 4x4 / 2x2, bit 2: 8x8) it replaces bandconv512 on them
+    if (p.dtype != 0 && carried(kFormFullK))
+        if (const int pb = fullk16_choice(p, l, batch)) return {kRouteFullK16, pb, 16 * pb, 16, 1, 1};
+    // 10. bandconv512 (16-bit stride-1 512 -> Cout at 16x16 / 8x8) once the launch has `bandconv_min_blocks` workgroups.  The 4x4 / 2x2 levels (a tile = 2 / 8 whole
+    //     frames) never by default: at 8 frames the 64 / 16 workgroups of such a launch lose to the igemm (normal 4460 -> 4388, large 2881 -> 2840 frames/s, A-B-A-B)
+    if (p.use_bandconv && carried(kFormBand) &&
+        (l.ho >= 8 ? (long)batch * (l.ho == 16 ? 4 : 2) * (l.cout / 32) >= p.bandconv_min_blocks : batch >= p.bandconv_min_frames_small)) {
+        BandConvParams q{};
+        q.B = batch; q.W = l.ho; q.Cout = l.cout; q.dtype = p.dtype;
+        if (bandconv_supported(q)) return {kRouteBand, 1, l.ho == 16 ? 64 : 32, 32, 1, 1};
+    }
+    // 11. fp32 full-K kernel (16x16 .. 2x2 stride-1 layers of small batches): last of the special kernels, it takes what the tiny-M and Winograd kernels left.  With K
+    //     in two halves over twice the workgroups (splits 2, combined in the launch) where its tiles fill at most half the chip; a single source then reads the
+    //     half-source form.  Without the form its variant reads, the layer stays on the implicit GEMM.
+    if (const int pb = fullk_choice(l, batch, p.dtype)) {
+        const bool k2 = fullk_split(p, l, batch, pb) && carried(l.c1 ? kFormFullK : kFormFullK2);
+        if (k2 || carried(kFormFullK)) return {kRouteFullK, pb, 16 * pb, 16, k2 ? 2 : 1, 1};
+    }
+    //     ... and, opt-in (`fullk_s2`), the stride-2 convs of the small levels at batch 1, K-split form only.  Round 3 measured it SLOWER for the whole forward although
+    //     two of its three launches are shorter (tools/s2_layer_delta.py)
+    if (p.use_fullk_s2 && p.use_fullk_split && carried(kFormFullK2) && fullk_s2_layer(l, p.dtype) && fullk_s2_choice(p, l, batch))
+        return {kRouteFullK, 1, 16, 16, 2, 1};
+    // 12. implicit GEMM: takes everything
+    RouteChoice c{kRouteIgemm, 0, 0, 0, 1, 1};
+    choose_tiling(M, l.cout, (l.up4 ? 4 : 9) * l.cin / p.ktile_channels(), l.up4 ? 4 : 1, l.up, p.dtype, &c.bm, &c.bn, &c.splits, &c.group);
+    return c;
 }
 
 static void level_channels(int depth, int ngf, int input_nc, int output_nc, int *cin, int *inner, int *cout)
@@ -349,109 +572,70 @@ std::string Plan::build(int variant_, int input_nc_, int feat_nc_, int output_nc
     return "";
 }
 
+// ---- the weight forms, each described once: who may carry it and how large it is.  In blob order: alignment and order decide the offsets ----
+namespace {
+struct FormRule {
+    WeightForm form;
+    bool (*carried)(const Plan &, const LayerDesc &);      // batch-independent: the *_layer predicate plus the plan's switches
+    size_t (*bytes)(const Plan &, const LayerDesc &);
+};
+size_t taps_typed(const Plan &p, const LayerDesc &l, int taps) { return (size_t)taps * l.cout * l.cin * p.elt(); }
+size_t taps_f32(const LayerDesc &l, int taps) { return (size_t)taps * l.cout * l.cin * sizeof(float); }
+bool body(const LayerDesc &l) { return l.kind == kIgemm; }
+const FormRule kFormRules[] = {
+    // every layer; the sub-pixel form (up4, last conv) has 16/9 of the 9-tap bytes; first / last conv weights stay fp32
+    {kFormRows, [](const Plan &, const LayerDesc &) { return true; },
+     [](const Plan &p, const LayerDesc &l) { return (size_t)l.cout * l.cin * ((l.up4 || l.kind == kLastConv) ? 16 : 9) * (p.layer_weights_typed(l) ? p.elt() : sizeof(float)); }},
+    {kFormGemmLast, [](const Plan &p, const LayerDesc &l) { return p.last_as_gemm(l); }, [](const Plan &p, const LayerDesc &l) { return taps_typed(p, l, 4 * 9); }},
+    // rowlast128 writes 12 columns per pixel (48-byte records): output_nc 3 only
+    {kFormRowLast, [](const Plan &p, const LayerDesc &l) { return p.last_as_gemm(l) && l.c0 == 64 && l.c1 == 64 && l.cout == 3 && (l.hs % 64) == 0; },
+     [](const Plan &p, const LayerDesc &) { return (size_t)9 * 4 * 64 * 8 * p.elt(); }},
+    // the 16x16 .. 2x2 layers in the tile-blocked layout of the full-K kernel (fp32: small-batch plans; 16-bit: the 8x8 / 4x4 / 2x2 levels, fullk16.hip) ...
+    {kFormFullK, [](const Plan &p, const LayerDesc &l) { return body(l) && (p.dtype == 0 ? fullk_layer(l, 0) : p.fullk16_levels && fullk16_layer(l, p.dtype)); },
+     [](const Plan &p, const LayerDesc &l) { return taps_typed(p, l, 9); }},
+    // ... and its K-split form, which reads a single source as two half-sources; the only full-K copy of the stride-2 convs (tune key `fullk_s2`: carried when switched on)
+    {kFormFullK2, [](const Plan &p, const LayerDesc &l) { return body(l) && ((fullk_layer(l, p.dtype) && l.c1 == 0 && l.c0 >= 256) || (p.use_fullk_s2 && fullk_s2_layer(l, p.dtype))); },
+     [](const Plan &, const LayerDesc &l) { return taps_f32(l, 9); }},
+    {kFormWino, [](const Plan &p, const LayerDesc &l) { return body(l) && p.use_wino && wino_layer(l, p.dtype); }, [](const Plan &, const LayerDesc &l) { return taps_f32(l, 16); }},
+    {kFormWino4, [](const Plan &p, const LayerDesc &l) { return body(l) && p.use_wino && p.use_wino4 && wino4_layer(l, p.dtype); }, [](const Plan &, const LayerDesc &l) { return taps_f32(l, 36); }},
+    {kFormWinoUp, [](const Plan &p, const LayerDesc &l) { return body(l) && p.use_wino && p.use_winoup && winoup_layer(l, p.dtype); }, [](const Plan &, const LayerDesc &l) { return taps_f32(l, 9); }},
+    {kFormRowUp, [](const Plan &p, const LayerDesc &l) { return body(l) && rowup_layer(l, p.dtype); }, [](const Plan &p, const LayerDesc &l) { return taps_typed(p, l, 16); }},
+    {kFormBand, [](const Plan &p, const LayerDesc &l) { return body(l) && bandconv_layer(l, p.dtype); }, [](const Plan &p, const LayerDesc &l) { return taps_typed(p, l, 9); }},
+    {kFormRow, [](const Plan &p, const LayerDesc &l) { return body(l) && rowconv_layer(l, p.dtype); }, [](const Plan &p, const LayerDesc &l) { return taps_typed(p, l, 9); }},
+};
+}  // namespace
+
+size_t Plan::form_bytes(const LayerDesc &l, WeightForm f) const
+{
+    for (const FormRule &r : kFormRules)
+        if (r.form == f) return r.bytes(*this, l);
+    return 0;
+}
+
 unsigned Plan::forms_used(const LayerDesc &l, const Plan &p)
 {
-    if (l.kind == kFirstConv) return kFormRows;
-    if (l.kind == kLastConv) return kFormRows | (p.last_as_gemm(l) ? kFormGemmLast : 0u);      // rows: the direct kernels (fp32 plans; `lastconv_direct` of 16-bit ones)
-    if (l.wino4) return kFormWino4;
-    if (l.wino) return kFormWino;
-    if (l.winoup) return kFormWinoUp;
-    if (l.rowup) return kFormRowUp;
-    if (l.bandconv) return kFormBand;
-    if (l.rowconv) return kFormRow;
-    if (l.fullk) return (p.dtype == 0 && (l.stride == 2 || (l.splits == 2 && !l.c1))) ? kFormFullK2 : kFormFullK;      // (16-bit plans: one tile-blocked form, fullk16.hip)
-    return kFormRows;
+    if (l.kind == kFirstConv) return 1u << kFormRows;
+    // rows: the direct kernels (fp32 plans; `lastconv_direct` of 16-bit ones)
+    if (l.kind == kLastConv) return 1u << kFormRows | (p.last_as_gemm(l) ? 1u << kFormGemmLast | 1u << kFormRowLast : 0u);
+    return 1u << route_form(l);
 }
 
 void Plan::assign_offsets(const std::vector<unsigned> *used)
 {
     size_t off = (size_t)blob_pad_kb * 1024;          // tools (tune key `blob_pad_kb`): where the weights sit relative to the workspace's channel interleave
+    auto take = [&](size_t bytes) { off = align_up(off, 256); const size_t at = off; off += bytes; return (int64_t)at; };
     for (size_t li = 0; li < layers.size(); ++li) {
         LayerDesc &l = layers[li];
         const unsigned need = used ? (*used)[li] : ~0u;
-        l.w_off = l.wgemm_off = l.wrl_off = l.wfk_off = l.wfk2_off = l.wwg_off = l.ww4_off = l.wwu_off = l.wru_off = l.wbc_off = l.wrc_off = -1;
+        for (const FormRule &r : kFormRules) l.form_off[r.form] = ((need >> r.form) & 1u) && r.carried(*this, l) ? take(r.bytes(*this, l)) : -1;
         l.scale_off = l.shift_off = -1;
-        if (need & kFormRows) {
-            off = align_up(off, 256);
-            l.w_off = (int64_t)off;
-            off += (size_t)l.cout * l.cin * ((l.up4 || l.kind == kLastConv) ? 16 : 9) * (layer_weights_typed(l) ? elt() : sizeof(float));
-        }
-        if ((need & kFormGemmLast) && last_as_gemm(l)) {
-            off = align_up(off, 256);
-            l.wgemm_off = (int64_t)off;
-            off += (size_t)4 * l.cout * 9 * l.cin * elt();
-            if (l.c0 == 64 && l.c1 == 64 && l.cout == 3 && (l.hs % 64) == 0) {     // rowlast128 writes 12 columns per pixel (48-byte records): output_nc 3 only
-                off = align_up(off, 256);
-                l.wrl_off = (int64_t)off;
-                off += (size_t)9 * 4 * 64 * 8 * elt();
-            }
-        }
-        if (l.kind == kIgemm && fullk_layer(l.hs, l.ho, l.c0, l.c1, l.cout, l.stride, l.up, l.up4, dtype)) {
-            // the 16x16 / 8x8 layers in the tile-blocked layout of the full-K kernel (small-batch plans) ...
-            if (need & kFormFullK) {
-                off = align_up(off, 256);
-                l.wfk_off = (int64_t)off;
-                off += (size_t)l.cout * 9 * l.cin * sizeof(float);
-            }
-            if ((need & kFormFullK2) && l.c1 == 0 && l.c0 >= 256) {                  // ... and its K-split form, which reads a single source as two half-sources
-                off = align_up(off, 256);
-                l.wfk2_off = (int64_t)off;
-                off += (size_t)l.cout * 9 * l.cin * sizeof(float);
-            }
-        }
-        // 16-bit plans: the 8x8 / 4x4 / 2x2 layers in the tile-blocked order of the 16-bit full-K kernel (fullk16.hip)
-        if (l.kind == kIgemm && dtype != 0 && (need & kFormFullK) && fullk16_levels && fullk16_layer(l.hs, l.ho, l.c0, l.c1, l.cout, l.stride, l.up, l.up4, dtype, l.inorm)) {
-            off = align_up(off, 256);
-            l.wfk_off = (int64_t)off;
-            off += (size_t)l.cout * 9 * l.cin * elt();
-        }
-        // the stride-2 convs of the small levels on the K-split full-K kernel (tune key `fullk_s2=1`): only carried when that path is switched on
-        if (l.kind == kIgemm && (need & kFormFullK2) && use_fullk_s2 && fullk_s2_layer(l.hs, l.ho, l.c0, l.c1, l.cout, l.stride, l.up, l.up4, dtype, l.inorm)) {
-            off = align_up(off, 256);
-            l.wfk2_off = (int64_t)off;                        // the only full-K copy of these layers: their single source as two half-sources
-            off += (size_t)l.cout * 9 * l.cin * sizeof(float);
-        }
-        if (l.kind == kIgemm && (need & kFormWino) && use_wino && wino_layer(l.hs, l.ho, l.c0, l.c1, l.cout, l.stride, l.up, l.up4, dtype, l.inorm)) {
-            off = align_up(off, 256);
-            l.wwg_off = (int64_t)off;                         // 16/9 of the 9-tap bytes
-            off += (size_t)16 * l.cout * l.cin * sizeof(float);
-        }
-        if (l.kind == kIgemm && (need & kFormWino4) && use_wino && use_wino4 && wino4_layer(l.hs, l.ho, l.c0, l.c1, l.cout, l.stride, l.up, l.up4, dtype, l.inorm)) {
-            off = align_up(off, 256);
-            l.ww4_off = (int64_t)off;                         // 36/9 of the 9-tap bytes
-            off += (size_t)36 * l.cout * l.cin * sizeof(float);
-        }
-        if (l.kind == kIgemm && (need & kFormWinoUp) && use_wino && use_winoup && winoup_layer(l.hs, l.c0, l.c1, l.cout, l.up4 || l.up, dtype, l.inorm)) {
-            off = align_up(off, 256);
-            l.wwu_off = (int64_t)off;
-            off += (size_t)9 * l.cout * l.cin * sizeof(float);
-        }
-        if (l.kind == kIgemm && (need & kFormRowUp) && rowup_layer(l.hs, l.c0, l.c1, l.cout, l.up4, dtype, l.inorm)) {
-            off = align_up(off, 256);
-            l.wru_off = (int64_t)off;
-            off += (size_t)16 * l.cout * l.cin * elt();
-        }
-        if (l.kind == kIgemm && (need & kFormBand) && bandconv_layer(l.ho, l.c0, l.c1, l.cout, l.stride, l.up, l.up4, dtype, l.inorm)) {
-            off = align_up(off, 256);
-            l.wbc_off = (int64_t)off;
-            off += (size_t)l.cout * 9 * l.cin * elt();
-        }
-        if (l.kind == kIgemm && (need & kFormRow) && rowconv_layer(l.ho, l.c0, l.c1, l.cout, l.stride, l.up, l.up4, dtype, l.inorm)) {
-            off = align_up(off, 256);
-            l.wrc_off = (int64_t)off;
-            off += (size_t)l.cout * 9 * l.cin * elt();
-        }
         if (!l.bnkey.empty() || !l.biaskey.empty()) {   // a conv bias travels as (scale 1, shift bias)
-            off = align_up(off, 256);
-            l.scale_off = (int64_t)off; off += (size_t)l.cout * sizeof(float);
-            off = align_up(off, 256);
-            l.shift_off = (int64_t)off; off += (size_t)l.cout * sizeof(float);
+            l.scale_off = take((size_t)l.cout * sizeof(float));
+            l.shift_off = take((size_t)l.cout * sizeof(float));
         }
     }
     blob_bytes = align_up(off, 256);
 }
-
-
 
 int64_t Plan::layer_flops(const LayerDesc &l) const { return 2ll * l.cout * l.cin * 9 * l.ho * l.ho; }
 
@@ -525,73 +709,20 @@ BatchLayout layout_for(const Plan &p, int batch, std::vector<size_t> *offsets, s
                     a.release(off[t], bytes_of(p.tensors[t]));
                 }
         if (l.kind == kIgemm) {
-            int bm, bn, splits, group;
+            const RouteChoice c = choose_route(p, l, batch);
+            const int bm = c.bm, bn = c.bn, splits = c.splits;
             const int Mout = batch * l.ho * l.ho;
             const int M = l.up4 ? batch * l.hs * l.hs : Mout;
-            choose_tiling(M, l.cout, (l.up4 ? 4 : 9) * l.cin / p.ktile_channels(), l.up4 ? 4 : 1, l.up, p.dtype, &bm, &bn, &splits, &group);
-            const bool smallm = !l.up4 && smallm_eligible(M, l.cin, l.c1, l.cout, (size_t)batch * l.hs * l.hs * l.cin * 4, p.dtype == 0 ? p.smallm_kb : 64);
-            if (smallm) { bm = bn = 1; splits = 1; group = 1; }
-            // (every kernel choice below looks only at the offset of the weight form IT reads: the blob of a handle carries just the forms its
-            // batch range uses, Plan::build)
-            int fullk = smallm ? 0 : fullk_choice(batch, l.hs, l.ho, l.c0, l.c1, l.cout, l.stride, l.up, l.up4, p.dtype);
-            bool fullk_k2 = false;
-            if (fullk) {
-                const bool want = p.use_fullk_split && fullk_split(batch, l.ho, l.c0, l.c1, l.cout, fullk, p.fullk_split_max_tiles);
-                if (want && (l.c1 ? l.wfk_off >= 0 : l.wfk2_off >= 0)) fullk_k2 = true;
-                else if (l.wfk_off < 0) fullk = 0;
-            }
-            const bool fullk_s2 = !fullk && !smallm && p.use_fullk_s2 && p.use_fullk_split && l.wfk2_off >= 0 &&
-                                  fullk_s2_layer(l.hs, l.ho, l.c0, l.c1, l.cout, l.stride, l.up, l.up4, p.dtype, l.inorm) &&
-                                  fullk_s2_choice(batch, l.hs, l.ho, l.c0, l.cout, p.use_fullk_s2) > 0;
-            if (fullk_s2) { fullk = 1; bm = 16; bn = 16; splits = 2; group = 1; }
-            else if (fullk) { bm = 16 * fullk; bn = 16; splits = fullk_k2 ? 2 : 1; group = 1; }
-            // 16-bit plans: the same single-launch structure, whole K per workgroup, no split (fullk16.hip)
-            const int fullk16 = (p.dtype != 0 && !smallm && l.wfk_off >= 0)
-                                    ? fullk16_choice(batch, l.hs, l.ho, l.c0, l.c1, l.cout, l.stride, l.up, l.up4, p.dtype, p.fullk16_levels, p.fullk16_min_frames) : 0;
-            if (fullk16) { fullk = fullk16; bm = 16 * fullk16; bn = 16; splits = 1; group = 1; }
-            int wsplits = 1;
-            int w4splits = 1;
-            const int wino4 = (p.use_wino && p.use_wino4 && l.ww4_off >= 0 && !smallm) ? wino4_choice(batch, l.ho, l.cin, l.cout, &w4splits) : 0;
-            const int wino = (!wino4 && p.use_wino && l.wwg_off >= 0 && !smallm) ? wino_choice(batch, l.ho, l.cin, l.cout, &wsplits) : 0;
-            if (wino) { bm = 32; bn = 32 * wino; splits = wsplits; group = 1; }
-            if (wino4) { bm = 32; bn = 32; splits = w4splits; group = 1; }
-            int usplits = 1;
-            const int winoup = (p.use_wino && p.use_winoup && l.wwu_off >= 0) ? winoup_choice(batch, l.hs, l.cin, l.cout, &usplits, p.winoup_nb, p.winoup_target, !l.up4) : 0;
-            if (winoup) { bm = 32; bn = 32 * winoup; splits = usplits; group = 1; }
-            const int rowconv = p.use_rowconv && l.wrc_off >= 0 ? rowconv_rows(batch, l.ho, l.ho, l.c0) : 0;
-            if (rowconv) { bm = (l.c0 == 64 ? 64 : 32) * rowconv; bn = l.c0; splits = 1; group = 1; }
-            int rowup = p.use_rowup && l.wru_off >= 0 ? rowup_rows(batch, l.hs, l.hs) : 0;
-            if (rowup < 8) rowup = 0;     // short strips (1 frame: 4 rows + 2 halo steps) do not beat the implicit GEMM: 22.4 vs 22.9 us
-            if (rowup) { bm = 32 * rowup; bn = 32; splits = 1; group = 1; }
-            const bool bandconv = p.use_bandconv && l.wbc_off >= 0 && !smallm && !fullk16 &&
-                                  (l.ho >= 8 ? (long)batch * (l.ho == 16 ? 4 : 2) * (l.cout / 32) >= p.bandconv_min_blocks
-                                             : batch >= p.bandconv_min_frames_small);
-            if (bandconv) { bm = l.ho == 16 ? 64 : 32; bn = 32; splits = 1; group = 1; }
-            int pbn = 0;
-            int patch16 = (p.use_patch16 && !smallm && !fullk && !rowconv && !bandconv)
-                              ? patch16_choice(batch, l.ho, l.c0, l.c1, l.cout, l.stride, l.up, l.up4, p.dtype, l.inorm, p.patch16_min_blocks, &pbn) : 0;
-            int patchup16 = 0;
-            if (!patch16 && p.use_patch16 && p.use_patchup16 && !smallm && !fullk && !rowup && !winoup)
-                patchup16 = patchup16_choice(batch, l.hs, l.c0, l.c1, l.cout, l.up4, p.dtype, l.inorm, p.patch16_min_blocks, &pbn);
-            if (patch16 || patchup16) {
-                // the launchers' own limits (32-bit buffer offsets: 2 GiB per tensor) decide too, like wino_choice(): a shape the launch would
-                // refuse keeps the implicit GEMM instead of failing during graph capture
-                PatchConvParams q{};
-                q.B = batch; q.H = q.W = patch16 ? l.ho : l.hs; q.C = l.c0; q.C1 = l.c1; q.Cout = l.cout; q.dtype = p.dtype;
-                q.src1 = l.c1 ? &q : nullptr;        // (only tested for presence)
-                if (patch16 ? !patch16_supported(q, patch16, pbn) : !patchup16_supported(q, patchup16, pbn)) patch16 = patchup16 = 0;
-            }
-            if (patch16 || patchup16) { bm = 256; bn = pbn; splits = 1; group = 1; }
+            const bool wino_family = c.route == kRouteWino || c.route == kRouteWino4 || c.route == kRouteWinoUp;
             int route = kInNone;
             if (l.inorm) {
                 // rows of one wave (32 per 32x32 tile row, bm / 2 waves... = bm / 2 for the 2x2-wave tiles) must stay inside one
                 // frame for the epilogue sums; tiny levels do statistics + normalisation in one workgroup per channel slab
                 const int hw = l.ho * l.ho, rhw = l.up4 ? l.hs * l.hs : hw;
-                const int wave_rows = in_fused_wave_rows(bm);
-                if (!smallm && !fullk && !wino && !wino4 && !winoup && in_fused_eligible(bm, splits, rhw)) {
+                if (c.route == kRouteIgemm && in_fused_eligible(bm, splits, rhw)) {
                     route = kInFused;
-                    groups_max = std::max(groups_max, (l.up4 ? 4 : 1) * rhw / wave_rows);
-                } else if ((wino || winoup) && !wino4 && p.in_wino_stats) {
+                    groups_max = std::max(groups_max, (l.up4 ? 4 : 1) * rhw / in_fused_wave_rows(bm));
+                } else if ((c.route == kRouteWino || c.route == kRouteWinoUp) && p.in_wino_stats) {
                     // one group per tile-block of 8 x 16 output pixels; also at 32 x 32 and below, where in_small would put a 512-channel frame on 16 workgroups
                     // (57.9 -> 33 us per layer at 32 x 32, batch 1)
                     route = kInWino;
@@ -605,14 +736,15 @@ BatchLayout layout_for(const Plan &p, int batch, std::vector<size_t> *offsets, s
                 cmax = std::max(cmax, l.cout);
             }
             if (tiled) {
+                LayerDesc &t = (*tiled)[li];
                 const long tiles = (long)(l.up4 ? 4 : 1) * ((M + bm - 1) / std::max(bm, 1)) * ((l.cout + bn - 1) / std::max(bn, 1));
-                (*tiled)[li].wino = wino;
-                (*tiled)[li].wino4 = wino4;
-                (*tiled)[li].winoup = winoup;
-                (*tiled)[li].fused_splitk = (wino || wino4 || winoup) ? splits > 1 : (p.dtype == 0 || p.fused_splitk16) && !rowconv && !bandconv && !rowup && !smallm && !fullk && !l.inorm && splits >= 2 && splits <= 8 && tiles <= (long)Plan::kTileCounters &&
-                                            (size_t)splits * Mout * l.cout * sizeof(float) < (size_t)0x7fffffff;
-                (*tiled)[li].bm = bm; (*tiled)[li].bn = bn; (*tiled)[li].splits = splits; (*tiled)[li].group = group;
-                (*tiled)[li].smallm = smallm; (*tiled)[li].in_route = route; (*tiled)[li].fullk = fullk; (*tiled)[li].rowconv = rowconv; (*tiled)[li].bandconv = bandconv; (*tiled)[li].rowup = rowup; (*tiled)[li].patch16 = patch16 ? patch16 : patchup16;
+                t.route = c.route; t.route_arg = c.arg;
+                t.bm = bm; t.bn = bn; t.splits = splits; t.group = c.group;
+                t.in_route = route;
+                // the Winograd kernels always combine their K slices inside the launch; the implicit GEMM does for 2..8 slices of an fp32 plan
+                t.fused_splitk = wino_family ? splits > 1
+                                             : c.route == kRouteIgemm && (p.dtype == 0 || p.fused_splitk16) && !l.inorm && splits >= 2 && splits <= 8 &&
+                                                   tiles <= (long)Plan::kTileCounters && (size_t)splits * Mout * l.cout * sizeof(float) < (size_t)0x7fffffff;
             }
             if (splits > 1) partial = std::max(partial, (size_t)splits * Mout * l.cout * sizeof(float));
         }
@@ -668,12 +800,15 @@ std::string Plan::pack(void *blob, size_t bytes) const
     char *base = static_cast<char *>(blob);
     auto get = [&](const std::string &k) -> const ParamDesc & { return params[param_index.at(k)]; };
     for (const auto &l : layers) {
+        // where a form of this layer goes (nullptr: this handle's blob does not carry it)
+        auto f32_at = [&](WeightForm f) { return l.form_off[f] >= 0 ? reinterpret_cast<float *>(base + l.form_off[f]) : nullptr; };
+        auto u16_at = [&](WeightForm f) { return l.form_off[f] >= 0 ? reinterpret_cast<uint16_t *>(base + l.form_off[f]) : nullptr; };
         const float *W = get(l.wkey).data.data();           // OIHW
         // igemm-family weights are stored in the plan's dtype; staged in fp32 then narrowed (RNE) if bf16
         const bool narrow = dtype != 0 && layer_weights_typed(l);
         const size_t wcount = (size_t)l.cout * l.cin * ((l.up4 || l.kind == kLastConv) ? 16 : 9);
         // the row form ([co][tap][ci], sub-pixel rows, or the first conv's [ci][tap][co]) is always staged on the host: every other form is derived
-        // from it (or from W), and it is copied into the blob only where a kernel reads it (w_off >= 0)
+        // from it (or from W), and it is copied into the blob only where a kernel reads it (form_off[kFormRows] >= 0)
         std::vector<float> stage_buf(wcount);
         float *dst = stage_buf.data();
         std::vector<uint16_t> rows16;                        // the same values in the plan's 16-bit storage type (RNE), for the forms regrouped from them
@@ -698,11 +833,10 @@ std::string Plan::pack(void *blob, size_t bytes) const
                                     dst[(((size_t)(py * 2 + px) * cout + co) * 4 + a * 2 + b) * cin + ci] = (float)acc;
                                 }
                         }
-            if (l.wwu_off >= 0) pack_winoup_weights(W, cin, cout, reinterpret_cast<float *>(base + l.wwu_off));
-            if (last_as_gemm(l) && l.wgemm_off >= 0) {
+            if (float *d = f32_at(kFormWinoUp)) pack_winoup_weights(W, cin, cout, d);
+            if (uint16_t *g = u16_at(kFormGemmLast)) {
                 // the same pre-summed taps as one 3x3 conv on the LOW-res source: output channel par*cout + co, tap
                 // (a, b) of parity (py, px) sits at low-res offset (py - 1 + a, px - 1 + b); the other taps are zero
-                uint16_t *g = reinterpret_cast<uint16_t *>(base + l.wgemm_off);
                 for (int par = 0; par < 4; ++par)
                     for (int co = 0; co < cout; ++co)
                         for (int a = 0; a < 2; ++a)
@@ -711,8 +845,7 @@ std::string Plan::pack(void *blob, size_t bytes) const
                                 for (int ci = 0; ci < cin; ++ci)
                                     g[(((size_t)par * cout + co) * 9 + tap) * cin + ci] = narrow16(dst[(((size_t)par * cout + co) * 4 + a * 2 + b) * cin + ci], dtype);
                             }
-                if (l.wrl_off >= 0)     // (the blob is zero-filled, so the untouched taps of g are zeros)
-                    pack_rowlast_weights(g, reinterpret_cast<uint16_t *>(base + l.wrl_off), 4 * cout);
+                if (uint16_t *d = u16_at(kFormRowLast)) pack_rowlast_weights(g, d, 4 * cout);     // (the blob is zero-filled, so the untouched taps of g are zeros)
             }
         } else if (l.kind == kIgemm) {
             // [co][tap][ci]  -- the implicit-GEMM B operand, K contiguous per output channel
@@ -720,11 +853,11 @@ std::string Plan::pack(void *blob, size_t bytes) const
                 for (int ci = 0; ci < cin; ++ci)
                     for (int t = 0; t < 9; ++t)
                         dst[((size_t)co * 9 + t) * cin + ci] = W[((size_t)co * cin + ci) * 9 + t];
-            if (l.wfk_off >= 0 && dtype == 0) pack_fullk_weights(dst, l.c0, l.c1 ? 2 : 1, cout, reinterpret_cast<float *>(base + l.wfk_off));
-            if (l.wfk2_off >= 0) pack_fullk_weights(dst, l.c0 / 2, 2, cout, reinterpret_cast<float *>(base + l.wfk2_off));
-            if (l.wwg_off >= 0) pack_wino_weights(W, cin, cout, reinterpret_cast<float *>(base + l.wwg_off));
-            if (l.ww4_off >= 0) pack_wino4_weights(W, cin, cout, reinterpret_cast<float *>(base + l.ww4_off));
-            if (l.wwu_off >= 0) pack_winoup_weights(W, cin, cout, reinterpret_cast<float *>(base + l.wwu_off));      // an up-conv below the sub-pixel extent that larger batches run on winoup3x3
+            if (float *d = f32_at(kFormFullK); d && dtype == 0) pack_fullk_weights(dst, l.c0, l.c1 ? 2 : 1, cout, d);
+            if (float *d = f32_at(kFormFullK2)) pack_fullk_weights(dst, l.c0 / 2, 2, cout, d);
+            if (float *d = f32_at(kFormWino)) pack_wino_weights(W, cin, cout, d);
+            if (float *d = f32_at(kFormWino4)) pack_wino4_weights(W, cin, cout, d);
+            if (float *d = f32_at(kFormWinoUp)) pack_winoup_weights(W, cin, cout, d);      // an up-conv below the sub-pixel extent that larger batches run on winoup3x3
         } else if (l.kind == kFirstConv) {
             // [ci][tap][co]  -- broadcast rows for the direct first-layer kernel
             for (int co = 0; co < cout; ++co)
@@ -735,18 +868,15 @@ std::string Plan::pack(void *blob, size_t bytes) const
         if (narrow) {
             rows16.resize(wcount);
             for (size_t i = 0; i < wcount; ++i) rows16[i] = narrow16(stage_buf[i], dtype);    // round to nearest even
-            if (l.w_off >= 0) std::memcpy(base + l.w_off, rows16.data(), wcount * sizeof(uint16_t));
-        } else if (l.w_off >= 0) {
-            std::memcpy(base + l.w_off, stage_buf.data(), wcount * sizeof(float));
+            if (l.form_off[kFormRows] >= 0) std::memcpy(base + l.form_off[kFormRows], rows16.data(), wcount * sizeof(uint16_t));
+        } else if (l.form_off[kFormRows] >= 0) {
+            std::memcpy(base + l.form_off[kFormRows], stage_buf.data(), wcount * sizeof(float));
         }
-        if (l.wru_off >= 0)
-            pack_rowup_weights(rows16.data(), reinterpret_cast<uint16_t *>(base + l.wru_off));
-        if (l.wfk_off >= 0 && dtype != 0 && l.kind == kIgemm)     // 16-bit plans: the narrowed rows regrouped into the tile-blocked order of conv3x3_fullk16
-            pack_fullk16_weights(rows16.data(), l.c0, l.c1 ? 2 : 1, cout, reinterpret_cast<uint16_t *>(base + l.wfk_off));
-        if (l.wbc_off >= 0)
-            pack_bandconv_weights(rows16.data(), reinterpret_cast<uint16_t *>(base + l.wbc_off), cout);
-        if (l.wrc_off >= 0)     // the same bf16 values, regrouped into the MFMA A-fragments the row kernel keeps in registers
-            pack_rowconv_weights(rows16.data(), reinterpret_cast<uint16_t *>(base + l.wrc_off), l.c0);
+        // 16-bit plans: the narrowed rows regrouped into the order each kernel reads (fullk16: tile blocks; rowconv: the MFMA A-fragments it keeps in registers)
+        if (uint16_t *d = u16_at(kFormRowUp)) pack_rowup_weights(rows16.data(), d);
+        if (uint16_t *d = u16_at(kFormFullK); d && dtype != 0 && l.kind == kIgemm) pack_fullk16_weights(rows16.data(), l.c0, l.c1 ? 2 : 1, cout, d);
+        if (uint16_t *d = u16_at(kFormBand)) pack_bandconv_weights(rows16.data(), d, cout);
+        if (uint16_t *d = u16_at(kFormRow)) pack_rowconv_weights(rows16.data(), d, l.c0);
         if (!l.biaskey.empty()) {
             const float *bv = get(l.biaskey).data.data();
             float *sc = reinterpret_cast<float *>(base + l.scale_off);

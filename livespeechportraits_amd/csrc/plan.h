@@ -27,6 +27,26 @@ struct TensorDesc {        // an activation tensor in the workspace (NHWC)
     size_t offset = 0;     // byte offset in the workspace for the planned batch
 };
 
+// which kernel runs a conv layer of the net body (LayerKind kIgemm) at the planned batch.  Exactly one per layer: choose_route() (plan.cpp) is
+// the only place that decides, run_layer / kernel_name (api.cpp) and route_form() switch on it
+enum ConvRoute { kRouteIgemm, kRouteSmallM, kRouteFullK, kRouteFullK16, kRouteWino, kRouteWino4, kRouteWinoUp,
+                 kRouteRowUp, kRouteRowConv, kRouteBand, kRoutePatch16, kRoutePatchUp16 };
+// the layouts a layer's weights can be packed in; the values are the ids of lspf2f_layer_form_offset() (include/lspf2f.h, _native.FORM_IDS)
+enum WeightForm {
+    kFormRows = 0,      // [co][tap][ci] rows of the implicit GEMM (sub-pixel rows for up4 / the last conv, [ci][tap][co] for the first conv)
+    kFormFullK = 1,     // the tile-blocked layout of the full-K kernels (fullk.hip fp32, fullk16.hip 16-bit)
+    kFormFullK2 = 2,    // fp32: the same with a single source packed as two half-sources (the K-split form and the stride-2 convs)
+    kFormWino = 3,      // G g G^T in the fragment order of wino.hip
+    kFormWino4 = 4,     // the 6x6 G g G^T in the order of the F(4x4,3x3) kernel (wino4.hip)
+    kFormWinoUp = 5,    // the 9 transformed taps in the fragment order of winoup.hip
+    kFormRowUp = 6,     // 16-bit: fragment order of rowup256 (rowconv.hip)
+    kFormBand = 7,      // 16-bit: fragment order of bandconv.hip
+    kFormRow = 8,       // 16-bit: fragment order of the weights-stationary kernels (rowconv.hip)
+    kFormGemmLast = 9,  // 16-bit, last conv: the sub-pixel weights as a 9-tap [4*cout][3][3][cin] GEMM operand
+    kFormRowLast = 10,  // 16-bit, last conv over two 64-channel sources: that operand in the fragment order of rowlast128 (rowconv.hip)
+    kNumForms
+};
+
 struct LayerDesc {
     std::string name;
     LayerKind kind = kIgemm;
@@ -42,33 +62,33 @@ struct LayerDesc {
     std::string biaskey;   // state-dict key of the conv bias ("" = none; InstanceNorm plans: the level convs, networks.py:590)
     bool inorm = false;    // an InstanceNorm2d (affine=False, eps 1e-5) follows the conv: per-(frame, channel) statistics at run time
     int in_route = 0;      // per-batch: how those statistics are gathered (kInFused / kInReduce / kInSmall)
-    int64_t w_off = -1, scale_off = -1, shift_off = -1;   // byte offsets in the packed blob
-    int64_t wfk_off = -1;    // fp32 plans, 16x16 / 8x8 stride-1 layers: a second copy of the weights in the tile-blocked layout of the full-K kernel
-    int64_t wbc_off = -1;    // bf16 plans, 512 -> Cout stride-1 layers at 16x16 / 8x8: a copy of the weights in the fragment order of bandconv.hip
-    int64_t wrc_off = -1;    // bf16 plans, 64 -> 64 stride-1 layers: a copy of the weights in the fragment order of the weights-stationary kernel (rowconv.hip)
-    int64_t wru_off = -1;    // bf16 plans, sub-pixel up-conv over two 128-channel sources -> 64 channels (L1.up): weights in the fragment order of rowup256
-    int64_t wfk2_off = -1;   // fp32 plans, single-source 8x8 layers: the full-K kernel's weights packed as two half-sources (its K-split form at batch 1)
-    int64_t wrl_off = -1;    // bf16 plans, last conv over two 64-channel sources: the GEMM-form weights in the fragment order of rowlast128 (rowconv.hip)
-    int64_t wwg_off = -1;    // fp32 plans, stride-1 single-source convs at >= 32x32: G g G^T in the fragment order of the Winograd kernel (wino.hip)
-    int64_t ww4_off = -1;    // fp32 plans, stride-1 single-source convs at >= 32x32 (extent % 32 == 0): the 6x6 G g G^T in the order of the F(4x4,3x3) kernel (wino4.hip)
-    int64_t wwu_off = -1;    // fp32 plans, sub-pixel up-convs over two equally wide sources: the 9 transformed taps in the fragment order of winoup.hip
-    int64_t wgemm_off = -1;  // bf16 plans, last conv only: the same sub-pixel weights as a 9-tap [4*cout][3][3][cin] bf16 GEMM operand
-    // per-batch tiling decision
-    int bm = 0, bn = 0, splits = 1, group = 1;   // group = K-tiles per pipeline step
-    bool smallm = false;   // executed by the single-launch tiny-M kernel (M <= 16) instead of the igemm
+    int64_t form_off[kNumForms] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // byte offsets in the packed blob (-1: this handle's blob does not carry the form)
+    int64_t scale_off = -1, shift_off = -1;
+    // per-batch decision (choose_route)
+    ConvRoute route = kRouteIgemm;
+    int route_arg = 0;     // SmallM 1 | FullK, FullK16: 16-pixel blocks per tile | Wino, WinoUp: 32-channel blocks per wave | Wino4 1 | RowUp: low-res rows per strip |
+                           // RowConv: output rows per strip | Band 1 | Patch16, PatchUp16: tile width in pixels
+    int bm = 0, bn = 0, splits = 1, group = 1;   // the route's tile; splits = its K splits; group = K-tiles per pipeline step
     bool fused_splitk = false;   // fp32 plans: 2..8 K-splits combined inside the igemm launch by the last-arriving workgroup (no splitk_reduce
                                  // launch): +1.0 % at fp32 batch 1, none at batch 8, -2.4 % on bf16 batch 8 (A-B-A-B, one session; restricted
                                  // to the <= 16x16 / <= 8x8 levels of a bf16 plan it still loses 0.7-0.9 %)
-    bool bandconv = false;  // executed by the activation-stationary kernel of the 16x16 / 8x8 levels (bandconv.hip, bf16 plans)
-    int rowup = 0;         // > 0: executed by rowup256 (rowconv.hip) with this many low-res rows per strip
-    int rowconv = 0;       // > 0: executed by the weights-stationary 64 -> 64 bf16 kernel (rowconv.hip) with this many output rows per strip
-    int wino = 0;          // > 0: executed by the Winograd F(2x2,3x3) kernel (wino.hip) with this many 32-channel blocks per wave (1 | 2); `splits` = its K splits
-    int wino4 = 0;         // 1: executed by the Winograd F(4x4,3x3) kernel (wino4.hip); `splits` = its K splits
-    int winoup = 0;        // > 0: executed by the up-conv Winograd kernel (winoup.hip) with this many 32-channel blocks per wave; `splits` = its K splits
-    int patch16 = 0;       // > 0: executed by the patch-staged 16-bit kernel (patch16.hip) with this tile width (64 | 32 pixels; 4 | 8 rows); bn = channels per workgroup
-    int fullk = 0;         // > 0: executed by the full-K single-launch kernel (fullk.hip) with this many 16-pixel blocks per tile
-                           // (splits == 2 with it: K in two halves over twice the workgroups, combined in the launch)
 };
+// the weight form the kernel of a (batch-planned) layer reads
+inline WeightForm route_form(const LayerDesc &l)
+{
+    switch (l.route) {
+    case kRouteFullK: return (l.stride == 2 || (l.splits == 2 && !l.c1)) ? kFormFullK2 : kFormFullK;
+    case kRouteFullK16: return kFormFullK;
+    case kRouteWino: return kFormWino;
+    case kRouteWino4: return kFormWino4;
+    case kRouteWinoUp: return kFormWinoUp;
+    case kRouteRowUp: return kFormRowUp;
+    case kRouteBand: return kFormBand;
+    case kRouteRowConv: return kFormRow;
+    case kRouteIgemm: case kRouteSmallM: case kRoutePatch16: case kRoutePatchUp16: break;
+    }
+    return kFormRows;
+}
 
 struct ParamDesc {         // an expected state-dict entry
     std::string key;
@@ -86,7 +106,7 @@ struct Plan {
                                // the storage type, so an fp16 plan takes the same kernel per layer as the bf16 plan)
     int norm = 0;              // 0: BatchNorm2d in eval mode (folded, the shipped checkpoints); 1: InstanceNorm2d (norm_layer argument
                                // of the reference constructors, networks.py:555 / :459): conv biases on, statistics at run time, fp32 only
-    int fullk16_levels = 3;    // 16-bit plans: which small levels run on the full-K kernel (fullk16.hip; tune key `fullk16`, bit mask as in fullk16_choice(); 0 = none)
+    int fullk16_levels = 3;    // 16-bit plans: which small levels run on the full-K kernel (fullk16.hip; tune key `fullk16`, bit mask as in fullk16_choice(), plan.cpp; 0 = none)
     int fullk16_min_frames = 2; // ... from this many frames up (tune key `fullk16_min_frames`)
     bool use_bandconv = true;  // bf16 plans: tune key `bandconv=0` puts the 16x16 / 8x8 layers back on the implicit GEMM (A-B runs)
     int bandconv_min_blocks = 128;  // (16x16 / 8x8 levels; the 4x4 / 2x2 levels, one tile per 2 / 8 frames, have their own bound below)
@@ -108,7 +128,7 @@ struct Plan {
     bool use_fullk_split = true;   // the 8x8 layers at batch 1 run the full-K kernel with K in two halves over twice the workgroups (tune key `fullk_split=0` at
                                    // create: unsplit, A-B runs)
     bool use_wino = true;      // fp32 plans: stride-1 convs at >= 32x32 on the Winograd kernel (tune key `wino=0`: the implicit GEMM, A-B runs)
-    bool use_wino4 = false;    // fp32 plans: ... and of those the layers wino4_choice() takes on the F(4x4,3x3) kernel (LSPF2F_FLAG_WINO4; measured slower at batch 1 and
+    bool use_wino4 = false;    // fp32 plans: ... and of those the layers choose_route() gives to the F(4x4,3x3) kernel (LSPF2F_FLAG_WINO4; measured slower at batch 1 and
                                // equal at batch 8, DESIGN.md 4.11, so off by default); decides whether the blob carries the 6x6 transformed weights
     int in_small_max_hw = 1024;  // `in_small_max_hw`: InstanceNorm plans take the one-launch route (in_small: one workgroup per (frame, 32 channels)) up to this many pixels per frame; above it
                                  // in_reduce_stats + in_finalize + in_apply spread the frame over the chip
@@ -158,10 +178,8 @@ struct Plan {
     // max_batch_forms > 0: the blob carries only the weight forms the plans of batch 1 .. max_batch_forms read (0: every form)
     std::string build(int variant, int input_nc, int feat_nc, int output_nc, int ngf, int num_downs,
                       int size, bool keep, int dtype = 0, int norm = 0, int max_batch_forms = 0);   // returns "" or an error message
-    // weight forms a layer can be packed in (bit mask)
-    enum : unsigned { kFormRows = 1, kFormFullK = 2, kFormFullK2 = 4, kFormWino = 8, kFormWino4 = 16, kFormWinoUp = 32, kFormRowUp = 64,
-                      kFormBand = 128, kFormRow = 256, kFormGemmLast = 512 };
-    static unsigned forms_used(const LayerDesc &tiled, const Plan &p);   // which form the kernel chosen for a (batch-planned) layer reads
+    static unsigned forms_used(const LayerDesc &tiled, const Plan &p);   // bit mask (1u << WeightForm) of the forms the kernel(s) of a (batch-planned) layer read
+    size_t form_bytes(const LayerDesc &l, WeightForm f) const;           // size of a layer's weights in that form
     void assign_offsets(const std::vector<unsigned> *used);               // lays the blob out with the forms of `used` (nullptr: every form)
     int blob_pad_kb = 0;           // tune key `blob_pad_kb` (tools): empty KB in front of the first layer's weights
     bool keep_all_forms = false;   // tune key `all_forms=1`: every form whatever the batch range (tests that look at forms other batches would use)
@@ -184,159 +202,26 @@ void choose_tiling(int M, int N, int ktiles, int par, bool up9, int dtype, int *
 // sub-pixel up-conv).  Shared by the planner and lspf2f_conv3x3_instnorm.
 inline int in_fused_wave_rows(int bm) { return bm == 32 ? 32 : bm / 2; }
 inline bool in_fused_eligible(int bm, int splits, int rhw) { return splits == 1 && rhw >= 1024 && rhw % in_fused_wave_rows(bm) == 0; }
-// tiny-M kernel eligibility (mirrors smallm_supported() in small_layers.hip)
-inline bool smallm_eligible(int M, int cin, int c1, int cout, size_t in_bytes, int max_kb = 64)
-{
-    return M <= 16 && c1 == 0 && cin % 256 == 0 && 9 * (cin / 4) <= 5 * 256 && in_bytes <= (size_t)max_kb * 1024 && cout % 2 == 0;
-}
-// weights-stationary kernel eligibility (mirrors rowconv_supported() in rowconv.hip): bf16 storage, one source of 64 or 128 channels,
-// as many out, stride 1, no upsample, BatchNorm (folded) plans
-inline bool rowconv_layer(int ho, int c0, int c1, int cout, int stride, bool up, bool up4, int dtype, bool inorm)
-{
-    if (dtype == 0 || c1 != 0 || cout != c0 || stride != 1 || up || up4 || inorm) return false;      // 16-bit storage: bf16 (1) or fp16 (2)
-    return (c0 == 64 && ho % 64 == 0) || (c0 == 128 && ho % 32 == 0);
-}
-// row kernel of the sub-pixel up-conv (mirrors rowup_supported() in rowconv.hip)
-inline bool rowup_layer(int hs, int c0, int c1, int cout, bool up4, int dtype, bool inorm)
-{
-    return dtype != 0 && up4 && c0 == 128 && c1 == 128 && cout == 64 && !inorm && hs % 32 == 0;
-}
-// activation-stationary kernel eligibility (mirrors bandconv_supported() in bandconv.hip)
-inline bool bandconv_layer(int ho, int c0, int c1, int cout, int stride, bool up, bool up4, int dtype, bool inorm)
-{
-    return dtype != 0 && c0 == 512 && c1 == 0 && cout % 32 == 0 && stride == 1 && !up && !up4 && !inorm && (ho == 16 || ho == 8 || ho == 4 || ho == 2);
-}
-// patch-staged 16-bit kernel (mirrors patch16_supported() in patch16.hip): stride-1 single-source convs of >= 128 channels at 64x64 (tiles of 4 rows x 64 pixels) and
-// 32x32 (8 rows x 32); returns the tile width (0 = keep the implicit GEMM) and the channels per workgroup: 128 when that still fills the chip, else 64
-inline int patch16_choice(int batch, int ho, int c0, int c1, int cout, int stride, bool up, bool up4, int dtype, bool inorm, int min_blocks, int *bn)
-{
-    if (dtype == 0 || c1 != 0 || stride != 1 || up || up4 || inorm) return 0;
-    if ((ho != 64 && ho != 32) || c0 % 64 || c0 < 128 || cout % 64) return 0;
-    const long mtiles = (long)batch * ho * ho / 256;
-    if (cout % 128 == 0 && mtiles * (cout / 128) >= min_blocks) { *bn = 128; return ho == 64 ? 64 : 32; }
-    if (mtiles * (cout / 64) >= min_blocks) { *bn = 64; return ho == 64 ? 64 : 32; }
-    return 0;
-}
-// its sub-pixel up-conv form (mirrors patchup16_supported()): up4 layers over one source or two equally wide ones at a 64x64 / 32x32 LOW-res extent
-inline int patchup16_choice(int batch, int hs, int c0, int c1, int cout, bool up4, int dtype, bool inorm, int min_blocks, int *bn)
-{
-    if (dtype == 0 || !up4 || inorm || (c1 != 0 && c1 != c0)) return 0;
-    if ((hs != 64 && hs != 32 && hs != 16) || c0 % 64 || c0 + c1 < 128 || cout % 64) return 0;
-    const long mtiles = (long)batch * hs * hs / 256 * 4;
-    if (hs >= 32 && cout % 128 == 0 && mtiles * (cout / 128) >= min_blocks) { *bn = 128; return hs == 64 ? 64 : 32; }
-    if (mtiles * (cout / 64) >= min_blocks) { *bn = 64; return hs == 64 ? 64 : hs; }      // (16x16 sources: a tile = one whole low-res frame, 64 channels per workgroup only)
-    return 0;
-}
-// full-K kernel eligibility (mirrors fullk_supported() in fullk.hip); returns the pixel blocks per tile (1 | 2) or 0
-// which layers get the tile-blocked weight copy at pack time (independent of the batch: the blob layout must not depend on it)
-inline bool fullk_layer(int hs, int ho, int c0, int c1, int cout, int stride, bool up, bool up4, int dtype)
-{
-    if (dtype != 0 || stride != 1 || up4) return false;
-    if (ho != 2 && ho != 4 && ho != 8 && ho != 16) return false;     // (4x4 / 2x2 belong to the tiny-M kernel while the batch has <= 16 output pixels: fullk_choice)
-    if (up ? 2 * hs != ho : hs != ho) return false;
-    return (c0 == 128 || c0 == 256 || c0 == 512) && (c1 == 0 || c1 == c0) && cout % 128 == 0;
-}
-// the stride-2 convs of the small levels (outputs 16x16 / 8x8 / 4x4 from a single source of 256 | 512 channels) on the K-split full-K kernel: half the
-// channels of their 5-row band fit LDS.  Batch-independent part (who gets the half-source weight copy) and the per-batch choice (pixel blocks per tile or 0).
-inline bool fullk_s2_layer(int hs, int ho, int c0, int c1, int cout, int stride, bool up, bool up4, int dtype, bool inorm)
-{
-    return dtype == 0 && stride == 2 && !up && !up4 && !inorm && c1 == 0 && (c0 == 256 || c0 == 512) && cout % 128 == 0 &&
-           (ho == 16 || ho == 8 || ho == 4) && hs == 2 * ho;
-}
-inline int fullk_s2_choice(int batch, int hs, int ho, int c0, int cout, int level = 1)
-{
-    if (level == 2 && ho > 8) return 0;
-    if (batch != 1) return 0;                                 // measured at batch 1 only; from 2 frames up the implicit GEMM has rows enough
-    const int nr = 16 / ho;                                   // one 16-pixel block per tile
-    const long tiles = (long)batch * ((ho + nr - 1) / nr) * (cout / 16);
-    const int rows = std::min(2 * (nr - 1) + 3, hs);
-    if (((size_t)rows * hs + 1) * (c0 / 2 + 4) * sizeof(float) > 150 * 1024) return 0;
-    return tiles <= 512 ? 1 : 0;                              // 2 x tiles workgroups, one per CU at a time: up to four rounds
-}
-// K split of the full-K kernel: when its tiles fill at most half the chip (8x8 outputs at batch 1: 4 x cout / 16 = 128 tiles on 256 CUs) and the input
-// has two sources or one of >= 256 channels to halve
-inline bool fullk_split(int batch, int ho, int c0, int c1, int cout, int pb, int max_tiles = 128)
-{
-    if (ho != 8 && ho != 16) return false;
-    const int nr = pb * (16 / ho);
-    const long tiles = (long)batch * (ho / nr) * (cout / 16);
-    return tiles <= max_tiles && (c1 == c0 || (c1 == 0 && c0 >= 256));
-}
-inline int fullk_choice(int batch, int hs, int ho, int c0, int c1, int cout, int stride, bool up, bool up4, int dtype)
-{
-    if (!fullk_layer(hs, ho, c0, c1, cout, stride, up, up4, dtype)) return 0;
-    if (up ? 2 * hs != ho : hs != ho) return 0;
-    if ((c0 != 128 && c0 != 256 && c0 != 512) || (c1 != 0 && c1 != c0) || cout % 128) return 0;
-    // whole tiles must fit one dispatch wave of the chip with room to spare: <= 512 workgroups (2 per CU on 256 CUs)
-    const int ntn = cout / 16;
-    // 4x4 / 2x2 frames (a tile = one whole frame, 16 / 4 of its 16 rows used): from the batch the tiny-M kernel stops taking (> 16 output pixels) up.  Measured per layer,
-    // 512 -> 512 (tools/time_conv.py): 4x4 at 2 / 4 / 8 frames 9.1 / 8.9 / 9.3 us against 13.5 / 15.1 / 20.1 for igemm + reduce; 2x2 at 8 frames 8.7 against 13.7
-    if (ho <= 4 && (long)batch * ho * ho <= 16) return 0;
-    for (int pb = 1; pb <= (ho == 16 ? 2 : 1); ++pb) {
-        const int nr = pb * (16 / ho);
-        const long tiles = (long)batch * ((ho + nr - 1) / nr) * ntn;
-        // 8x8 frames: up to four rounds of workgroups still beat the split-K implicit GEMM (8 frames: 28.1 against 35.6 us)
-        if (ho == 8 && tiles > 512 && tiles <= 1024) return 1;
-        // the band of source rows behind a tile must fit the 150 KB of LDS fullk_supported() (fullk.hip) grants: (rows * Ws + 1 zero pixel) x (C0 + 4 pad)
-        // floats per source -- 133 KB for the widest shape the generators build (4 rows x 16 px x 512 ch)
-        const int rows = std::min(up ? nr / 2 + 2 : nr + 2, hs);
-        if ((size_t)(c1 ? 2 : 1) * ((size_t)rows * hs + 1) * (c0 + 4) * sizeof(float) > 150 * 1024) continue;
-        if (tiles <= 256 || (pb == (ho == 16 ? 2 : 1) && tiles <= 512)) return pb;
-    }
-    return 0;
-}
-// The 16-bit twin (fullk16.hip): the 8x8 / 4x4 / 2x2 levels of the bf16 / fp16 plans from 2 frames up -- stride 1, stride 2 (one source) or nearest x2 upsample in
-// front, one source of 256 | 512 channels or two equal ones.  Batch-independent part (who gets the tile-blocked 16-bit weight copy) and the per-batch choice
-// (pixel blocks per tile, or 0).  `levels` (tune key `fullk16`): bit 0 = the 4x4 / 2x2 levels, bit 1 = the stride-2 / upsampling convs that WRITE 8x8
-// (igemm + splitk_reduce otherwise), bit 2 = the stride-1 single-source 8x8 layers (bandconv512 otherwise).
-inline bool fullk16_layer(int hs, int ho, int c0, int c1, int cout, int stride, bool up, bool up4, int dtype, bool inorm)
-{
-    if (dtype == 0 || up4 || inorm) return false;
-    if (ho != 2 && ho != 4 && ho != 8) return false;
-    if (up) { if (stride != 1 || 2 * hs != ho) return false; }
-    else if (stride == 2) { if (hs != 2 * ho || c1 != 0) return false; }
-    else if (stride != 1 || hs != ho) return false;
-    return (c0 == 256 || c0 == 512) && (c1 == 0 || c1 == c0) && cout % 128 == 0;
-}
-inline int fullk16_choice(int batch, int hs, int ho, int c0, int c1, int cout, int stride, bool up, bool up4, int dtype, int levels = 3, int min_frames = 2)
-{
-    if (!fullk16_layer(hs, ho, c0, c1, cout, stride, up, up4, dtype, false) || batch < min_frames) return 0;
-    const int bit = ho <= 4 ? 1 : (up || stride == 2) ? 2 : 4;
-    if (!(levels & bit)) return 0;
-    const int nr = 16 / ho > 0 ? 16 / ho : 1;                 // output rows per 16-pixel block (a 4x4 / 2x2 frame is one block)
-    const long tiles = (long)batch * ((ho + nr - 1) / nr) * (cout / 16);
-    const int S = (!up && stride == 2) ? 2 : 1;
-    const int rows = std::min(up ? nr / 2 + 2 : S * (nr - 1) + 3, hs);
-    if ((size_t)(c1 ? 2 : 1) * ((size_t)rows * hs + 1) * (c0 * 2 + 16) > 150 * 1024) return 0;
-    return tiles <= 1024 ? 1 : 0;                             // up to four rounds of workgroups (8x8 at 8 frames), like the fp32 kernel
-}
-// Winograd kernel eligibility, batch-independent part (which layers get the G g G^T copy at pack time); the per-batch choice asks
-// wino_supported() itself (kernels.h) through wino_choice() in plan.cpp
-static const int kWinoMinExtent = 16;     // 16x16 only from 4 frames up (wino_choice): below that the full-K kernel is as fast
-inline bool wino_layer(int hs, int ho, int c0, int c1, int cout, int stride, bool up, bool up4, int dtype, bool inorm)
-{
-    // InstanceNorm plans too (inorm): the kernel then writes the raw conv output (+ bias) and the statistics come from the separate passes
-    (void)inorm;
-    return dtype == 0 && stride == 1 && !up && !up4 && c1 == 0 && hs == ho && ho >= kWinoMinExtent && ho % 16 == 0 &&
-           c0 % 8 == 0 && cout % 32 == 0;
-}
-// per batch: 32-channel blocks per wave (0 = keep the implicit GEMM) and K splits
-int wino_choice(int batch, int ho, int cin, int cout, int *splits);
-// the F(4x4, 3x3) kernel (wino4.hip): tile-blocks of 16 x 32 output pixels -> extents that are multiples of 32
-inline bool wino4_layer(int hs, int ho, int c0, int c1, int cout, int stride, bool up, bool up4, int dtype, bool inorm)
-{
-    return wino_layer(hs, ho, c0, c1, cout, stride, up, up4, dtype, inorm) && ho >= 32 && ho % 32 == 0;
-}
-// per batch: 1 (and the K splits) when the layer runs on it, 0 = keep wino_choice()'s answer
-int wino4_choice(int batch, int ho, int cin, int cout, int *splits);
-// the up-conv form (winoup.hip): sub-pixel up-convs of fp32 plans whose two sources are equally wide
-// (any Upsample + Conv3x3 layer: those below kUp4MinExtent keep their 9-tap rows for the full-K kernel / implicit GEMM and take this kernel from the batch where it wins)
-inline bool winoup_layer(int hs, int c0, int c1, int cout, bool up_any, int dtype, bool inorm)
-{
-    (void)inorm;
-    return dtype == 0 && up_any && (c1 == c0 || c1 == 0) && c0 % 8 == 0 && cout % 32 == 0 && hs % 8 == 0;
-}
-int winoup_choice(int batch, int hs, int cin, int cout, int *splits, int force_nb = 0, int target = 1024, bool small_level = false);
+
+// Who gets a weight form at pack time: the batch-independent half of each kernel family's rule (the blob layout must not depend on the batch).
+// Policy only -- which layers a family is FOR; extents, alignments and LDS bounds are the kernel's own *_supported() (kernels.h), asked here
+// for one frame and by choose_route() for the batch.  Also used by lspf2f_conv3x3 on a LayerDesc filled from its arguments.
+bool fullk_layer(const LayerDesc &l, int dtype);       // fp32 16x16 .. 2x2 stride-1 layers (incl. the nearest-upsampling up-convs below the sub-pixel extent)
+bool fullk_s2_layer(const LayerDesc &l, int dtype);    // fp32 stride-2 convs writing 16x16 / 8x8 / 4x4 from one source of 256 | 512 channels (K-split form only)
+bool fullk16_layer(const LayerDesc &l, int dtype);     // 16-bit 8x8 / 4x4 / 2x2 layers: stride 1, stride 2 (one source) or nearest x2 upsample in front
+bool wino_layer(const LayerDesc &l, int dtype);        // fp32 stride-1 single-source convs at >= 16x16
+bool wino4_layer(const LayerDesc &l, int dtype);       // ... of those the extents that are multiples of 32 (tile-blocks of 16 x 32 output pixels)
+bool winoup_layer(const LayerDesc &l, int dtype);      // fp32 up-convs (either form) over one source or two equally wide ones
+bool rowup_layer(const LayerDesc &l, int dtype);       // 16-bit sub-pixel up-conv over two 128-channel sources -> 64 channels (L1.up)
+bool rowconv_layer(const LayerDesc &l, int dtype);     // 16-bit stride-1 single-source convs with as many channels out as in (64 | 128)
+bool bandconv_layer(const LayerDesc &l, int dtype);    // 16-bit stride-1 512 -> Cout convs at 16x16 .. 2x2
+// per batch: pixel blocks per tile of the fp32 full-K kernel for a fullk_layer (0 = another kernel keeps it); shared with lspf2f_conv3x3's tile 0x0
+int fullk_choice(const LayerDesc &l, int batch, int dtype);
+static const int kWinoMinExtent = 16;  // 16x16 only from 4 frames up (choose_route): below that the full-K kernel is as fast
 static const int kUp4MinExtent = 32;   // up-convs writing >= 32x32 use the sub-pixel form
+
+// THE kernel choice of a body layer at a batch: the route, its argument (LayerDesc::route_arg) and its tile
+struct RouteChoice { ConvRoute route; int arg, bm, bn, splits, group; };
+RouteChoice choose_route(const Plan &p, const LayerDesc &l, int batch);
 
 }  // namespace lspf2f
