@@ -6,8 +6,8 @@
 //                (models/audio2headpose.py:16-21, BatchNorm1d folded) and ALL layers' cond_filter/cond_gate
 //                1x1 convs (models/networks.py:277-287) for every audio frame at once -- none of it depends
 //                on the sampled poses, so it leaves the sequential loop.
-//   a2h_stream   ONE persistent workgroup runs every time step of the loop: start convs, the gated residual
-//                layers evaluated incrementally (per-layer dilation queues in LDS), end convs, GMM sampling,
+//   a2h_stream   ONE persistent workgroup per stream (a table of streams; a clip is a table of one) runs every
+//                time step of the loop: start convs, the gated residual layers evaluated incrementally (per-layer dilation queues in LDS), end convs, GMM sampling,
 //                feedback.  The step-to-step dependence goes through the 12 sampled values, so there is no
 //                parallelism across steps or layers; the kernel is a chain of 256x256 / 384x128 mat-vecs
 //                whose weights (6.4 MB per step) stream from L2 in kernel-specific packed layouts, one
@@ -62,11 +62,8 @@ struct StreamParams {
     unsigned *status;                   // 0 ok, else the code of the first hand-off that timed out
     unsigned epoch;                     // tag of this call (never 0)
     int stride;                         // only blocks with blockIdx.x % stride == 0 work (8: all on one XCD, for speed only)
-    // stream kernel: resumable form (lspa2h_generate_resume); the whole-clip call has frame0 = 0, no states, ring = max_audio_frames
-    int frame0;                         // first frame of this call; out / noise / expq row 0 belongs to it
-    int ring;                           // proj holds audio row r at row r % ring
-    const float *state_in;              // null: start of the clip; else queues [qrows][128], inb [16], step counter (int bits)
-    float *state_out;                   // null, or where the state after the last step goes (same layout)
+    // stream kernel only; its per-stream tensors, states and step range are in the StreamTable
+    int ring;                           // a stream's proj holds audio row r at row r % ring
 };
 
 template <int CTRL> __device__ __forceinline__ float dpp_add(float v)
@@ -96,186 +93,8 @@ __device__ __forceinline__ float dot4(float4 w, float4 v, float acc)
     return acc;
 }
 
-__global__ __launch_bounds__(NT) void a2h_stream(StreamParams p)
-{
-    extern __shared__ float smem[];
-    float *xbuf = smem;                  // [128] current layer input
-    float *zbuf = xbuf + RC;             // [128] gated activation
-    float *tbuf = zbuf + RC;             // [128] start_conv1 output
-    float *sbuf = tbuf + RC;             // [256] lrelu(skip sum)
-    float *r1 = sbuf + SC;               // [64]  end_conv_1 output (lrelu applied)
-    float *r2 = r1 + MAX_OUT;            // [64]  end_conv_2 output
-    float *inb = r2 + MAX_OUT;           // [16]  WaveNet input of this step (head pose)
-    float *queue = inb + 16;             // [sum of dilations][128]
-    const int tid = threadIdx.x;
-
-    int qrows = 0;
-    for (int l = 0; l < p.layers; ++l) qrows += p.dil[l];
-    const int nsteps = p.field - 1 + p.frame0 + p.nframe;
-    int s0 = 0;                                      // start of a clip: every priming step, queues zero, input = pre
-    if (p.state_in) {                                // resumed: the state saved after step field - 1 + frame0 - 1
-        s0 = p.field - 1 + p.frame0;
-        if (__float_as_int(p.state_in[qrows * RC + 16]) != s0) {
-            if (tid == 0) atomicCAS(p.status, 0u, 0x5000000u);    // the state belongs to another frame: refuse, outputs untouched
-            return;
-        }
-        for (int i = tid; i < qrows * RC; i += NT) queue[i] = p.state_in[i];
-        if (tid < 16) inb[tid] = p.state_in[qrows * RC + tid];
-    } else {
-        for (int i = tid; i < qrows * RC; i += NT) queue[i] = 0.f;
-        if (tid < 16) inb[tid] = tid < p.ndim ? p.pre[tid] : 0.f;
-    }
-
-    const int fu = tid >> 3, fpart = tid & 7;        // fg item: channels fu and fu+64, 32-column part
-    const int rq = tid >> 2, rpart = tid & 3;        // rs item: rows rq, 128+rq, 256+rq, 32-column part
-    const unsigned fg_stride = 32 * NT * 16, rs_stride = 24 * NT * 16;   // bytes per layer
-    const __amdgpu_buffer_rsrc_t blob = __builtin_amdgcn_make_buffer_rsrc((void *)p.blob, 0, (int)p.blob_bytes, 0x00020000);
-    const int voff = tid * 16;
-    const int projN = p.layers * 256;
-
-    // Weight registers.  F + R together are 87 % of the CU's register file, so the next mat-vec's weights
-    // cannot all be in flight while the current set is live: half of the next set is requested before a
-    // set is consumed, the other half as soon as its registers are free.
-    float4 F[32], R[24];
-    load_packed<0, 32>(F, blob, p.fg_w, voff);
-    __syncthreads();
-
-    for (int s = s0; s < nsteps; ++s) {
-        int arow = s + p.frame_future - (p.field - 1);
-        arow = arow < 0 ? 0 : arow;                  // the reference prepends field-1 copies of audio row 0
-        const float *projrow = p.proj + (size_t)(arow % p.ring) * projN;
-        // ---- start convs (networks.py:198-199): 1x1, bias, LeakyReLU
-        if (tid < RC) {
-            float a = p.start1_b[tid];
-            for (int k = 0; k < p.ndim; ++k) a = fmaf(p.start1_w[tid * p.ndim + k], inb[k], a);
-            tbuf[tid] = lrelu(a);
-        }
-        __syncthreads();
-        {
-            float4 w[8];
-            load_packed<0, 8>(w, blob, p.start2_w, voff);
-            const float4 *v = reinterpret_cast<const float4 *>(tbuf + rpart * 32);
-            float a = 0.f;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) a = dot4(w[q], v[q], a);
-            a = sum4(a);
-            if (rpart == 0) xbuf[rq] = lrelu(a + p.start2_b[rq]);
-        }
-        float skip0 = 0.f, skip1 = 0.f;              // skip rows rq and 128+rq (leader lanes)
-        __syncthreads();
-
-        for (int l = 0; l < p.layers; ++l) {
-            const int d = p.dil[l];
-            float *qslot = queue + (size_t)(p.qoff[l] + (s & (d - 1))) * RC;   // holds x[t-d]; overwritten with x[t]
-            const unsigned rsw = p.rs_w + (unsigned)l * rs_stride;
-            load_packed<0, 16>(R, blob, rsw, voff);                                    // in flight during the fg mat-vec
-            float4 pb = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (fpart == 0) pb = *reinterpret_cast<const float4 *>(projrow + l * 256 + fu * 4);
-            // ---- filter/gate dilated convs + cond (networks.py:303-314): 256 rows x [x[t-d] ; x[t]]
-            {
-                const float4 *v = reinterpret_cast<const float4 *>((fpart < 4 ? qslot + fpart * 32 : xbuf + (fpart - 4) * 32));
-                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const float4 x = v[q];
-                    a0 = dot4(F[q], x, a0); a1 = dot4(F[8 + q], x, a1); a2 = dot4(F[16 + q], x, a2); a3 = dot4(F[24 + q], x, a3);
-                }
-                asm volatile("" ::: "memory");                  // keep the late half late: its registers are not free earlier
-                load_packed<16, 24>(R, blob, rsw, voff);
-                a0 = sum8(a0); a1 = sum8(a1); a2 = sum8(a2); a3 = sum8(a3);
-                if (fpart == 0) {   // tanh(filter) * sigmoid(gate), networks.py:317-319
-                    zbuf[fu] = tanhf(a0 + pb.x) * (1.f / (1.f + expf(-(a1 + pb.y))));
-                    zbuf[fu + 64] = tanhf(a2 + pb.z) * (1.f / (1.f + expf(-(a3 + pb.w))));
-                }
-            }
-            __syncthreads();
-            // next fg weights (next layer, or layer 0 of the next step) stream in during the rs mat-vec
-            const unsigned fgw = p.fg_w + (unsigned)(l + 1 == p.layers ? 0 : l + 1) * fg_stride;
-            load_packed<0, 16>(F, blob, fgw, voff);
-            // ---- residual + skip 1x1 convs (networks.py:322-323)
-            {
-                const float4 *v = reinterpret_cast<const float4 *>(zbuf + rpart * 32);
-                float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const float4 z = v[q];
-                    a0 = dot4(R[q], z, a0); a1 = dot4(R[8 + q], z, a1); a2 = dot4(R[16 + q], z, a2);
-                }
-                asm volatile("" ::: "memory");
-                load_packed<16, 32>(F, blob, fgw, voff);
-                a0 = sum4(a0); a1 = sum4(a1); a2 = sum4(a2);
-                if (rpart == 0) {
-                    const float *b = p.rs_b + l * 384;
-                    const float x = xbuf[rq];
-                    qslot[rq] = x;                       // every reader of x[t-d] is past the barrier above
-                    xbuf[rq] = a0 + b[rq] + x;           // residual = residual_conv(x) + input
-                    skip0 += a1 + b[128 + rq];
-                    skip1 += a2 + b[256 + rq];
-                }
-            }
-            __syncthreads();
-        }
-
-        const int frame = s - (p.field - 1);
-        if (frame < 0) continue;                         // still filling the first receptive field
-        // ---- end convs (networks.py:207-208) on the summed skips
-        if (rpart == 0) { sbuf[rq] = lrelu(skip0); sbuf[128 + rq] = lrelu(skip1); }
-        __syncthreads();
-        {
-            float4 w[8];
-            load_packed<0, 8>(w, blob, p.end1_w, voff);
-            const float4 *v = reinterpret_cast<const float4 *>(sbuf + fpart * 32);
-            float a = 0.f;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) a = dot4(w[q], v[q], a);
-            a = sum8(a);
-            if (fpart == 0) r1[fu] = lrelu(a + p.end1_b[fu]);
-        }
-        __syncthreads();
-        if (tid < p.nout) {
-            float a = p.end2_b[tid];
-            for (int k = 0; k < p.nout; ++k) a = fmaf(p.end2_w[tid * p.nout + k], r1[k], a);
-            r2[tid] = a;
-        }
-        __syncthreads();
-        // ---- Sample_GMM (losses.py:68-112) / L2 passthrough
-        if (tid < p.ndim) {
-            float v;
-            if (p.loss == LSPA2H_LOSS_L2) {
-                v = r2[tid];
-            } else {
-                int idx = 0;
-                if (p.ncenter > 1) {   // softmax -> prob / Exp(1) draw -> argmax  (torch.multinomial, one sample)
-                    float mx = r2[0];
-                    for (int k = 1; k < p.ncenter; ++k) mx = fmaxf(mx, r2[k]);
-                    float den = 0.f;
-                    for (int k = 0; k < p.ncenter; ++k) den += expf(r2[k] - mx);
-                    float best = -1.f;
-                    for (int k = 0; k < p.ncenter; ++k) {
-                        const float val = (expf(r2[k] - mx) / den) / p.expq[(size_t)(frame - p.frame0) * p.ncenter + k];
-                        if (val > best) { best = val; idx = k; }
-                    }
-                }
-                const float mu = r2[p.ncenter + idx * p.ndim + tid];
-                const float sigma = expf(-r2[p.ncenter + p.ncenter * p.ndim + idx * p.ndim + tid]) * p.sigma_scale;
-                const float nz = p.noise ? p.noise[(size_t)(frame - p.frame0) * p.ndim + tid] : 0.f;
-                v = nz * sigma + mu;
-            }
-            p.out[(size_t)(frame - p.frame0) * p.ndim + tid] = v;
-            inb[tid] = v;                                // history_headpose <- cat(history[1:], pred), :186
-        }
-        __syncthreads();
-    }
-    if (p.state_out) {                                   // every step ended on a barrier: the queues and inb are final
-        for (int i = tid; i < qrows * RC; i += NT) p.state_out[i] = queue[i];
-        if (tid < 16) p.state_out[qrows * RC + tid] = inb[tid];
-        if (tid == 0) p.state_out[qrows * RC + 16] = __int_as_float(nsteps);
-    }
-}
-
-// The loop of a2h_stream for steps [s0, s1) of one stream of a2h_stream_multi -- a separate instance: a2h_stream above stays the code it
-// was (sharing one body changed its register allocation).  Steps below field - 1 fill the first receptive field and emit nothing, step
-// field - 1 + f emits frame f into row f - fbase of out (noise / expq likewise); per step the instructions are a2h_stream's.
+// Steps [s0, nsteps) of one stream.  Steps below field - 1 fill the first receptive field and emit nothing, step field - 1 + f emits
+// frame f into row f - fbase of out (noise / expq likewise).
 __device__ __forceinline__ void stream_steps(const StreamParams &p, float *smem, const float *proj, const float *pre, const float *noise,
                                              const float *expq, float *out, const float *state_in, float *state_out, int s0, const int nsteps,
                                              const int fbase)
@@ -452,19 +271,20 @@ __device__ __forceinline__ void stream_steps(const StreamParams &p, float *smem,
     }
 }
 
-// Several streams per launch (lspa2h_generate_resume_multi): workgroup b runs entry b of the table.  A stream's dilation queues fill most of
-// a CU's LDS, so one workgroup per stream is forced; the workgroups share nothing but the weights (read-only) and the status word.
+// Workgroup b runs entry b of the table: several streams per launch for lspa2h_generate_resume_multi, one entry for the whole-clip call
+// (steps 0 .. field - 1 + nframe, no states) and for lspa2h_generate_resume.  A stream's dilation queues fill most of a CU's LDS, so one
+// workgroup per stream is forced; the workgroups share nothing but the weights (read-only) and the status word.
 struct StreamItem {
     const float *proj;                  // this stream's projection ring
     const float *pre, *noise, *expq;
     float *out;
-    const float *state_in;
-    float *state_out;
+    const float *state_in;              // null: start of the clip; else queues [qrows][128], inb [16], step counter (int bits)
+    float *state_out;                   // null, or where the state after the last step goes (same layout)
     int step0, step1;                   // steps [step0, step1) of the stream; out / noise / expq row 0 is the first frame they emit
 };
 struct StreamTable { StreamItem it[LSPA2H_MAX_STREAMS]; };
 
-__global__ __launch_bounds__(NT) void a2h_stream_multi(StreamParams p, StreamTable tb)
+__global__ __launch_bounds__(NT) void a2h_stream(StreamParams p, StreamTable tb)
 {
     extern __shared__ float smem[];
     const StreamItem &it = tb.it[blockIdx.x];
@@ -790,7 +610,7 @@ struct lspa2h_handle {
     float *mws = nullptr;                // the several-streams workspace (lspa2h_bind_workspace_multi)
     int mstreams = 0;
     bool packed = false;
-    bool attr_done = false, mattr_done = false, pipe_attr_done = false, pipe_fits = false, boxes_clean = false;
+    bool attr_done = false, pipe_attr_done = false, pipe_fits = false, boxes_clean = false;
     unsigned epoch = 0;
     int last_rows = 0;
     size_t xbox_bytes() const { return (size_t)(layers + 1) * (size_t)(field - 1 + cfg.max_audio_frames) * RC * 8; }
@@ -808,6 +628,40 @@ struct lspa2h_handle {
 };
 
 static size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
+
+// dynamic LDS of a2h_stream: the step buffers and every layer's dilation queue
+static size_t stream_lds(const lspa2h_handle *h) { return (size_t)(RC * 3 + SC + 2 * MAX_OUT + 16 + (size_t)h->qrows * RC) * sizeof(float); }
+
+// the part of StreamParams that comes from the handle; the per-call tensors, the mailboxes and the status word are the caller's
+static StreamParams stream_params(const lspa2h_handle *h, float sigma_scale, int frame_future)
+{
+    const float *b = h->blob;
+    StreamParams p{};
+    p.start1_w = b + h->o_start1_w; p.start1_b = b + h->o_start1_b;
+    p.blob = b; p.blob_bytes = (unsigned)(h->blob_floats * sizeof(float));
+    p.start2_w = (unsigned)(h->o_start2_w * 4); p.start2_b = b + h->o_start2_b;
+    p.fg_w = (unsigned)(h->o_fg_w * 4); p.rs_w = (unsigned)(h->o_rs_w * 4); p.rs_b = b + h->o_rs_b;
+    p.end1_w = (unsigned)(h->o_end1_w * 4); p.end1_b = b + h->o_end1_b;
+    p.end2_w = b + h->o_end2_w; p.end2_b = b + h->o_end2_b;
+    p.layers = h->layers; p.ndim = h->cfg.ndim; p.ncenter = h->cfg.ncenter; p.nout = h->nout; p.loss = h->cfg.loss;
+    p.field = h->field; p.frame_future = frame_future; p.sigma_scale = sigma_scale; p.ring = h->cfg.max_audio_frames;
+    for (int l = 0; l < h->layers; ++l) { p.dil[l] = h->dil[l]; p.qoff[l] = h->qoff[l]; }
+    return p;
+}
+
+// entries [0, n) of the table, one workgroup each
+static int launch_stream(lspa2h_handle *h, const StreamParams &p, const StreamTable &tb, int n, hipStream_t s)
+{
+    if (!h->attr_done) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&a2h_stream),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return hipfail(e, "hipFuncSetAttribute(a2h_stream)");
+        h->attr_done = true;
+    }
+    hipLaunchKernelGGL(a2h_stream, dim3(n), dim3(NT), stream_lds(h), s, p, tb);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LSPA2H_OK : hipfail(e, "a2h_stream launch");
+}
 
 extern "C" {
 
@@ -844,8 +698,7 @@ int lspa2h_create(const lspa2h_config *cfg, lspa2h_handle **out)
             h->qrows += 1 << i;
             h->field += 1 << i;     // kernel_size 2: additional_scope doubles per layer (networks.py:150-166)
         }
-    const size_t lds = (size_t)(RC * 3 + SC + 2 * MAX_OUT + 16 + (size_t)h->qrows * RC) * sizeof(float);
-    if (lds > 160 * 1024) { delete h; return fail(LSPA2H_ERR_UNSUPPORTED, "dilation queues exceed the 160 KB LDS of one CU"); }
+    if (stream_lds(h) > 160 * 1024) { delete h; return fail(LSPA2H_ERR_UNSUPPORTED, "dilation queues exceed the 160 KB LDS of one CU"); }
 
     const size_t H = cfg->hidden_size, nd = cfg->ndim, no = h->nout;
     h->add("audio_downsample.0.weight", {H, 2 * H});
@@ -1047,6 +900,15 @@ static int launch_gemm(const float *A, const float *W, const float *scale, const
     return e == hipSuccess ? LSPA2H_OK : hipfail(e, "gemm_f32 launch");
 }
 
+// audio_downsample on n rows: Linear(2H->H) + BatchNorm1d(eval) + LeakyReLU(0.2) + Linear(H->H)   (audio2headpose.py:16-21)
+static int downsample(const lspa2h_handle *h, const float *audio_dev, int n, float *hid, float *cond, hipStream_t s)
+{
+    const float *b = h->blob;
+    const int H = h->cfg.hidden_size;
+    if (int rc = launch_gemm(audio_dev, b + h->o_mlp0_w, b + h->o_mlp0_scale, b + h->o_mlp0_shift, hid, n, H, 2 * H, 1, s)) return rc;
+    return launch_gemm(hid, b + h->o_mlp1_w, nullptr, b + h->o_mlp1_b, cond, n, H, H, 0, s);
+}
+
 static int generate_impl(lspa2h_handle *h, const float *audio_dev, int n_audio, const float *pre_dev, const float *noise_dev,
                          const float *expq_dev, float sigma_scale, int frame_future, float *out_dev, int nframe, hipStream_t s,
                          hipEvent_t mid)
@@ -1064,33 +926,20 @@ static int generate_impl(lspa2h_handle *h, const float *audio_dev, int n_audio, 
     float *hid = h->ws, *cond = hid + align64(rows * H), *proj = cond + align64(rows * H);
     const float *b = h->blob;
     int rc;
-    // audio_downsample: Linear(2H->H) + BatchNorm1d(eval) + LeakyReLU(0.2) + Linear(H->H)   (audio2headpose.py:16-21)
-    if ((rc = launch_gemm(audio_dev, b + h->o_mlp0_w, b + h->o_mlp0_scale, b + h->o_mlp0_shift, hid, n_audio, H, 2 * H, 1, s))) return rc;
-    if ((rc = launch_gemm(hid, b + h->o_mlp1_w, nullptr, b + h->o_mlp1_b, cond, n_audio, H, H, 0, s))) return rc;
+    if ((rc = downsample(h, audio_dev, n_audio, hid, cond, s))) return rc;
     // every layer's cond_filter_conv / cond_gate_conv on every frame (networks.py:310-311)
     if ((rc = launch_gemm(cond, b + h->o_proj_w, nullptr, b + h->o_proj_b, proj, n_audio, L * 256, H, 0, s))) return rc;
     if (mid) (void)hipEventRecord(mid, s);
     h->last_rows = n_audio;
 
-    StreamParams p{};
-    p.start1_w = b + h->o_start1_w; p.start1_b = b + h->o_start1_b;
-    p.blob = b; p.blob_bytes = (unsigned)(h->blob_floats * sizeof(float));
-    p.start2_w = (unsigned)(h->o_start2_w * 4); p.start2_b = b + h->o_start2_b;
-    p.fg_w = (unsigned)(h->o_fg_w * 4); p.rs_w = (unsigned)(h->o_rs_w * 4); p.rs_b = b + h->o_rs_b;
-    p.end1_w = (unsigned)(h->o_end1_w * 4); p.end1_b = b + h->o_end1_b;
-    p.end2_w = b + h->o_end2_w; p.end2_b = b + h->o_end2_b;
-    p.proj = proj; p.pre = pre_dev; p.noise = noise_dev; p.expq = expq_dev; p.out = out_dev;
-    p.layers = L; p.ndim = h->cfg.ndim; p.ncenter = h->cfg.ncenter; p.nout = h->nout; p.loss = h->cfg.loss;
-    p.field = h->field; p.nframe = nframe; p.frame_future = frame_future; p.sigma_scale = sigma_scale;
-    p.frame0 = 0; p.ring = (int)rows; p.state_in = nullptr; p.state_out = nullptr;
-    for (int l = 0; l < L; ++l) { p.dil[l] = h->dil[l]; p.qoff[l] = h->qoff[l]; }
-    const bool single = (h->cfg.flags & LSPA2H_FLAG_SINGLE_WORKGROUP) != 0;
+    StreamParams p = stream_params(h, sigma_scale, frame_future);
+    p.proj = proj; p.pre = pre_dev; p.noise = noise_dev; p.expq = expq_dev; p.out = out_dev; p.nframe = nframe;
     char *tail = reinterpret_cast<char *>(proj + align64(rows * (size_t)L * 256));
     p.xbox = reinterpret_cast<unsigned long long *>(tail);
     p.sbox = reinterpret_cast<unsigned long long *>(tail + h->xbox_bytes());
     p.status = reinterpret_cast<unsigned *>(tail + h->xbox_bytes() + h->sbox_bytes());
     if (hipMemsetAsync(p.status, 0, 64, s) != hipSuccess) return fail(LSPA2H_ERR_HIP, "hipMemsetAsync(status)");
-    if (!single) {
+    if (!(h->cfg.flags & LSPA2H_FLAG_SINGLE_WORKGROUP)) {
         // mailbox tags: the call counter, so slots of earlier calls never match; whatever the buffer held when it
         // was bound is cleared once
         if (!h->boxes_clean) {
@@ -1114,25 +963,19 @@ static int generate_impl(lspa2h_handle *h, const float *audio_dev, int n_audio, 
             h->pipe_fits = ok;
             h->pipe_attr_done = true;
         }
-        if (!h->pipe_fits) goto single_workgroup;            // a device too small for the pipeline: the one-workgroup kernel needs no co-residency
-        // Blocks are dealt round-robin over the 8 XCDs (observed, not contractual): using every 8th block puts the
-        // whole chain behind one L2.  Measured 45.4 vs 51.0 us per frame; results do not depend on it.
-        p.stride = (h->cfg.flags & LSPA2H_FLAG_CONSECUTIVE_BLOCKS) ? 1 : 8;     // (the flag: tools only)
-        hipLaunchKernelGGL(a2h_pipe, dim3((L + 1) * p.stride), dim3(NT), lds_pipe, s, p);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? LSPA2H_OK : hipfail(e, "a2h_pipe launch");
+        if (h->pipe_fits) {
+            // Blocks are dealt round-robin over the 8 XCDs (observed, not contractual): using every 8th block puts the
+            // whole chain behind one L2.  Measured 45.4 vs 51.0 us per frame; results do not depend on it.
+            p.stride = (h->cfg.flags & LSPA2H_FLAG_CONSECUTIVE_BLOCKS) ? 1 : 8;     // (the flag: tools only)
+            hipLaunchKernelGGL(a2h_pipe, dim3((L + 1) * p.stride), dim3(NT), lds_pipe, s, p);
+            const hipError_t e = hipGetLastError();
+            return e == hipSuccess ? LSPA2H_OK : hipfail(e, "a2h_pipe launch");
+        }
+        // a device too small for the pipeline: the one-workgroup kernel needs no co-residency
     }
-single_workgroup:
-    const size_t lds = (size_t)(RC * 3 + SC + 2 * MAX_OUT + 16 + (size_t)h->qrows * RC) * sizeof(float);
-    if (!h->attr_done) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&a2h_stream),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return hipfail(e, "hipFuncSetAttribute(a2h_stream)");
-        h->attr_done = true;
-    }
-    hipLaunchKernelGGL(a2h_stream, dim3(1), dim3(NT), lds, s, p);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LSPA2H_OK : hipfail(e, "a2h_stream launch");
+    StreamTable tb{};   // the whole clip as one entry: every step from the start, no states
+    tb.it[0] = StreamItem{proj, pre_dev, noise_dev, expq_dev, out_dev, nullptr, nullptr, 0, h->field - 1 + nframe};
+    return launch_stream(h, p, tb, 1, s);
 }
 
 size_t lspa2h_state_bytes(const lspa2h_handle *h) { return h ? ((size_t)h->qrows * RC + 16 + 4) * sizeof(float) : 0; }
@@ -1163,39 +1006,22 @@ int lspa2h_generate_resume(lspa2h_handle *h, const float *audio_dev, int row0, i
     const float *b = h->blob;
     int rc;
     if (n_new > 0) {   // the new rows only: downsample MLP, then the cond projections into ring rows row % R (split at the wrap)
-        if ((rc = launch_gemm(audio_dev, b + h->o_mlp0_w, b + h->o_mlp0_scale, b + h->o_mlp0_shift, hid, n_new, H, 2 * H, 1, s))) return rc;
-        if ((rc = launch_gemm(hid, b + h->o_mlp1_w, nullptr, b + h->o_mlp1_b, cond, n_new, H, H, 0, s))) return rc;
+        if ((rc = downsample(h, audio_dev, n_new, hid, cond, s))) return rc;
         const int slot = row0 % R, first = n_new < R - slot ? n_new : R - slot;
         if ((rc = launch_gemm(cond, b + h->o_proj_w, nullptr, b + h->o_proj_b, proj + (size_t)slot * L * 256, first, L * 256, H, 0, s))) return rc;
         if (first < n_new &&
             (rc = launch_gemm(cond + (size_t)first * H, b + h->o_proj_w, nullptr, b + h->o_proj_b, proj, n_new - first, L * 256, H, 0, s))) return rc;
     }
-    StreamParams p{};
-    p.start1_w = b + h->o_start1_w; p.start1_b = b + h->o_start1_b;
-    p.blob = b; p.blob_bytes = (unsigned)(h->blob_floats * sizeof(float));
-    p.start2_w = (unsigned)(h->o_start2_w * 4); p.start2_b = b + h->o_start2_b;
-    p.fg_w = (unsigned)(h->o_fg_w * 4); p.rs_w = (unsigned)(h->o_rs_w * 4); p.rs_b = b + h->o_rs_b;
-    p.end1_w = (unsigned)(h->o_end1_w * 4); p.end1_b = b + h->o_end1_b;
-    p.end2_w = b + h->o_end2_w; p.end2_b = b + h->o_end2_b;
-    p.proj = proj; p.pre = pre_dev; p.noise = noise_dev; p.expq = expq_dev; p.out = out_dev;
-    p.layers = L; p.ndim = h->cfg.ndim; p.ncenter = h->cfg.ncenter; p.nout = h->nout; p.loss = h->cfg.loss;
-    p.field = h->field; p.nframe = nframe; p.frame_future = frame_future; p.sigma_scale = sigma_scale;
-    p.frame0 = frame0; p.ring = R;
-    p.state_in = static_cast<const float *>(state_in); p.state_out = static_cast<float *>(state_out);
-    for (int l = 0; l < L; ++l) { p.dil[l] = h->dil[l]; p.qoff[l] = h->qoff[l]; }
+    StreamParams p = stream_params(h, sigma_scale, frame_future);
     char *tail = reinterpret_cast<char *>(proj + align64(rows * (size_t)L * 256));
     p.status = reinterpret_cast<unsigned *>(tail + h->xbox_bytes() + h->sbox_bytes());
     if (hipMemsetAsync(p.status, 0, 64, s) != hipSuccess) return fail(LSPA2H_ERR_HIP, "hipMemsetAsync(status)");
-    const size_t lds = (size_t)(RC * 3 + SC + 2 * MAX_OUT + 16 + (size_t)h->qrows * RC) * sizeof(float);
-    if (!h->attr_done) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&a2h_stream),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return hipfail(e, "hipFuncSetAttribute(a2h_stream)");
-        h->attr_done = true;
-    }
-    hipLaunchKernelGGL(a2h_stream, dim3(1), dim3(NT), lds, s, p);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LSPA2H_OK : hipfail(e, "a2h_stream launch");
+    // frames [frame0, frame0 + nframe) as steps: a resumed call continues at step field - 1 + frame0, the start of a clip (frame0 == 0) also
+    // runs the field - 1 steps that fill the first receptive field
+    StreamTable tb{};
+    tb.it[0] = StreamItem{proj, pre_dev, noise_dev, expq_dev, out_dev, static_cast<const float *>(state_in), static_cast<float *>(state_out),
+                          state_in ? h->field - 1 + frame0 : 0, h->field - 1 + frame0 + nframe};
+    return launch_stream(h, p, tb, 1, s);
 }
 
 // several-streams workspace: hid / cond / projection staging for max_streams * max_audio_frames new rows, one ring per stream, the status word
@@ -1292,35 +1118,16 @@ int lspa2h_generate_resume_multi(lspa2h_handle *h, int nstreams, const lspa2h_st
     int rc;
     if (hipMemsetAsync(status, 0, 64, s) != hipSuccess) return fail(LSPA2H_ERR_HIP, "hipMemsetAsync(status)");
     if (n_new > 0) {   // the new rows of every stream: one launch per GEMM, then one copy launch into the rings
-        if ((rc = launch_gemm(audio_dev, b + h->o_mlp0_w, b + h->o_mlp0_scale, b + h->o_mlp0_shift, hid, n_new, H, 2 * H, 1, s))) return rc;
-        if ((rc = launch_gemm(hid, b + h->o_mlp1_w, nullptr, b + h->o_mlp1_b, cond, n_new, H, H, 0, s))) return rc;
+        if ((rc = downsample(h, audio_dev, n_new, hid, cond, s))) return rc;
         if ((rc = launch_gemm(cond, b + h->o_proj_w, nullptr, b + h->o_proj_b, stage, n_new, L * 256, H, 0, s))) return rc;
         hipLaunchKernelGGL(proj_scatter, dim3(n_new), dim3(256), 0, s, sp);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return hipfail(e, "proj_scatter launch");
     }
     if (!steps) return LSPA2H_OK;
-    StreamParams p{};
-    p.start1_w = b + h->o_start1_w; p.start1_b = b + h->o_start1_b;
-    p.blob = b; p.blob_bytes = (unsigned)(h->blob_floats * sizeof(float));
-    p.start2_w = (unsigned)(h->o_start2_w * 4); p.start2_b = b + h->o_start2_b;
-    p.fg_w = (unsigned)(h->o_fg_w * 4); p.rs_w = (unsigned)(h->o_rs_w * 4); p.rs_b = b + h->o_rs_b;
-    p.end1_w = (unsigned)(h->o_end1_w * 4); p.end1_b = b + h->o_end1_b;
-    p.end2_w = b + h->o_end2_w; p.end2_b = b + h->o_end2_b;
-    p.layers = L; p.ndim = h->cfg.ndim; p.ncenter = h->cfg.ncenter; p.nout = h->nout; p.loss = h->cfg.loss;
-    p.field = h->field; p.frame_future = frame_future; p.sigma_scale = sigma_scale; p.ring = R;
-    for (int l = 0; l < L; ++l) { p.dil[l] = h->dil[l]; p.qoff[l] = h->qoff[l]; }
+    StreamParams p = stream_params(h, sigma_scale, frame_future);
     p.status = status;
-    const size_t lds = (size_t)(RC * 3 + SC + 2 * MAX_OUT + 16 + (size_t)h->qrows * RC) * sizeof(float);
-    if (!h->mattr_done) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&a2h_stream_multi),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return hipfail(e, "hipFuncSetAttribute(a2h_stream_multi)");
-        h->mattr_done = true;
-    }
-    hipLaunchKernelGGL(a2h_stream_multi, dim3(nstreams), dim3(NT), lds, s, p, tb);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LSPA2H_OK : hipfail(e, "a2h_stream_multi launch");
+    return launch_stream(h, p, tb, nstreams, s);
 }
 
 int lspa2h_status_multi(lspa2h_handle *h, void *stream, uint32_t *code)

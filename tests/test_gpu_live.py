@@ -123,7 +123,7 @@ def _resume_chain(e, cfg, audio, pre, noise, expq, sigma, ff, cuts):
     return np.concatenate(outs)
 
 
-@pytest.mark.parametrize("name", ["default_n300", "nc2_l4b1"])
+@pytest.mark.parametrize("name", ["default_n300", "nc2_l4b1", "l2_l5b2"])
 def test_a2h_resume_split_equals_one_call(name):
     from test_gpu_a2h import make_engine, run
     meta, cfg, sd, audio, pre, ref, noise, expq = load_case(name)
@@ -160,9 +160,37 @@ def test_a2h_resume_refusals():
         e.generate_resume(d(audio[ff + 1:ff + 2]), ff + 1, None, nz, eq, 0.3, ff, 1, 1, s0, s0)
     with pytest.raises(N.Lspa2hError, match="left the projection ring"):   # frame 1 reads row ff + 1: overwritten by rows ff+5 ..
         e.generate_resume(d(audio[ff + 5:2 * ff + 9]), ff + 5, None, d(noise[1:2]), d(expq[1:2]), 0.3, ff, 1, 1, s0, s1)
-    # a state that belongs to another frame is refused on the device, through the status word
-    e.generate_resume(d(audio[ff + 1:ff + 3]), ff + 1, None, d(noise[:1]), d(expq[:1]), 0.3, ff, 2, 1, s0, s1)
+    # a state that belongs to another frame is refused on the device, through the status word; the refused call writes nothing
+    out = torch.full((1, cfg["ndim"]), -7777.25, device=DEV)
+    s1.fill_(0xA5)
+    e.generate_resume(d(audio[ff + 1:ff + 3]), ff + 1, None, d(noise[:1]), d(expq[:1]), 0.3, ff, 2, 1, s0, s1, out=out)
     assert e.status() == 0x5000000
+    assert torch.equal(out.cpu(), torch.full((1, cfg["ndim"]), -7777.25)), "a refused call wrote its output"
+    assert bool((s1 == 0xA5).all()), "a refused call wrote state_out"
+
+
+def test_a2h_short_field_no_future_frames():
+    """frame_future 0 with a receptive field of 8 and a ring of 3 rows: audio-row clamping (rows below 0 read row 0), the first frame of a
+    call and the ring wrap all act within the first few steps.  One call (both kernels) == one frame per call, bit for bit."""
+    from livespeechportraits_amd import synth
+    from oracle import a2h_oracle
+    from test_gpu_a2h import make_engine, run
+    dev = torch.device(DEV)
+    cfg = dict(synth.A2H_DEFAULTS, residual_layers=3, residual_blocks=1)
+    sd = synth.make_a2h_state_dict(cfg, seed=11)
+    n, ff, sigma = 12, 0, 0.4
+    audio, pre = synth.make_a2h_inputs(n, cfg, seed=12)
+    noise = torch.randn(n, cfg["ndim"], generator=torch.Generator().manual_seed(12)).numpy()
+    expq = np.ones((n, 1), np.float32)
+    want = a2h_oracle.stream(sd, cfg, audio, pre, noise, expq, sigma, ff)
+    single = make_engine(cfg, sd, dev, max_audio_frames=n, single_workgroup=True)
+    assert single.receptive_field == 8
+    whole = run(single, cfg, audio, pre, noise, expq, sigma, ff, dev)
+    piped = run(make_engine(cfg, sd, dev, max_audio_frames=n), cfg, audio, pre, noise, expq, sigma, ff, dev)
+    chain = _resume_chain(_a2h_engine(cfg, sd, 3), cfg, audio, pre, noise, expq, sigma, ff, list(range(1, n)))
+    print("\n[a2h field 8, frame_future 0] max-abs vs streaming oracle %.3e" % np.abs(whole - want).max())
+    assert np.array_equal(piped, whole) and np.array_equal(chain, whole)
+    assert whole.shape == want.shape and np.abs(whole - want).max() <= A2H_TOL
 
 
 # ---- mel over a window range ------------------------------------------------------------------------------
