@@ -1,4 +1,4 @@
-"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h, include/lspjpegdec.h, include/lsplmk.h, include/lspavi.h, include/lsprs.h).
+"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h, include/lspjpegdec.h, include/lsplmk.h, include/lspavi.h, include/lsprs.h, include/lspresize.h).
 
 There is deliberately no fallback: if the shared library is missing or does not
 load, importing the hot path raises -- a GPU box must never silently run
@@ -452,6 +452,33 @@ RS_SIGNATURES = {
     "lsprs_launch_count": (c_int64, [c_void_p]),
 }
 
+
+
+class RszInfo(Structure):
+    """lsprsz_info (include/lspresize.h)"""
+    _fields_ = [(n, c_int32) for n in ("in_w", "in_h", "out_w", "out_h", "filter", "need_h", "need_v", "ksize_h", "ksize_v", "row0", "rows", "path_h",
+                                       "path_v", "launches")] + [("lds_h", c_uint32), ("lds_v", c_uint32), ("bytes", ctypes.c_uint64)]
+
+
+class RszOutput(Structure):
+    """lsprsz_output (include/lspresize.h)"""
+    _fields_ = [("ptr", c_void_p), ("table", c_void_p), ("image_stride", c_int64), ("plane_stride", c_int64), ("form", c_int32), ("reserved", c_int32)]
+
+
+RSZ_MAX_SIDE = 8192
+RSZ_FILTERS = {"box": 0, "bilinear": 1, "hamming": 2, "bicubic": 3, "lanczos": 4}
+RSZ_PATHS = {0: None, 1: "tile", 2: "general"}
+RSZ_FORM_U8, RSZ_FORM_PLANAR_F32 = 0, 1
+# every symbol include/lspresize.h declares
+RSZ_SIGNATURES = {
+    "lsprsz_last_error": (c_char_p, []),
+    "lsprsz_plan": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
+    "lsprsz_plan_info": (c_int, [c_void_p, POINTER(RszInfo)]),
+    "lsprsz_plan_axis": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t]),
+    "lsprsz_workspace_bytes": (c_int64, [c_void_p, c_int, c_int]),
+    "lsprsz_resize": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, POINTER(RszOutput), c_void_p, c_size_t, c_void_p]),
+}
+
 _lib = None
 
 
@@ -469,7 +496,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise NativeLibraryError("failed to load %s: %s" % (LIB_PATH, e)) from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JPEGDEC_SIGNATURES.items()) + list(LMK_SIGNATURES.items()) + list(AVI_SIGNATURES.items()) + list(RS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JPEGDEC_SIGNATURES.items()) + list(LMK_SIGNATURES.items()) + list(AVI_SIGNATURES.items()) + list(RS_SIGNATURES.items()) + list(RSZ_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -624,3 +651,17 @@ def check_rs(rc: int) -> None:
     if rc != OK:
         msg = load().lsprs_last_error()
         raise LsprsError(rc, msg.decode() if msg else "")
+
+
+class LsprszError(RuntimeError):
+    def __init__(self, code: int, msg: str):
+        super().__init__("lsprsz error %d: %s" % (code, msg))
+        self.code = code
+
+
+def check_rsz(rc: int) -> int:
+    """negative codes of include/lspresize.h raise; anything else (0, a size, a count) is handed back"""
+    if rc < 0:
+        msg = load().lsprsz_last_error()
+        raise LsprszError(rc, msg.decode() if msg else "")
+    return rc

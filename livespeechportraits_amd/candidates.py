@@ -9,7 +9,9 @@
 ``load_candidates`` decodes the four files with jpeg.JpegDecoder (the pixels Pillow returns, bit for bit) straight into channels
 3j .. 3j + 2 of the float tensor, through a 256-entry table that holds the normalisation: no uint8 image and no host tensor in
 between.  The table is ``float32(float64(v) / 255.0)``, then ``(t - 0.5f) / 0.5f`` in float32 -- what ToTensor(normalize=...)
-computes (``img / 255.0`` then ``F.normalize``).  albumentations is not installed where this is built, so the table is
+computes (``img / 255.0`` then ``F.normalize``).  With ``resize=`` a photograph of any size the decoder takes is decoded at its own size
+and resampled on the device to ``size`` x ``size`` (resize.Resizer: ``Image.open(f).resize((size, size), filter)``, bit for bit), its pixels
+going through the same table into the same channels.  albumentations is not installed where this is built, so the table is
 *parity-unpinned against albumentations*: it is pinned on that formula (tests/test_jpeg_decode_cpu.py).
 """
 from __future__ import annotations
@@ -33,11 +35,18 @@ def candidate_paths(data_root: str) -> list:
     return [os.path.join(data_root, "candidates", "normalized_full_%d.jpg" % j) for j in range(CANDIDATES)]
 
 
-def load_candidates(paths_or_data_root: Union[str, Sequence], device="cuda:0", size: int = 512, decoder=None) -> torch.Tensor:
+def load_candidates(paths_or_data_root: Union[str, Sequence], device="cuda:0", size: int = 512, decoder=None, resize=None, resizer=None) -> torch.Tensor:
     """float32 ``[1, 12, size, size]`` on ``device`` from four JPEG files: a data root (``<root>/candidates/normalized_full_{0..3}.jpg``), four
     paths, or four ``bytes`` objects.  Files that are not 3-component ``size`` x ``size`` are refused (ValueError); files the decoder
-    cannot take raise jpeg.JpegError."""
+    cannot take raise jpeg.JpegError.
+
+    ``resize`` ("box", "bilinear", "hamming", "bicubic" or "lanczos"; None: off): the files may have any geometry the decoder takes, each its
+    own; a file that is not ``size`` x ``size`` is resampled to it as ``Image.resize((size, size), filter)`` does, one that is takes the path
+    above.  ``resizer``: a resize.Resizer to reuse."""
     from .jpeg import JpegDecoder, probe
+    if resize is not None:
+        from .resize import Resizer, check_filter
+        resize = check_filter(resize)
     src = candidate_paths(paths_or_data_root) if isinstance(paths_or_data_root, (str, os.PathLike)) else list(paths_or_data_root)
     if len(src) != CANDIDATES:
         raise ValueError("%d candidate images, demo.py reads %d" % (len(src), CANDIDATES))
@@ -48,13 +57,24 @@ def load_candidates(paths_or_data_root: Union[str, Sequence], device="cuda:0", s
         else:
             with open(s, "rb") as f:
                 files.append(f.read())
+    other = []                                                  # the files to resample
     for j, data in enumerate(files):
         i = probe(data)
         if i.status == 0 and (i.width, i.height, i.components) != (size, size, 3):
-            raise ValueError("candidate %d is %dx%d with %d components, the generator takes %dx%d RGB" % (j, i.width, i.height, i.components, size, size))
+            if resize is None or i.components != 3:
+                raise ValueError("candidate %d is %dx%d with %d components, the generator takes %dx%d RGB" % (j, i.width, i.height, i.components, size, size))
+            other.append((j, max(i.width, i.height)))
     device = torch.device(device)
-    decoder = decoder or JpegDecoder(device, max_side=size, max_batch=CANDIDATES)
+    decoder = decoder or JpegDecoder(device, max_side=max([size] + [side for _, side in other]), max_batch=CANDIDATES)
     out = torch.empty((3 * CANDIDATES, size, size), dtype=torch.float32, device=device)
     table = torch.from_numpy(normalisation_table()).to(device)
-    decoder.decode_into(files, out, 0, table)
+    if not other:
+        decoder.decode_into(files, out, 0, table)
+        return out.unsqueeze(0)
+    resizer = resizer or Resizer(device, max_batch=1)
+    for j in range(CANDIDATES):
+        if j not in [k for k, _ in other]:
+            decoder.decode_into([files[j]], out, 3 * j, table)
+    for (j, _), pixels in zip(other, decoder.decode([files[j] for j, _ in other])):
+        resizer.resize_planes(pixels, size, table, out[3 * j:3 * j + 3], resize)
     return out.unsqueeze(0)

@@ -10,6 +10,9 @@ layers is cached by the engine as in the render loop.  Inside a tick:
 4. the generator with fused ``tensor2im`` in groups of at most ``max_batch`` frames (``last_groups`` records them);
 5. JPEG when asked for.
 
+4b. with ``out_size``: every generator group is resampled once (resize.Resizer: ``Image.resize``, bit for bit) right behind its forward;
+   the frames handed out, the JPEG files and the ``video`` recordings are then ``out_size``.  The edge-map recordings stay ``load_size``.
+
 6. recording, for the sessions that have a writer: the frames of a tick are encoded and muxed in groups of at most ``max_batch``, one
    fragment per file out of one ``lspavi_pack_multi`` call, the audio from per-session rings on the device.
 
@@ -35,13 +38,18 @@ class LivePortraitPool:
     "device" (one lspavi_pack_multi per group of frames) or "host" (JpegEncoder + append_jpegs per session); both write the same files.
 
     ``audio_input``: an AudioInputStage on the same device with at least as many sessions; sessions may then be opened at one of its rates
-    and pushed raw capture audio.  The stage's lookahead (R input samples, at most 8 ms) adds at most one frame to ``delay``."""
+    and pushed raw capture audio.  The stage's lookahead (R input samples, at most 8 ms) adds at most one frame to ``delay``.
+
+    ``out_size`` (an int or ``(width, height)``; None: off) with ``resample`` ("box", "bilinear", "hamming", "bicubic", "lanczos"): the colour
+    frames leave the pool at that size -- one resize call per generator group, nothing else added to a tick.  ``video`` writers must then be
+    of ``out_size``; ``video_input`` (the edge maps, the generator's input) stays ``load_size``."""
 
     fps = 60                                                                       # live.py: a clip of N samples has int(N / 16000 * 60) frames
     rate = 16000
 
     def __init__(self, audio, stage, model, cand_image, load_size: int = 512, max_batch: int = 8, raster_chunk: int = 64,
-                 record_quality: Optional[int] = None, record_route: Optional[str] = None, audio_input=None):
+                 record_quality: Optional[int] = None, record_route: Optional[str] = None, audio_input=None, out_size=None,
+                 resample: str = "bicubic"):
         import torch
         from .feature_map import FeatureMapRasteriser
         self.torch = torch
@@ -65,6 +73,13 @@ class LivePortraitPool:
         self.last_heard: Dict[int, tuple] = {}                                     # the input stage's output of the last tick, per session
         self.load_size, self.max_batch, self.raster_chunk = int(load_size), int(max_batch), int(raster_chunk)
         self.raster = FeatureMapRasteriser(self.load_size, 18, self.device)
+        self.out_size, self.resample, self._resizer, self._full = None, resample, None, None
+        if out_size is not None:
+            from .resize import Resizer, check_filter, check_size
+            self.out_size, self.resample = check_size(out_size), check_filter(resample)
+            self._resizer = Resizer(self.device, max_batch=self.max_batch)
+            self._full = torch.empty((self.max_batch, self.load_size, self.load_size, 3), dtype=torch.uint8, device=self.device)     # a group at the generator's size
+        self.frame_width, self.frame_height = self.out_size or (self.load_size, self.load_size)                                          # of the colour frames that leave
         rows = stage.max_push - audio.ff_mouth - 2                                # a push's frames, + the mouth tail at finish, + rounding
         if rows < 1:
             raise ValueError("the landmark stage's max_push (%d) must exceed the mouth lookahead + 2 (%d)" % (stage.max_push, audio.ff_mouth + 2))
@@ -152,9 +167,10 @@ class LivePortraitPool:
         channels = 3 if which == "video" else 1
         if not isinstance(writer, AviWriter) or writer._f is None:
             raise ValueError("%s must be an open AviWriter" % which)
-        if (writer.width, writer.height, writer.channels, writer.fps) != (self.load_size, self.load_size, channels, self.fps):
+        width, height = (self.frame_width, self.frame_height) if which == "video" else (self.load_size, self.load_size)
+        if (writer.width, writer.height, writer.channels, writer.fps) != (width, height, channels, self.fps):
             raise ValueError("%s must be an AviWriter of %dx%d with %d channel(s) at %d fps (got %dx%d, %d, %d fps)" % (
-                which, self.load_size, self.load_size, channels, self.fps, writer.width, writer.height, writer.channels, writer.fps))
+                which, width, height, channels, self.fps, writer.width, writer.height, writer.channels, writer.fps))
         if writer.audio_rate not in (None, self.rate):
             raise ValueError("%s: the audio stream of a live recording is %d Hz (or audio_rate=None), not %d" % (which, self.rate, writer.audio_rate))
         if writer.nframes or writer.nsamples:
@@ -168,7 +184,7 @@ class LivePortraitPool:
             self._check_writer(video_input, "video_input")
 
     def record(self, sid: int, video, video_input=None, on_full=None) -> None:
-        """Record session ``sid`` from its next emitted frame: ``video`` an AviWriter of load_size x load_size x 3 at the pool's fps,
+        """Record session ``sid`` from its next emitted frame: ``video`` an AviWriter of load_size x load_size x 3 (``out_size`` x 3 with ``out_size``) at the pool's fps,
         with a 16 kHz audio stream or none; ``video_input`` a grayscale one for the rasterised edge maps.  ``on_full(sid, which)`` (which:
         "video" / "video_input") hands out the next writer when a file is full; without it the recording stops there
         (``recording_stopped``).  The writers stay the caller's: ``tick`` appends to them, the caller closes them."""
@@ -264,7 +280,7 @@ class LivePortraitPool:
         self.last_groups = []
         recorded = [sid for sid in named if sid in self._rec and spans[sid][2]]
         with torch.cuda.device(self.device):
-            frames = torch.empty((total, H, H, 3), dtype=torch.uint8, device=self.device)
+            frames = torch.empty((total, self.frame_height, self.frame_width, 3), dtype=torch.uint8, device=self.device)
             edges = None
             if any("video_input" in self._rec[sid] for sid in recorded):          # the {0, 255} maps of the same launch, for the gray files
                 edges = torch.empty((total, H, H), dtype=torch.uint8, device=self.device)
@@ -274,7 +290,11 @@ class LivePortraitPool:
                                                     out_u8=None if edges is None else edges[c0:c1])
                 for g0 in range(c0, c1, self.max_batch):                                            # 4. the generator, uint8 HWC out of its last kernel
                     g1 = min(c1, g0 + self.max_batch)
-                    self.model.inference_image(maps[g0 - c0:g1 - c0], self.cand, out=frames[g0:g1])
+                    if self._resizer is None:
+                        self.model.inference_image(maps[g0 - c0:g1 - c0], self.cand, out=frames[g0:g1])
+                    else:                                                                           # 4b. the group once, at out_size, into its rows
+                        self.model.inference_image(maps[g0 - c0:g1 - c0], self.cand, out=self._full[:g1 - g0])
+                        self._resizer.resize(self._full[:g1 - g0], self.out_size, self.resample, out=frames[g0:g1])
                     self.last_groups.append(owner[g0:g1])
             result = {}
             if jpeg_quality is not None:                                           # 5. complete files; only the compressed bytes cross PCIe
@@ -335,7 +355,8 @@ class LivePortraitPool:
         if pair is None:
             from .jpeg import JpegEncoder
             from .video import DeviceMultiMuxer
-            enc = JpegEncoder(self.load_size, 3 if which == "video" else 1, self.record_quality, self.device, max_batch=self.max_batch)
+            size = (self.frame_height, self.frame_width) if which == "video" else self.load_size
+            enc = JpegEncoder(size, 3 if which == "video" else 1, self.record_quality, self.device, max_batch=self.max_batch)
             pair = self._mux[which] = (enc, DeviceMultiMuxer(enc, self.rate, self.fps) if self.record_route == "device" else None)
         return pair
 
@@ -412,5 +433,5 @@ class LivePortraitPool:
         enc = self._jpeg.get(quality)
         if enc is None:
             from .jpeg import JpegEncoder
-            enc = self._jpeg[quality] = JpegEncoder(self.load_size, 3, quality, self.device, max_batch=self.max_batch)
+            enc = self._jpeg[quality] = JpegEncoder((self.frame_height, self.frame_width), 3, quality, self.device, max_batch=self.max_batch)
         return enc

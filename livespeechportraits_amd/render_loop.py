@@ -28,7 +28,8 @@ def batched(it: Iterable, n: int) -> Iterator[List]:
 def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch.Tensor, batch: int = 8,
                   device: Optional[torch.device] = None,
                   on_frame: Optional[Callable[[int, np.ndarray], None]] = None, streams: int = 2,
-                  jpeg_quality=None, video=None, audio=None, video_route: Optional[str] = None) -> List[np.ndarray]:
+                  jpeg_quality=None, video=None, audio=None, video_route: Optional[str] = None,
+                  out_size=None, resample: str = "bicubic") -> List[np.ndarray]:
     """``feature_maps`` yields [1,H,W] (or [C,H,W]) CPU/GPU tensors as
     ``facedataset.dataset.get_data_test_mode`` does (demo.py:262); ``cand_image`` is demo.py's
     ``img_candidates`` ([1,12,H,W], already on the device).  Returns (or streams to ``on_frame``) uint8 HWC
@@ -52,11 +53,17 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
     on the device behind the encoder (video.DeviceMuxer, include/lspavi.h) and the fragments are appended in frame order; ``jpeg_quality`` defaults to 75,
     the function returns [] (``on_frame(i, None)`` is still called per frame).  ``audio``: the CLIP's float32 waveform at the writer's rate (tensor or
     array), required exactly when the writer has an audio stream; frame k of the file carries its samples [k * rate // fps, (k + 1) * rate // fps).
-    ``video_route`` "device" / "host" (JpegEncoder.collect + AviWriter.append_jpegs) overrides video.DEFAULT_VIDEO_ROUTE; both write the same file."""
+    ``video_route`` "device" / "host" (JpegEncoder.collect + AviWriter.append_jpegs) overrides video.DEFAULT_VIDEO_ROUTE; both write the same file.
+
+    ``out_size`` (an int or ``(width, height)``, as Pillow's ``size``; None: off) with ``resample`` ("box", "bilinear", "hamming", "bicubic", "lanczos"): every lane
+    resamples its batch on its own stream right behind the generator (resize.Resizer, include/lspresize.h: ``Image.resize``, bit for bit) into a buffer it owns; the host
+    copy, the JPEG encoder and the video sink then see ``out_size`` frames, and ``video`` must be a writer of that geometry."""
     device = device or cand_image.device
     frames: List[np.ndarray] = []
     idx = 0
     on_gpu = device.type == "cuda"
+    if out_size is not None:
+        out_size = _check_out_size(out_size, resample, on_gpu, video)
     if video is not None and jpeg_quality is None:
         jpeg_quality = 75
     if jpeg_quality is not None and not on_gpu:
@@ -110,7 +117,7 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
                 st = torch.cuda.Stream(device) if nlane > 1 else None
                 if st is not None:
                     st.wait_stream(cur)                          # cand_image was produced there
-                lanes.append({"stream": st, "busy": None, "host": None, "u8": None, "jpeg": None, "sink": None,
+                lanes.append({"stream": st, "busy": None, "host": None, "u8": None, "jpeg": None, "sink": None, "resizer": None, "small": None,
                               "stage": torch.empty(shape, dtype=torch.float32, pin_memory=True), "dev": torch.empty(shape, dtype=torch.float32, device=device)})
                 lanes[-1]["stage_np"] = lanes[-1]["stage"].numpy()
         lane = lanes[n % nlane]
@@ -142,6 +149,10 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
                     lane["u8"] = torch.empty((batch, H, H, 3), dtype=torch.uint8, device=device)
                 kw["out"] = lane["u8"][:b]
             u8 = model.inference_image(lane["dev"][:b], cand_image, **kw)
+            if out_size is not None:
+                if lane["resizer"] is None:
+                    lane["resizer"], lane["small"] = _lane_resizer(device, batch, out_size)
+                u8 = lane["resizer"].resize(u8, out_size, resample, out=lane["small"][:b])       # on the lane's stream, behind the generator
             if video is not None:
                 if lane["sink"] is None:
                     lane["sink"] = VideoSink(video, tuple(u8.shape[1:3]), jpeg_quality, device, batch, audio_dev, audio_host, video_route)
@@ -165,6 +176,24 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
     return frames
 
 
+def _check_out_size(out_size, resample, on_gpu, video):
+    """(width, height) of ``out_size``; everything the resampler or the writer would refuse is refused here, before anything runs"""
+    from .resize import check_filter, check_size
+    check_filter(resample)
+    out_size = check_size(out_size)
+    if not on_gpu:
+        raise ValueError("out_size: the resampler runs on the device only, and this model renders on the host")
+    if video is not None and (video.width, video.height) != out_size:
+        raise ValueError("video is an AviWriter of %dx%d, out_size is %dx%d" % (video.width, video.height, out_size[0], out_size[1]))
+    return out_size
+
+
+def _lane_resizer(device, batch, out_size):
+    """a Resizer (its plans and workspace) and the uint8 buffer of the resized frames, both owned by one lane"""
+    from .resize import Resizer
+    return Resizer(device, max_batch=batch), torch.empty((batch, out_size[1], out_size[0], 3), dtype=torch.uint8, device=device)
+
+
 class _null:
     def __enter__(self):
         return None
@@ -177,7 +206,7 @@ def render_frames_from_landmarks(model, landmarks: Iterable, shoulders: Iterable
                                  pad=None, load_size: int = 512, batch: int = 8,
                                  on_frame: Optional[Callable[[int, np.ndarray], None]] = None,
                                  jpeg_quality=None, save_input: bool = False, video=None, audio=None, video_input=None,
-                                 video_route: Optional[str] = None) -> List[np.ndarray]:
+                                 video_route: Optional[str] = None, out_size=None, resample: str = "bicubic") -> List[np.ndarray]:
     """demo.py:260-272 with the edge map drawn on the device: per frame the loop moves the 73 landmarks and the shoulder
     points (~1.5 KB) instead of a host-rasterised 1 MiB feature map.  ``landmarks`` yields [73, 2] arrays (``pred_landmarks[i]``
     of demo.py:262), ``shoulders`` yields [n, 2] arrays (``pred_shoulders[i]``); ``pad`` as ``facedataset.dataset.image_pad``.
@@ -187,9 +216,15 @@ def render_frames_from_landmarks(model, landmarks: Iterable, shoulders: Iterable
     ``np.uint8(map * 255)`` -- written by the rasteriser in the same launch as the float map, and JPEG-encoded (grayscale) with ``jpeg_quality``.
 
     ``video`` / ``audio`` / ``video_route`` as render_frames: the frames go into that AviWriter (``jpeg_quality`` defaults to 75) and the function returns [];
-    with ``save_input`` a second, grayscale writer for the edge maps may be passed as ``video_input`` (it gets the same ``audio`` if it has an audio stream)."""
+    with ``save_input`` a second, grayscale writer for the edge maps may be passed as ``video_input`` (it gets the same ``audio`` if it has an audio stream).
+
+    ``out_size`` / ``resample`` as render_frames: the frames are resampled behind the generator and leave (host copy, JPEG, ``video``) at ``out_size``; the edge maps
+    of ``save_input`` / ``video_input`` stay ``load_size``."""
     from .feature_map import FeatureMapRasteriser
     device = cand_image.device
+    if out_size is not None:
+        out_size = _check_out_size(out_size, resample, device.type == "cuda", video)
+    resizer = small = None
     if video is not None and jpeg_quality is None:
         jpeg_quality = 75
     if video_input is not None and not (save_input and video is not None):
@@ -227,6 +262,10 @@ def render_frames_from_landmarks(model, landmarks: Iterable, shoulders: Iterable
     for maps, edges in chunks():
         u8 = model.inference_image(maps, cand_image)
         b = u8.shape[0]
+        if out_size is not None:
+            if resizer is None:
+                resizer, small = _lane_resizer(device, batch, out_size)
+            u8 = resizer.resize(u8, out_size, resample, out=small[:b])
         if video is not None:
             if sink is None:
                 sink = VideoSink(video, tuple(u8.shape[1:3]), jpeg_quality, device, batch, tracks[0], tracks[1], video_route)

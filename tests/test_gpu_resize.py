@@ -1,0 +1,285 @@
+"""The 8-bit resampler on the device (include/lspresize.h, resize.Resizer) and its three call sites (candidates.load_candidates(resize=),
+render_loop's out_size=, live_render.LivePortraitPool(out_size=)): every comparison is equality with Pillow's pixels, frozen under
+tests/golden (tools/make_golden_resize.py), with live Pillow where it is installed, or with the numpy restatement tests/resize_model.py.
+No tolerance anywhere.  None of this exists on the parent commit: the whole file fails there."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import resize_model as M
+from conftest import GOLDEN
+
+pytestmark = pytest.mark.gpu
+
+CASES = M.cases()
+GEOMS = [g[:4] for g in M.GEOMETRIES]
+
+
+@pytest.fixture(scope="module")
+def fixtures():
+    meta = json.load(open(os.path.join(GOLDEN, "resize.json")))
+    whole = {k: v for k, v in np.load(os.path.join(GOLDEN, "resize.npz")).items() if not k.startswith("candidate_")}
+    assert [c["name"] for c in meta["cases"]] == [c["name"] for c in CASES], "tests/golden/resize.json is not of this case list: run tools/make_golden_resize.py"
+    return {c["name"]: c for c in meta["cases"]}, whole
+
+
+@pytest.fixture(scope="module")
+def resizer(gpu_device):
+    from livespeechportraits_amd.resize import Resizer
+    return Resizer(gpu_device, max_batch=8)
+
+
+def _pillow(batch, case):
+    try:
+        from PIL import Image
+    except ImportError:
+        return None
+    flt = getattr(Image.Resampling, case["filter"].upper())
+    return np.stack([np.asarray(Image.fromarray(im).resize((case["out_w"], case["out_h"]), flt)) for im in batch])
+
+
+@pytest.mark.parametrize("geom", GEOMS, ids=["%dx%d_%dx%d" % g for g in GEOMS])
+def test_device_output_is_pillows_bit_for_bit(resizer, fixtures, geom, gpu_device):
+    """grey and RGB, the five filters, a batch of three DIFFERENT images in one call: the bytes of the fixture (whole, or their SHA-256), and
+    live Pillow's where it is installed (else the model's, for the cases small enough to be quick)"""
+    frozen, whole = fixtures
+    for case in (c for c in CASES if (c["h"], c["w"], c["out_h"], c["out_w"]) == geom):
+        batch = M.batch_of(case)
+        assert not np.array_equal(batch[0], batch[1]) or batch[0].size == 1
+        got = resizer.resize(torch.from_numpy(np.array(batch)).to(gpu_device), (case["out_w"], case["out_h"]), case["filter"],
+                             channels=case["channels"]).cpu().numpy()
+        assert got.dtype == np.uint8 and got.shape == (M.BATCH, case["out_h"], case["out_w"]) + ((3,) if case["channels"] == 3 else ())
+        if case["name"] in whole:
+            assert np.array_equal(got, whole[case["name"]]), case["name"]
+        assert M.sha256(got) == frozen[case["name"]]["sha256"], case["name"]
+        live = _pillow(batch, case)
+        if live is None and batch[0].size <= 64 * 64 * 3:
+            live = np.stack([M.resize(im, (case["out_w"], case["out_h"]), case["filter"]) for im in batch])
+        if live is not None:
+            assert np.array_equal(got, live), case["name"]
+
+
+def test_every_path_is_planned_and_run(resizer):
+    """the accessor names the path of every pass of every geometry: the tile path and the general path (tap counts past the LDS budget) of BOTH
+    passes, the single passes and the copy all occur in the list test_device_output_is_pillows_bit_for_bit runs"""
+    seen = set()
+    for (ih, iw, oh, ow) in GEOMS:
+        for filt in M.FILTERS:
+            p = resizer.plan((iw, ih), (ow, oh), filt)
+            want_h, want_v = iw != ow, ih != oh
+            assert (p.paths[0] is not None) == want_h and (p.paths[1] is not None) == (want_v or not want_h), (ih, iw, oh, ow, filt, p.paths)
+            assert p.launches == (2 if want_h and want_v else 1)
+            seen.add(p.paths)
+            if (ih, iw) == (2100, 1500):
+                assert p.paths[0] == "general" and p.paths[1] == ("general" if filt in ("bicubic", "lanczos") else "tile"), (filt, p.paths)
+            elif (ih, iw) == (1080, 1920) or ih == 512:
+                assert p.paths == ("tile", "tile") and 0 < p.info.lds_h <= 48 * 1024 and 0 < p.info.lds_v <= 48 * 1024
+    assert seen >= {("tile", "tile"), ("general", "general"), ("general", "tile"), (None, "tile"), ("tile", None)}, seen
+
+
+def test_float_planes_through_the_normalisation_table(resizer, gpu_device):
+    """the PLANAR_F32 form equals the table applied to the uint8 result: both passes, one pass each way, and the copy; grey and RGB"""
+    from livespeechportraits_amd.candidates import normalisation_table
+    table = normalisation_table()
+    tdev = torch.from_numpy(table).to(gpu_device)
+    for name in ("37x53_64x48_c3_lanczos", "37x53_64x48_c1_bicubic", "64x64_64x32_c3_bicubic", "64x64_32x64_c3_hamming", "64x64_64x64_c3_box", "257x255_64x64_c3_bilinear"):
+        case = next(c for c in CASES if c["name"] == name)
+        x = torch.from_numpy(np.array(M.batch_of(case))).to(gpu_device)
+        u8 = resizer.resize(x, (case["out_w"], case["out_h"]), case["filter"]).cpu().numpy()
+        ch = case["channels"]
+        big = torch.full((M.BATCH, ch + 2, case["out_h"], case["out_w"]), 7.0, dtype=torch.float32, device=gpu_device)
+        resizer.resize_planes(x, (case["out_w"], case["out_h"]), tdev, big[:, 1:1 + ch], case["filter"])
+        got = big.cpu().numpy()
+        want = table[u8.reshape(M.BATCH, case["out_h"], case["out_w"], ch)].transpose(0, 3, 1, 2)
+        assert np.array_equal(got[:, 1:1 + ch], want), name
+        assert (got[:, 0] == 7.0).all() and (got[:, 1 + ch] == 7.0).all(), name        # the neighbouring planes are untouched
+
+
+def test_the_workspace_content_on_entry_is_irrelevant(resizer, gpu_device):
+    """two different batches through one Resizer, the workspace poisoned with 0xFF in between: the first batch's result again"""
+    a = next(c for c in CASES if c["name"] == "257x255_64x64_c3_lanczos")
+    b = next(c for c in CASES if c["name"] == "100x60_33x200_c3_bicubic")
+    xa, xb = (torch.from_numpy(np.array(M.batch_of(c))).to(gpu_device) for c in (a, b))
+    first = resizer.resize(xa, (a["out_w"], a["out_h"]), a["filter"]).cpu().numpy()
+    assert resizer.workspace.numel() > 0
+    resizer.workspace.fill_(0xFF)
+    other = resizer.resize(xb, (b["out_w"], b["out_h"]), b["filter"]).cpu().numpy()
+    resizer.workspace.fill_(0xFF)
+    again = resizer.resize(xa, (a["out_w"], a["out_h"]), a["filter"]).cpu().numpy()
+    assert np.array_equal(first, again)
+    assert np.array_equal(other, np.stack([M.resize(im, (b["out_w"], b["out_h"]), b["filter"]) for im in M.batch_of(b)]))
+
+
+def test_strided_input_out_slices_and_another_stream(resizer, gpu_device):
+    """a batch taken as every second image of a larger tensor (and from an odd byte offset), out= into a slice of a larger tensor whose
+    other images stay untouched, a single image, all on a stream that is not the current one's default"""
+    case = next(c for c in CASES if c["name"] == "37x53_64x48_c3_bicubic")
+    grey = next(c for c in CASES if c["name"] == "37x53_64x48_c1_lanczos")
+    size = (case["out_w"], case["out_h"])
+    for c in (case, grey):
+        batch = np.array(M.batch_of(c))
+        want = np.stack([M.resize(im, size, c["filter"]) for im in batch])
+        flat = torch.zeros(1 + 6 * batch[0].size, dtype=torch.uint8, device=gpu_device)
+        big = flat[1:].view((6,) + batch.shape[1:])                  # images start at an odd address
+        big[::2] = torch.from_numpy(batch).to(gpu_device)
+        out_big = torch.full((5,) + want.shape[1:], 0x5A, dtype=torch.uint8, device=gpu_device)
+        st = torch.cuda.Stream(gpu_device)
+        st.wait_stream(torch.cuda.current_stream(gpu_device))
+        with torch.cuda.stream(st):
+            ret = resizer.resize(big[::2], size, c["filter"], out=out_big[1:4])
+            one = resizer.resize(big[2], size, c["filter"])
+        st.synchronize()
+        assert ret.data_ptr() == out_big[1:4].data_ptr()
+        got = out_big.cpu().numpy()
+        assert np.array_equal(got[1:4], want), c["name"]
+        assert (got[0] == 0x5A).all() and (got[4] == 0x5A).all()
+        assert np.array_equal(one.cpu().numpy(), want[1])
+
+
+# ---- the three call sites -----------------------------------------------------------------------------------------------------------------
+def _host_resize(frames, size, filt="bicubic"):
+    """Image.resize of uint8 frames on the host: live Pillow where it is installed, else the model"""
+    try:
+        from PIL import Image
+    except ImportError:
+        return np.stack([M.resize(f, size, filt) for f in frames])
+    size = (size, size) if isinstance(size, int) else size
+    return np.stack([np.asarray(Image.fromarray(f).resize(size, getattr(Image.Resampling, filt.upper()))) for f in frames])
+
+
+def test_load_candidates_resamples_photographs_of_any_size(gpu_device):
+    """four JPEG files of different geometries (64x48, 96x96, 33x70, 128x100; width x height; Pillow's encoder, frozen in resize.npz): the
+    tensor is the normalisation table applied to Image.resize of the DECODER's pixels; files of the right size give today's tensor"""
+    import jpeg_model as J
+    from livespeechportraits_amd.candidates import load_candidates, normalisation_table
+    from livespeechportraits_amd.jpeg import JpegDecoder
+    sizes = M.CANDIDATE_SIZES
+    frozen = np.load(os.path.join(GOLDEN, "resize.npz"))
+    files = [frozen["candidate_%d" % j].tobytes() for j in range(4)]
+    pixels = [t.cpu().numpy() for t in JpegDecoder(gpu_device, max_side=128).decode(files)]
+    assert [p.shape for p in pixels] == [(h, w, 3) for w, h in sizes]
+    table = normalisation_table()
+    for filt in ("bicubic", "lanczos"):
+        got = load_candidates(files, gpu_device, size=64, resize=filt).cpu().numpy()
+        assert got.shape == (1, 12, 64, 64) and got.dtype == np.float32
+        for j, p in enumerate(pixels):
+            want = table[_host_resize(p[None], 64, filt)[0]].transpose(2, 0, 1)
+            assert np.array_equal(got[0, 3 * j:3 * j + 3], want), (filt, j)
+    with pytest.raises(ValueError, match="candidate 0 is 64x48"):
+        load_candidates(files, gpu_device, size=64)                # off by default: today's refusal
+    mixed = load_candidates([files[1], files[0], files[1], files[3]], gpu_device, size=96, resize="bicubic").cpu().numpy()      # two files take today's path
+    assert np.array_equal(mixed[0, 0:3], table[pixels[1]].transpose(2, 0, 1)) and np.array_equal(mixed[0, 6:9], mixed[0, 0:3])
+    assert np.array_equal(mixed[0, 3:6], table[_host_resize(pixels[0][None], 96)[0]].transpose(2, 0, 1))
+    right = [J.encode(M.make_image({"kind": "smooth", "h": 64, "w": 64, "channels": 3, "seed": 310 + j}), 90) for j in range(4)]
+    assert torch.equal(load_candidates(right, gpu_device, size=64), load_candidates(right, gpu_device, size=64, resize="bicubic"))
+
+
+def _render_problem(tmp_path, gpu_device, frames=5):
+    from test_gpu_jpeg import _model
+    model, topo, cand = _model(tmp_path, "normal_s64_b3")
+    rng = np.random.default_rng(4)
+    lms = [topo.size / 2 + rng.normal(0, topo.size / 8, (73, 2)) for _ in range(frames)]
+    shs = [np.stack([np.linspace(0, topo.size, 18), np.full(18, topo.size - 10.0)], 1) for _ in range(frames)]
+    return model, topo, torch.from_numpy(cand[:1]).to(gpu_device), lms, shs       # one candidate stack, as demo.py's
+
+
+def test_render_frames_from_landmarks_at_out_size(gpu_device, tmp_path):
+    """a small synthetic `normal` generator (64 x 64 frames), out_size 48 (down), 256 (up) and (320, 180) (not square): the frames are
+    Image.resize of the frames of the same call without out_size; with jpeg_quality the files are JpegEncoder's of those frames; with an
+    AviWriter of out_size the file parses and its chunks are those files; a writer of another geometry is refused before anything runs"""
+    import avi_parser as P
+    from livespeechportraits_amd.jpeg import JpegEncoder
+    from livespeechportraits_amd.render_loop import render_frames_from_landmarks
+    from livespeechportraits_amd.video import AviWriter
+    model, topo, c, lms, shs = _render_problem(tmp_path, gpu_device)
+    kw = dict(pad=(1, 0, 0, 2), load_size=topo.size, batch=2)
+    plain = np.stack(render_frames_from_landmarks(model, lms, shs, c, **kw))
+    assert plain.shape == (5, topo.size, topo.size, 3)
+    for out_size, filt in ((256, "bicubic"), ((320, 180), "bicubic"), (48, "lanczos")):
+        got = np.stack(render_frames_from_landmarks(model, lms, shs, c, out_size=out_size, resample=filt, **kw))
+        assert np.array_equal(got, _host_resize(plain, out_size, filt)), (out_size, filt)
+    small = _host_resize(plain, 256)
+    files = render_frames_from_landmarks(model, lms, shs, c, out_size=256, jpeg_quality=75, **kw)
+    want = JpegEncoder(256, 3, 75, gpu_device, max_batch=5).encode(torch.from_numpy(small).to(gpu_device))
+    assert files == want
+    pairs = render_frames_from_landmarks(model, lms, shs, c, out_size=256, jpeg_quality=75, save_input=True, **kw)
+    assert [p for p, _ in pairs] == want and all(i[:2] == b"\xff\xd8" for _, i in pairs)     # the edge maps stay load_size
+    assert pairs[0][1] == render_frames_from_landmarks(model, lms, shs, c, jpeg_quality=75, save_input=True, **kw)[0][1]
+    path = str(tmp_path / "small.avi")
+    with AviWriter(path, 256, 256, audio_rate=None) as w:
+        assert render_frames_from_landmarks(model, lms, shs, c, out_size=256, video=w, **kw) == []
+    assert P.parse(open(path, "rb").read())["video"] == want
+    with AviWriter(str(tmp_path / "full.avi"), topo.size, topo.size, audio_rate=None) as w:
+        with pytest.raises(ValueError, match="out_size is 256x256"):
+            render_frames_from_landmarks(model, iter(lambda: pytest.fail("ran"), None), shs, c, out_size=256, video=w, **kw)
+        assert w.nframes == 0
+
+
+def test_render_frames_at_out_size_on_two_lanes(gpu_device, tmp_path):
+    """render_frames: 7 maps in batches of 3 on two lanes, each lane resampling on its own stream into its own buffer"""
+    from livespeechportraits_amd import synth
+    from livespeechportraits_amd.jpeg import JpegEncoder
+    from livespeechportraits_amd.render_loop import render_frames
+    model, topo, c, _, _ = _render_problem(tmp_path, gpu_device)
+    feats, _ = synth.make_inputs(7, topo.size, seed=23, cand_batch=1)
+    maps = lambda: (torch.from_numpy(f) for f in feats)
+    plain = np.stack(render_frames(model, maps(), c, batch=3))
+    got = np.stack(render_frames(model, maps(), c, batch=3, out_size=(80, 48), resample="hamming"))
+    assert np.array_equal(got, _host_resize(plain, (80, 48), "hamming"))
+    files = render_frames(model, maps(), c, batch=3, out_size=(80, 48), resample="hamming", jpeg_quality=75)
+    assert files == JpegEncoder((48, 80), 3, 75, gpu_device, max_batch=7).encode(torch.from_numpy(got).to(gpu_device))
+
+
+from test_gpu_live import DEV, models, wave_of  # noqa: E402,F401  (models: the module-scoped fixture)
+from test_gpu_live_render import _avatar, _pieces, generators  # noqa: E402,F401  (generators: the module-scoped fixture)
+
+
+def test_the_live_pool_at_out_size(models, generators, tmp_path):
+    """one short stream pushed in ticks through a pool without out_size and one with out_size=256 (recording): the frames are Image.resize of
+    the plain pool's, the `video` file's chunks are the JPEG files of those frames, `video_input` stays 512 x 512, last_groups is unchanged"""
+    import avi_parser as P
+    from test_gpu_landmarks import make_stage
+    from test_gpu_live_pool import pool_of
+    from livespeechportraits_amd.jpeg import JpegEncoder
+    from livespeechportraits_amd.live_render import LivePortraitPool
+    from livespeechportraits_amd.video import AviWriter
+    gens, cand = generators
+    meta, cfg = _avatar()
+    clip = wave_of(int(60 * 16000 / 60) + 1, seed=77)                # (the pool emits the frames whose lookahead the clip still covers: about 45)
+    pieces = _pieces(len(clip), 5, top=3000)
+
+    def run(pool, jpeg_quality=None, **open_kw):
+        sid = pool.open(np.zeros(12, np.float32), torch.Generator().manual_seed(9), **open_kw)
+        frames, groups, at = [], [], 0
+        for k, n in enumerate(pieces):
+            start, f = pool.tick({sid: clip[at:at + n]}, finish=[sid] if k == len(pieces) - 1 else [], jpeg_quality=jpeg_quality)[sid]
+            assert start == sum(len(x) for x in frames)
+            frames.append(f if jpeg_quality else f.cpu().numpy())
+            groups.append(pool.last_groups)
+            at += n
+        return (sum(frames, []) if jpeg_quality else np.concatenate(frames)), groups
+
+    plain, groups = run(LivePortraitPool(pool_of(models, max_sessions=1), make_stage(cfg, meta, DEV, max_sessions=1), gens["f32"], cand, max_batch=4))
+    assert plain.shape[0] >= 20 and plain.shape[1:] == (512, 512, 3)
+    pool = LivePortraitPool(pool_of(models, max_sessions=1), make_stage(cfg, meta, DEV, max_sessions=1), gens["f32"], cand, max_batch=4, record_quality=75,
+                            out_size=256)
+    with AviWriter(str(tmp_path / "big.avi"), 512, 512, audio_rate=None) as big:
+        with pytest.raises(ValueError, match="video must be an AviWriter of 256x256"):
+            pool.open(np.zeros(12, np.float32), video=big)
+    assert not pool.open_sessions
+    video = AviWriter(str(tmp_path / "v.avi"), 256, 256, audio_rate=None)
+    edges = AviWriter(str(tmp_path / "e.avi"), 512, 512, channels=1, audio_rate=None)
+    small, small_groups = run(pool, video=video, video_input=edges)
+    video.close(), edges.close()
+    assert small_groups == groups
+    assert np.array_equal(small, _host_resize(plain, 256))
+    enc = JpegEncoder(256, 3, 75, DEV, max_batch=4)
+    want = [f for g0 in range(0, len(small), 4) for f in enc.encode(torch.from_numpy(small[g0:g0 + 4]).to(DEV))]
+    assert P.parse(open(video.path, "rb").read())["video"] == want
+    gray = P.parse(open(edges.path, "rb").read())
+    assert len(gray["video"]) == len(small) and (gray["avih"]["dwWidth"], gray["avih"]["dwHeight"]) == (512, 512)
+    # the files a tick hands out with jpeg_quality are out_size too (the groups differ from the recording's, the files do not)
+    assert run(pool, jpeg_quality=75)[0] == want
