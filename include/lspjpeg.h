@@ -20,12 +20,28 @@
  *              with ZRL and EOB; id 0 for Y, 1 for Cb and Cr; DC differences under the restart rule), and jpeg_gen_optimal_table builds each
  *              table (csrc/jpegenc_core.h states it).  The frame's bytes are then DHT DC0, AC0 [, DC1, AC1] (a segment each), [DRI,] SOS, the
  *              scan, EOI, and lspjpeg_header() ends behind SOF0.  A file is header + frame bytes either way.
- * Not supported: 4:4:4, progressive, EXIF / ICC.
+ * A format handle (lspjpeg_create_format; Pillow's subsampling=0 / 1 / 2 and pictures of any size), still byte for byte Pillow's file.  With
+ * luma factors (hs, vs) = (2, 2) for 4:2:0, (2, 1) for 4:2:2, (1, 1) for 4:4:4 (csrc/jpegenc_geom.h states the grid):
+ *   MCU grid   colour: ceil(W / 8hs) x ceil(H / 8vs) MCUs, each its hs * vs luma blocks (row-major), Cb, Cr.  Grey: a non-interleaved scan, one
+ *              block per MCU, ceil(W / 8) x ceil(H / 8) blocks.  SOF0 carries the true W and H, hs << 4 | vs for luma and 0x11 for chroma.
+ *   columns    jcsample.c expand_right_edge: the last pixel of a row is repeated BEFORE downsampling, and the bias patterns run on from column 0
+ *              into the padding: h2v2 (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2 ...; h2v1 (a + b + bias) >> 1 with bias 0, 1, 0, 1 ...;
+ *              4:4:4 chroma is the converted sample itself.
+ *   rows       jcprepct.c: the last pixel row is repeated up to a multiple of vs only; the plane is downsampled; then the last row of each
+ *              COMPONENT plane is repeated down to the block grid (for even H under 4:2:0 the padded chroma rows repeat box(H - 2, H - 1)).
+ *   dummy      jccoefct.c: a luma block of an edge MCU whose column >= ceil(W / 8) or row >= ceil(H / 8) is not transformed: its AC coefficients
+ *              are 0 and its quantised DC is that of the block before it in the MCU's coding order (a chain: Y3 = Y2 = Y1 = Y0 in the bottom-right
+ *              MCU).  It codes as DC category 0 + EOB, and counts in optimize's histograms and in the DC prediction.  The first luma block of an
+ *              MCU and the chroma blocks are never dummy.
+ *   restart    the interval counts MCUs of that grid (Pillow's restart_marker_rows: rows * MCUs per row, capped at 65535).
+ *   the rest   tables, DCT, quantiser, entropy coding, stuffing, optimize, DRI / RSTn: as above.
+ * Not supported: other sampling factors, progressive, EXIF / ICC.
  *
  * Output bound (per frame, what lspjpeg_capacity_bytes() returns): a block codes at most 11 + 11 bits of DC (longest DC code, 11-bit
  * difference) and at most 63 AC symbols of <= 16 + 10 bits (a nonzero coefficient, a ZRL for 16 zeros or one EOB per block: never more
  * symbols than AC positions), so T <= 1660 bits per block; stuffing at most doubles the ceil(T / 8) bytes; + 2 bytes of EOI:
  *     capacity = 2 * ceil(blocks * 1660 / 8) + 2,   blocks = H * W / 64 * (components == 3 ? 1.5 : 1)
+ * (a format handle: blocks = MCUs * blocks per MCU of its grid, dummy blocks included: a dummy block codes 6 bits without optimize: category 0 and EOB)
  * Nothing the encoder writes can pass it, so there is no overflow path.
  * A handle made with options restates the bound from its parts (a handle without keeps the value above exactly):
  *   bits per block  B = 1660 with the Annex K tables; 1665 with optimize, where a DC code can be 16 bits long: 16 + 11 + 63 * (16 + 10);
@@ -59,7 +75,7 @@ extern "C" {
 #define LSPJPEG_ERR_UNSUPPORTED (-2)
 #define LSPJPEG_ERR_HIP (-3)
 
-#define LSPJPEG_MAX_SIDE 8192       /* keeps a frame's bit offsets below 2^32 */
+#define LSPJPEG_MAX_SIDE 8192       /* keeps a frame's bit offsets below 2^32 (4:2:0 and grey; lspjpeg_create_format checks its own grid) */
 #define LSPJPEG_BLOCK_BITS 1660     /* worst-case coded bits of one 8x8 block (see the bound above) */
 
 typedef struct lspjpeg_handle lspjpeg_handle;
@@ -77,6 +93,23 @@ typedef struct lspjpeg_options {
     int32_t restart_interval;   /* MCUs per restart interval, 0 = none, at most 65535 */
 } lspjpeg_options;
 int lspjpeg_create_opts(const lspjpeg_options *o, lspjpeg_handle **out);
+
+/* Frames of any size in 4:4:4, 4:2:2 or 4:2:0, or grey frames of any size; abi_version = LSPJPEG_FORMAT_ABI_VERSION.  The same kind of handle:
+ * header, capacity_bytes, workspace_bytes, encode and destroy work on it unchanged, in four launches.  A format whose geometry lspjpeg_create
+ * takes (4:2:0 with both sides multiples of 16, grey with multiples of 8) gives that handle and its kernels (src_dev 16-byte aligned); any
+ * other runs kernels of its own, which read src_dev byte by byte: no alignment is asked of it.
+ * Refused before any device work: INVALID_ARGUMENT for values out of range (abi_version, quality, sides outside 1..LSPJPEG_MAX_SIDE, optimize,
+ * restart_interval, factors outside 1..4, a grey frame with factors other than (1, 1)); UNSUPPORTED for components other than 1 or 3, for a
+ * factor pair other than the three above, e.g. (1, 2), and for a grid whose worst-case bit count blocks * 1665 does not fit 32 bits (4:4:4 at
+ * 8192 x 8192). */
+#define LSPJPEG_FORMAT_ABI_VERSION 1
+typedef struct lspjpeg_format {
+    int32_t abi_version;
+    int32_t width, height, components, quality;   /* any 1..LSPJPEG_MAX_SIDE */
+    int32_t optimize, restart_interval;            /* as lspjpeg_options */
+    int32_t h_samp, v_samp;                        /* luma: (2,2) (2,1) (1,1); components 1: (1,1) */
+} lspjpeg_format;
+int lspjpeg_create_format(const lspjpeg_format *f, lspjpeg_handle **out);
 int lspjpeg_destroy(lspjpeg_handle *h);
 const char *lspjpeg_last_error(void);
 
@@ -97,6 +130,12 @@ int lspjpeg_encode(const lspjpeg_handle *h, const unsigned char *src_dev, int ba
 /* jpeg_gen_optimal_table on the host, with the code the kernel runs (csrc/jpegenc_core.h): freq[s] occurrences of symbol s -> bits[1..16]
  * codes per length (bits[0] = 0), the symbols in code order, and their number.  For the tests. */
 int lspjpeg_host_optimal_table(const uint32_t freq[256], unsigned char bits[17], unsigned char huffval[256], int *nsymbols);
+
+/* The block grid of a format on the host, with the code the kernels run (csrc/jpegenc_geom.h): per coded block, in coding order, six int32:
+ * component (0 Y, 1 Cb, 2 Cr), block column and row in the component's plane, dummy (0 / 1), the index of the previous block of the component
+ * in the frame (-1 for the first), and the index of the block whose quantised DC this one codes (itself unless dummy).  map may be NULL to
+ * query; returns the number of blocks, or a negative code (the refusals of lspjpeg_create_format).  For the tests. */
+int64_t lspjpeg_host_block_map(const lspjpeg_format *f, int32_t *map, size_t cap_blocks);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -307,11 +307,21 @@ class JpegEncOptions(ctypes.Structure):
 
 JPEG_ABI_VERSION = 1
 
+
+class JpegEncFormat(ctypes.Structure):
+    """lspjpeg_format"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("abi_version", "width", "height", "components", "quality", "optimize", "restart_interval", "h_samp", "v_samp")]
+
+
+JPEG_FORMAT_ABI_VERSION = 1
+
 # every symbol include/lspjpeg.h declares
 JPEG_SIGNATURES = {
     "lspjpeg_create": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     "lspjpeg_create_opts": (c_int, [POINTER(JpegEncOptions), POINTER(c_void_p)]),
+    "lspjpeg_create_format": (c_int, [POINTER(JpegEncFormat), POINTER(c_void_p)]),
     "lspjpeg_host_optimal_table": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
+    "lspjpeg_host_block_map": (c_int64, [POINTER(JpegEncFormat), c_void_p, c_size_t]),
     "lspjpeg_destroy": (c_int, [c_void_p]),
     "lspjpeg_last_error": (c_char_p, []),
     "lspjpeg_header": (c_int64, [c_void_p, c_void_p, c_size_t]),

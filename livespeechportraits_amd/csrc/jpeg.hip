@@ -17,6 +17,12 @@
 // jpegenc_core.h, the frame's DHT .. SOS, bit offsets per block and byte offsets per interval), jpeg_emit<true> (codes from the workspace, every
 // interval padded on its own), jpeg_stuff<true> (RSTn behind every interval but the last).  The options are template parameters: the
 // instances of a plain handle hold none of that code.
+//
+// A format handle (lspjpeg_create_format: frames of any size in 4:4:4, 4:2:2, 4:2:0 or grey) whose geometry is not the one above runs four launches
+// as well: jpeg_transform_geom (thread per coded block of the grid of jpegenc_geom.h, dummy blocks included; pixels read byte by byte at clamped
+// coordinates), jpeg_tables_geom and jpeg_emit_geom (the bodies of jpeg_tables and jpeg_emit<true> with the block's table and its DC difference
+// taken from that grid: a dummy block's DC is read at its DC source), and jpeg_stuff<true> itself.  With the geometry above it gets the handle and
+// the instances above.
 #include "../../include/lspjpeg.h"
 
 #include <hip/hip_runtime.h>
@@ -26,6 +32,7 @@
 #include <vector>
 
 #include "jpegenc_core.h"
+#include "jpegenc_geom.h"
 
 namespace lspjpeg {
 
@@ -110,6 +117,12 @@ struct OptParams : Params {
 template <bool kOpts>
 using ParamsOf = std::conditional_t<kOpts, OptParams, Params>;
 
+// a format handle of another geometry than the two above (lspjpeg_create_format: any size, 4:4:4 / 4:2:2 / 4:2:0 / grey) runs the *_geom instances:
+// the MCU layout comes from jpegenc_geom.h, the rest is the code of a handle with options
+struct GeomParams : OptParams {
+    lspgeom::Geom geo;
+};
+
 // ---- device helpers ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int nbits(int v)
 {
@@ -167,6 +180,8 @@ __device__ __forceinline__ int prev_block(int g, int comps)
 }
 
 __device__ __forceinline__ int table_of(int g, int comps) { return comps == 3 && g % 6 >= 4 ? 1 : 0; }
+__device__ __forceinline__ int table_of(const Params &p, int g) { return table_of(g, p.comps); }
+__device__ __forceinline__ int table_of(const GeomParams &p, int g) { return lspgeom::table_of(p.geo, g); }
 
 // exclusive prefix sum over the NS threads of the workgroup; *total = the sum.  `lds` holds NS / 64 + 1 words.
 __device__ __forceinline__ unsigned block_scan(unsigned v, unsigned *lds, unsigned *total)
@@ -194,6 +209,31 @@ __device__ __forceinline__ unsigned block_scan(unsigned v, unsigned *lds, unsign
     *total = lds[NS / 64];
     __syncthreads();                        // lds is reused by the next call
     return r;
+}
+
+// islow DCT of the level-shifted samples s, quantisation (round half away from zero) with the divisors div (natural order), and the block's
+// coefficients in zigzag order: in z, and as 64 shorts at dst.  The tail of jpeg_transform below, for jpeg_transform_geom (jpeg_transform keeps its
+// own text: its instances are the code objects a handle of lspjpeg_create has always launched)
+__device__ __forceinline__ void dct_quantise_store(int (&s)[64], const unsigned short (&div)[64], int (&z)[64], short *dst)
+{
+#pragma unroll
+    for (int r = 0; r < 8; ++r) fdct_pass<true, 1>(s + r * 8);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) fdct_pass<false, 8>(s + c);
+#pragma unroll
+    for (int k = 0; k < 64; ++k) {
+        const int v = s[kNatural[k]];
+        const unsigned d = div[kNatural[k]];
+        const unsigned a = ((unsigned)(v < 0 ? -v : v) + (d >> 1)) / d;
+        z[k] = v < 0 ? -(int)a : (int)a;
+    }
+    uint4 *out = reinterpret_cast<uint4 *>(dst);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int *zz = z + k * 8;
+        out[k] = make_uint4((zz[0] & 0xffff) | ((unsigned)zz[1] << 16), (zz[2] & 0xffff) | ((unsigned)zz[3] << 16),
+                            (zz[4] & 0xffff) | ((unsigned)zz[5] << 16), (zz[6] & 0xffff) | ((unsigned)zz[7] << 16));
+    }
 }
 
 // ---- 1. transform + quantise + AC bits ----------------------------------------------------------------------------------------
@@ -311,6 +351,85 @@ __global__ __launch_bounds__(NT) void jpeg_transform(ParamsOf<kOpts> p)
     }
 }
 
+// ---- 1'. the same for a format handle of any geometry ----------------------------------------------------------------------------------
+// jccolor.c: one converted sample of component `comp` (0 Y, 1 Cb, 2 Cr) from the three bytes at px
+__device__ __forceinline__ int ycc_sample(const unsigned char *px, int comp)
+{
+    const int R = px[0], G = px[1], B = px[2];
+    if (comp == 0) return (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
+    const int kr = comp == 2 ? 32768 : -11059, kg = comp == 2 ? -27439 : -21709, kb = comp == 2 ? -5329 : 32768;
+    return (kr * R + kg * G + kb * B + (128 << 16) + 32767) >> 16;
+}
+
+// The 64 level-shifted samples of a chroma block under luma factors (HS, VS).  jcsample.c / jcprepct.c at the edges: pixel columns repeat the
+// last one BEFORE the box (the bias pattern runs on from column 0 of the plane: block columns start even), pixel rows repeat the last one up to a
+// multiple of VS only, and below that the last row of the COMPONENT plane repeats: the row index is clamped in the plane, then in the picture.
+template <int HS, int VS>
+__device__ __forceinline__ void chroma_samples(const lspgeom::Geom &G, const lspgeom::Block &b, const unsigned char *src, int (&s)[64])
+{
+    const int crows = lspgeom::ceil_div(G.h, VS);
+    const size_t row = (size_t)G.w * 3;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int cy = min(b.by * 8 + r, crows - 1);
+#pragma unroll
+        for (int x = 0; x < 8; ++x) {
+            const int cx = b.bx * 8 + x;
+            int sum = 0;
+#pragma unroll
+            for (int rr = 0; rr < VS; ++rr) {
+                const unsigned char *line = src + (size_t)min(cy * VS + rr, G.h - 1) * row;
+#pragma unroll
+                for (int cc = 0; cc < HS; ++cc) sum += ycc_sample(line + (size_t)min(cx * HS + cc, G.w - 1) * 3, b.comp);
+            }
+            if (HS == 2 && VS == 2)
+                sum = (sum + 1 + (x & 1)) >> 2;                 // h2v2_downsample: bias 1, 2, 1, 2 ...
+            else if (HS == 2)
+                sum = (sum + (x & 1)) >> 1;                     // h2v1_downsample: bias 0, 1, 0, 1 ...
+            s[r * 8 + x] = sum - 128;
+        }
+    }
+}
+
+// Thread per coded block in coding order, dummy blocks included (zero coefficients: their DC is resolved where the differences are formed).  Pixels
+// are read byte by byte at clamped coordinates: with an odd width neither a row nor a frame of the batch starts on an aligned address.
+__global__ __launch_bounds__(NT) void jpeg_transform_geom(GeomParams p)
+{
+    const int f = blockIdx.y;
+    const int g = blockIdx.x * NT + threadIdx.x;
+    if (g >= p.nblk) return;
+    const lspgeom::Geom &G = p.geo;
+    const lspgeom::Block b = lspgeom::block_of(G, g);
+    short *dst = p.coef + ((size_t)f * p.nblk + g) * 64;
+    if (b.dummy) {
+        uint4 *out = reinterpret_cast<uint4 *>(dst);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) out[k] = make_uint4(0u, 0u, 0u, 0u);
+        return;
+    }
+    const unsigned char *src = p.src + (size_t)f * G.h * G.w * G.comps;
+    int s[64];
+    if (b.comp == 0) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const unsigned char *line = src + (size_t)min(b.by * 8 + r, G.h - 1) * G.w * G.comps;
+#pragma unroll
+            for (int x = 0; x < 8; ++x) {
+                const int px = min(b.bx * 8 + x, G.w - 1);
+                s[r * 8 + x] = (G.comps == 1 ? (int)line[px] : ycc_sample(line + (size_t)px * 3, 0)) - 128;
+            }
+        }
+    } else if (G.vs == 2) {
+        chroma_samples<2, 2>(G, b, src, s);
+    } else if (G.hs == 2) {
+        chroma_samples<2, 1>(G, b, src, s);
+    } else {
+        chroma_samples<1, 1>(G, b, src, s);
+    }
+    int z[64];
+    dct_quantise_store(s, p.div[b.comp ? 1 : 0], z, dst);
+}
+
 __device__ __forceinline__ int dc_diff(const Params &p, int f, int g)
 {
     const short *c = p.coef + (size_t)f * p.nblk * 64;
@@ -348,6 +467,15 @@ __device__ __forceinline__ int dc_diff_opts(const OptParams &p, int f, int g)   
     const short *c = p.coef + (size_t)f * p.nblk * 64;
     const int pg = lspenc::pred_block(g, p.ibl, p.bpm);
     return (int)c[(size_t)g * 64] - (pg >= 0 ? (int)c[(size_t)pg * 64] : 0);
+}
+
+// the same on the grid of jpegenc_geom.h; a dummy block's DC is read where its chain of copies starts (dc_src), on both sides of the difference
+__device__ __forceinline__ int dc_diff_opts(const GeomParams &p, int f, int g)
+{
+    const short *c = p.coef + (size_t)f * p.nblk * 64;
+    const lspgeom::Block b = lspgeom::block_of(p.geo, g);
+    const int pg = lspgeom::pred_block(b, g, p.ibl);
+    return (int)c[(size_t)b.dc_src * 64] - (pg >= 0 ? (int)c[(size_t)lspgeom::block_of(p.geo, pg).dc_src * 64] : 0);
 }
 
 // fn(symbol) for every AC symbol of a block, in scan order: (run << 4) | size, 0xF0 (ZRL), 0x00 (EOB); jchuff.c encode_one_block / htest_one_block
@@ -396,7 +524,8 @@ struct WaveMin {
 // the codes; (c) all threads write DHT per table, DRI, SOS at the start of the frame's bytes.  Without: the Annex K codes.  Then, as jpeg_offsets,
 // (d) the bits of every block and their exclusive scan S, (e) per interval ceil((S[end] - S[begin]) / 8) bytes and their scan, and the zeroed
 // stream words.  jpeg_emit puts block g of interval i at bit 8 * istart[i] + S[g] - S[begin of i].
-__global__ __launch_bounds__(NS) void jpeg_tables(OptParams p)
+template <class P>                                              // OptParams, or GeomParams for the grid of jpegenc_geom.h
+__device__ __forceinline__ void tables_body(const P p)
 {
     __shared__ unsigned lds[NS / 64 + 1];
     __shared__ unsigned codes[4][256];
@@ -413,7 +542,7 @@ __global__ __launch_bounds__(NS) void jpeg_tables(OptParams p)
         __syncthreads();
         unsigned eob[2] = {0u, 0u};
         for (int g = tid; g < p.nblk; g += NS) {
-            const int tab = table_of(g, p.comps);
+            const int tab = table_of(p, g);
             atomicAdd(&hist[2 * tab][nbits(dc_diff_opts(p, f, g))], 1u);
             unsigned *h = hist[2 * tab + 1];
             unsigned e = 0;
@@ -478,7 +607,7 @@ __global__ __launch_bounds__(NS) void jpeg_tables(OptParams p)
         const int g = base + tid;
         unsigned b = 0;
         if (g < p.nblk) {
-            const int tab = table_of(g, p.comps);
+            const int tab = table_of(p, g);
             const int nb = nbits(dc_diff_opts(p, f, g));
             b = (codes[2 * tab][nb] >> 16) + nb;
             const unsigned *ac = codes[2 * tab + 1];
@@ -511,6 +640,9 @@ __global__ __launch_bounds__(NS) void jpeg_tables(OptParams p)
     for (unsigned i = tid; i < nw; i += NS) w[i] = 0u;
 }
 
+__global__ __launch_bounds__(NS) void jpeg_tables(OptParams p) { tables_body(p); }
+__global__ __launch_bounds__(NS) void jpeg_tables_geom(GeomParams p) { tables_body(p); }
+
 // ---- 3. the symbols of every block at its offset ---------------------------------------------------------------------------------
 struct BitWriter {
     unsigned *w;
@@ -535,13 +667,13 @@ struct BitWriter {
 
 __device__ __forceinline__ unsigned value_bits(int v, int nb) { return (unsigned)(v < 0 ? v - 1 : v) & ((1u << nb) - 1u); }
 
-template <bool kOpts>
-__global__ __launch_bounds__(NT) void jpeg_emit(ParamsOf<kOpts> p)
+template <bool kOpts, class P>
+__device__ __forceinline__ void emit_body(const P p)
 {
     const int f = blockIdx.y;
     const int g = blockIdx.x * NT + threadIdx.x;
     if (g >= p.nblk) return;
-    const int tab = table_of(g, p.comps);
+    const int tab = table_of(p, g);
     unsigned off;
     int diff;
     const unsigned *dc, *acv;
@@ -599,6 +731,10 @@ __global__ __launch_bounds__(NT) void jpeg_emit(ParamsOf<kOpts> p)
     }
     bw.flush();
 }
+
+template <bool kOpts>
+__global__ __launch_bounds__(NT) void jpeg_emit(ParamsOf<kOpts> p) { emit_body<kOpts>(p); }
+__global__ __launch_bounds__(NT) void jpeg_emit_geom(GeomParams p) { emit_body<true>(p); }
 
 // ---- 4. bytes, padding, stuffing, EOI ---------------------------------------------------------------------------------------------
 // With options the stream arrives padded per interval (jpeg_emit), starts behind the frame's DHT .. SOS, and RSTn follows the last byte of every
@@ -713,6 +849,9 @@ struct lspjpeg_handle {
     std::vector<unsigned char> header;
     bool opts;                              // made with optimize or a restart interval: the *<true> instances and jpeg_tables
     int optimize, restart, nint, ibl, bpm;
+    int hs, vs;                             // luma sampling factors
+    bool general;                           // a format handle of another geometry than lspjpeg_create's: the *_geom instances
+    lspgeom::Geom geo;
 };
 
 namespace {
@@ -747,7 +886,7 @@ void build_header(lspjpeg_handle *h, const unsigned char (&q)[2][64])
     v.push_back((unsigned char)h->comps);
     for (int c = 0; c < h->comps; ++c) {
         v.push_back((unsigned char)(c + 1));
-        v.push_back(c == 0 && h->comps == 3 ? 0x22 : 0x11);
+        v.push_back(c == 0 ? (unsigned char)(h->hs << 4 | h->vs) : 0x11);
         v.push_back(c == 0 ? 0 : 1);
     }
     if (h->optimize) return;                // DHT, DRI and SOS are the frame's own
@@ -787,35 +926,23 @@ extern "C" {
 
 const char *lspjpeg_last_error(void) { return g_err.c_str(); }
 
-static int create(int width, int height, int components, int quality, int optimize, int restart, lspjpeg_handle **out)
+// everything of a handle that does not depend on how its MCU grid is laid out: intervals, buffer sizes, tables, header
+static void finish(lspjpeg_handle *h, int quality, int optimize, int restart)
 {
-    if (components != 1 && components != 3) return fail(LSPJPEG_ERR_UNSUPPORTED, "components must be 3 (RGB, 4:2:0) or 1 (grayscale)");
-    if (quality < 1 || quality > 100) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "quality must be in 1..100");
-    const int m = components == 3 ? 16 : 8;
-    if (width < m || height < m || width % m || height % m || width > LSPJPEG_MAX_SIDE || height > LSPJPEG_MAX_SIDE)
-        return fail(LSPJPEG_ERR_UNSUPPORTED, "width and height must be multiples of " + std::to_string(m) + " in " + std::to_string(m) + ".." +
-                                                 std::to_string(LSPJPEG_MAX_SIDE) + " (got " + std::to_string(width) + "x" + std::to_string(height) + ")");
-    lspjpeg_handle *h = new lspjpeg_handle();
-    h->w = width;
-    h->h = height;
-    h->comps = components;
     h->quality = quality;
-    h->mcux = width / m;
-    h->nmcu = h->mcux * (height / m);
-    h->nblk = h->nmcu * (components == 3 ? 6 : 1);
     h->optimize = optimize;
     h->restart = restart;
     h->opts = optimize || restart > 0;
-    h->bpm = components == 3 ? 6 : 1;
     h->nint = lspenc::interval_count(h->nmcu, restart);
     h->ibl = lspenc::interval_blocks(h->nmcu, restart, h->bpm);
-    if (h->opts) {
+    if (h->opts || h->general) {            // (the *_geom instances lay the stream out as a handle with options does)
         const size_t bytes = (size_t)lspenc::stream_bytes_bound((uint64_t)h->nblk, (uint64_t)h->nint, optimize ? lspenc::kBlockBitsOpt : lspenc::kBlockBitsStd);
         h->wcap = (int)(((bytes + 3) / 4 + 1 + 3) & ~(size_t)3);
         h->cap = (size_t)lspenc::capacity_bound((uint64_t)h->nblk, (uint64_t)h->nint, optimize);
-    } else {
+    }
+    if (!h->opts) {                         // no options: the bound of lspjpeg_create, whatever the geometry
         const size_t bits = (size_t)h->nblk * LSPJPEG_BLOCK_BITS;
-        h->wcap = (int)(((bits + 31) / 32 + 1 + 3) & ~(size_t)3);
+        if (!h->general) h->wcap = (int)(((bits + 31) / 32 + 1 + 3) & ~(size_t)3);
         h->cap = 2 * ((bits + 7) / 8) + 2;
     }
     // jcparam.c jpeg_quality_scaling + jpeg_add_quant_table(force_baseline = TRUE)
@@ -831,10 +958,30 @@ static int create(int width, int height, int components, int quality, int optimi
         }
     }
     build_header(h, q);
+}
+
+static int create(int width, int height, int components, int quality, int optimize, int restart, lspjpeg_handle **out)
+{
+    if (components != 1 && components != 3) return fail(LSPJPEG_ERR_UNSUPPORTED, "components must be 3 (RGB, 4:2:0) or 1 (grayscale)");
+    if (quality < 1 || quality > 100) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "quality must be in 1..100");
+    const int m = components == 3 ? 16 : 8;
+    if (width < m || height < m || width % m || height % m || width > LSPJPEG_MAX_SIDE || height > LSPJPEG_MAX_SIDE)
+        return fail(LSPJPEG_ERR_UNSUPPORTED, "width and height must be multiples of " + std::to_string(m) + " in " + std::to_string(m) + ".." +
+                                                 std::to_string(LSPJPEG_MAX_SIDE) + " (got " + std::to_string(width) + "x" + std::to_string(height) + ")");
+    lspjpeg_handle *h = new lspjpeg_handle();
+    h->w = width;
+    h->h = height;
+    h->comps = components;
+    h->mcux = width / m;
+    h->nmcu = h->mcux * (height / m);
+    h->nblk = h->nmcu * (components == 3 ? 6 : 1);
+    h->bpm = components == 3 ? 6 : 1;
+    h->hs = h->vs = components == 3 ? 2 : 1;
+    h->general = false;
+    finish(h, quality, optimize, restart);
     *out = h;
     return LSPJPEG_OK;
 }
-
 int lspjpeg_create(int width, int height, int components, int quality, lspjpeg_handle **out)
 {
     if (!out) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "null out");
@@ -852,6 +999,72 @@ int lspjpeg_create_opts(const lspjpeg_options *o, lspjpeg_handle **out)
     if (o->optimize != 0 && o->optimize != 1) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "optimize must be 0 or 1");
     if (o->restart_interval < 0 || o->restart_interval > 65535) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "restart_interval must be in 0..65535 MCUs");
     return create(o->width, o->height, o->components, o->quality, o->optimize, o->restart_interval, out);
+}
+
+// the refusals of lspjpeg_create_format, in the order include/lspjpeg.h states them; *g receives the grid
+static int check_format(const lspjpeg_format *f, lspgeom::Geom *g)
+{
+    if (!f) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "null format");
+    if (f->abi_version != LSPJPEG_FORMAT_ABI_VERSION)
+        return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "lspjpeg_format.abi_version is " + std::to_string(f->abi_version) + ", this library speaks " + std::to_string(LSPJPEG_FORMAT_ABI_VERSION));
+    if (f->components != 1 && f->components != 3) return fail(LSPJPEG_ERR_UNSUPPORTED, "components must be 3 (RGB) or 1 (grayscale)");
+    if (f->quality < 1 || f->quality > 100) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "quality must be in 1..100");
+    if (f->width < 1 || f->height < 1 || f->width > LSPJPEG_MAX_SIDE || f->height > LSPJPEG_MAX_SIDE)
+        return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "width and height must be in 1.." + std::to_string(LSPJPEG_MAX_SIDE) + " (got " + std::to_string(f->width) + "x" + std::to_string(f->height) + ")");
+    if (f->optimize != 0 && f->optimize != 1) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "optimize must be 0 or 1");
+    if (f->restart_interval < 0 || f->restart_interval > 65535) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "restart_interval must be in 0..65535 MCUs");
+    if (f->h_samp < 1 || f->h_samp > 4 || f->v_samp < 1 || f->v_samp > 4) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "h_samp and v_samp must be in 1..4");
+    const bool one = f->h_samp == 1 && f->v_samp == 1;
+    if (f->components == 1 && !one) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "a grayscale frame has sampling factors (1, 1)");
+    if (!one && !(f->h_samp == 2 && f->v_samp <= 2))
+        return fail(LSPJPEG_ERR_UNSUPPORTED, "luma sampling factors must be (2, 2) 4:2:0, (2, 1) 4:2:2 or (1, 1) 4:4:4 (got (" + std::to_string(f->h_samp) + ", " + std::to_string(f->v_samp) + "))");
+    *g = lspgeom::make_geom(f->width, f->height, f->components, f->h_samp, f->v_samp);
+    if ((uint64_t)g->nblk * lspenc::kBlockBitsOpt > 0xffffffffull)
+        return fail(LSPJPEG_ERR_UNSUPPORTED, std::to_string(g->nblk) + " blocks per frame: their worst-case bits do not fit the 32-bit offsets of a frame");
+    return LSPJPEG_OK;
+}
+
+int lspjpeg_create_format(const lspjpeg_format *f, lspjpeg_handle **out)
+{
+    if (!out) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    lspgeom::Geom g;
+    const int rc = check_format(f, &g);
+    if (rc) return rc;
+    // the geometry of lspjpeg_create: that handle, with the kernels it has always run
+    const int m = g.comps == 3 ? 16 : 8;
+    if ((g.comps == 1 || (g.hs == 2 && g.vs == 2)) && g.w % m == 0 && g.h % m == 0) return create(g.w, g.h, g.comps, f->quality, f->optimize, f->restart_interval, out);
+    lspjpeg_handle *h = new lspjpeg_handle();
+    h->w = g.w;
+    h->h = g.h;
+    h->comps = g.comps;
+    h->mcux = g.mcux;
+    h->nmcu = g.nmcu;
+    h->nblk = g.nblk;
+    h->bpm = g.bpm;
+    h->hs = g.hs;
+    h->vs = g.vs;
+    h->general = true;
+    h->geo = g;
+    finish(h, f->quality, f->optimize, f->restart_interval);
+    *out = h;
+    return LSPJPEG_OK;
+}
+
+int64_t lspjpeg_host_block_map(const lspjpeg_format *f, int32_t *map, size_t cap_blocks)
+{
+    lspgeom::Geom g;
+    const int rc = check_format(f, &g);
+    if (rc) return rc;
+    if (map) {
+        if (cap_blocks < (size_t)g.nblk) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "the map needs room for " + std::to_string(g.nblk) + " blocks");
+        for (int i = 0; i < g.nblk; ++i) {
+            const lspgeom::Block b = lspgeom::block_of(g, i);
+            const int32_t row[6] = {b.comp, b.bx, b.by, b.dummy, b.prev, b.dc_src};
+            std::copy(row, row + 6, map + (size_t)i * 6);
+        }
+    }
+    return g.nblk;
 }
 
 int lspjpeg_host_optimal_table(const uint32_t freq[256], unsigned char bits[17], unsigned char huffval[256], int *nsymbols)
@@ -890,7 +1103,7 @@ static size_t workspace_layout(const lspjpeg_handle *h, int batch, size_t off[8]
     off[2] = o; o = align256(o + nb * sizeof(unsigned));
     off[3] = o; o = align256(o + (size_t)batch * sizeof(unsigned));
     off[4] = o; o = align256(o + (size_t)batch * h->wcap * sizeof(unsigned));
-    if (h->opts) {
+    if (h->opts || h->general) {
         off[5] = o; o = align256(o + (size_t)batch * 1024 * sizeof(unsigned));
         off[6] = o; o = align256(o + (size_t)batch * (h->nint + 1) * sizeof(unsigned));
         off[7] = o; o = align256(o + (size_t)batch * sizeof(unsigned));
@@ -910,13 +1123,14 @@ int lspjpeg_encode(const lspjpeg_handle *h, const unsigned char *src_dev, int ba
 {
     if (!h || !src_dev || !dst_dev || !sizes_dev || !workspace_dev) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "null argument");
     if (batch < 1 || batch > 65535) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "batch must be in 1..65535");
-    if (reinterpret_cast<uintptr_t>(src_dev) % 16 || reinterpret_cast<uintptr_t>(workspace_dev) % 256)
+    // (the *_geom instances read bytes: a format handle of another geometry than lspjpeg_create's takes frames at any address)
+    if ((!h->general && reinterpret_cast<uintptr_t>(src_dev) % 16) || reinterpret_cast<uintptr_t>(workspace_dev) % 256)
         return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "src_dev must be 16-byte aligned and workspace_dev 256-byte aligned");
     size_t off[8];
     const size_t need = workspace_layout(h, batch, off);
     if (workspace_bytes < need) return fail(LSPJPEG_ERR_INVALID_ARGUMENT, "workspace needs " + std::to_string(need) + " bytes");
     char *ws = static_cast<char *>(workspace_dev);
-    OptParams p{};
+    GeomParams p{};
     p.src = src_dev;
     p.coef = reinterpret_cast<short *>(ws + off[0]);
     p.acbits = reinterpret_cast<unsigned *>(ws + off[1]);
@@ -937,7 +1151,7 @@ int lspjpeg_encode(const lspjpeg_handle *h, const unsigned char *src_dev, int ba
         for (int k = 0; k < 64; ++k) p.div[t][k] = h->div[t][k];
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const dim3 per_block((h->nblk + NT - 1) / NT, batch);
-    if (h->opts) {
+    if (h->opts || h->general) {
         p.codes = reinterpret_cast<unsigned *>(ws + off[5]);
         p.istart = reinterpret_cast<unsigned *>(ws + off[6]);
         p.prelen = reinterpret_cast<unsigned *>(ws + off[7]);
@@ -946,10 +1160,19 @@ int lspjpeg_encode(const lspjpeg_handle *h, const unsigned char *src_dev, int ba
         p.ibl = h->ibl;
         p.bpm = h->bpm;
         p.optimize = h->optimize;
-        hipLaunchKernelGGL(jpeg_transform<true>, per_block, dim3(NT), 0, st, p);
-        hipLaunchKernelGGL(jpeg_tables, dim3(batch), dim3(NS), 0, st, p);
-        hipLaunchKernelGGL(jpeg_emit<true>, per_block, dim3(NT), 0, st, p);
-        hipLaunchKernelGGL(jpeg_stuff<true>, dim3(batch), dim3(NS), 0, st, p);
+        const OptParams &o = p;
+        if (h->general) {                                       // (stuffing knows no geometry: the instance of a handle with options)
+            p.geo = h->geo;
+            hipLaunchKernelGGL(jpeg_transform_geom, per_block, dim3(NT), 0, st, p);
+            hipLaunchKernelGGL(jpeg_tables_geom, dim3(batch), dim3(NS), 0, st, p);
+            hipLaunchKernelGGL(jpeg_emit_geom, per_block, dim3(NT), 0, st, p);
+            hipLaunchKernelGGL(jpeg_stuff<true>, dim3(batch), dim3(NS), 0, st, o);
+        } else {
+            hipLaunchKernelGGL(jpeg_transform<true>, per_block, dim3(NT), 0, st, o);
+            hipLaunchKernelGGL(jpeg_tables, dim3(batch), dim3(NS), 0, st, o);
+            hipLaunchKernelGGL(jpeg_emit<true>, per_block, dim3(NT), 0, st, o);
+            hipLaunchKernelGGL(jpeg_stuff<true>, dim3(batch), dim3(NS), 0, st, o);
+        }
     } else {
         const Params &q = p;
         hipLaunchKernelGGL(jpeg_transform<false>, per_block, dim3(NT), 0, st, q);

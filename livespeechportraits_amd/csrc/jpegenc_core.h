@@ -21,7 +21,7 @@
 #include <stdint.h>
 
 #ifdef __HIPCC__
-#define LSPENC_HD __host__ __device__
+#define LSPENC_HD __host__ __device__ __attribute__((always_inline))    // (two kernels call each function: inlined into both, as into the one before)
 #define LSPENC_UNROLL _Pragma("unroll")
 #else
 #define LSPENC_HD
@@ -133,7 +133,7 @@ LSPENC_UNROLL
 }
 
 // codesize[257] of huff_merge -> bits[17] (bits[l] symbols of length l, bits[0] = 0) and huffval (the symbols in code order); returns their
-// number.  One caller.
+// number.  One lane per table calls it.
 LSPENC_HD inline int huff_finish(const uint16_t *codesize, unsigned char *bits, unsigned char *huffval)
 {
     uint16_t cnt[kMaxLen + 2];

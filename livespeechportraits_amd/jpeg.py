@@ -8,7 +8,8 @@ each frame's bytes.  There is no CPU path.
 
 ``JpegOptions`` carries Pillow's other two baseline switches, byte for byte Pillow's as well: ``optimize`` (per-frame optimal Huffman
 tables, about a tenth fewer bytes) and ``restart_rows`` / ``restart_blocks`` (restart intervals, which ``JpegDecoder`` decodes in
-parallel).  No default uses them.
+parallel), and ``subsampling`` (Pillow's ``subsampling=``: 4:4:4, 4:2:2 or 4:2:0, and with it frames of ANY size, padded as libjpeg pads
+them).  No default uses them.
 
 The way back is ``JpegDecoder`` (include/lspjpegdec.h): baseline files -- the candidate images of demo.py:88-95, the frames of an
 ``AviWriter`` recording, anything Pillow writes by default -- decoded on the device to the pixels Pillow returns, bit for bit.  The
@@ -41,35 +42,60 @@ class JpegOptions(NamedTuple):
     """What Pillow's ``Image.save(f, "JPEG", quality=, optimize=, restart_marker_rows=, restart_marker_blocks=)`` takes, as one value:
     accepted wherever a JPEG quality is (``render_frames(jpeg_quality=)``, ``LivePortraitPool.tick(jpeg_quality=)``, ``record_quality=``,
     ``VideoSink``).  ``optimize``: per-frame optimal Huffman tables; ``restart_rows`` MCU rows or ``restart_blocks`` MCUs per restart
-    interval (not both; 0 = none)."""
+    interval (not both; 0 = none).  ``subsampling``: None is the 4:2:0 encoder for frames whose sides are multiples of 16 (grey: 8);
+    ``"4:4:4"`` / ``"4:2:2"`` / ``"4:2:0"`` (or Pillow's 0 / 1 / 2) is Pillow's ``subsampling=`` for frames of any size.  Grey frames have no
+    chroma: any value but None selects the any-size route, and the value itself is ignored, as Pillow ignores it."""
     quality: int = 75
     optimize: bool = False
     restart_rows: int = 0
     restart_blocks: int = 0
+    subsampling: Optional[str] = None
 
     @classmethod
     def of(cls, value) -> "JpegOptions":
         """an int (a quality, today's form) or a JpegOptions -> JpegOptions with plain types; the restart keywords are checked here, the
         quality where it always was (lspjpeg_create: LspjpegError; the pools: ValueError)"""
         o = value if isinstance(value, cls) else cls(quality=value)
-        o = cls(int(o.quality), bool(o.optimize), int(o.restart_rows), int(o.restart_blocks))
+        sub = o.subsampling
+        if sub is not None:
+            if isinstance(sub, bool) or sub not in _SUBSAMPLING:
+                raise ValueError("subsampling must be None, '4:4:4', '4:2:2', '4:2:0' or Pillow's 0, 1, 2 (got %r)" % (sub, ))
+            sub = _SUBSAMPLING[sub]
+        o = cls(int(o.quality), bool(o.optimize), int(o.restart_rows), int(o.restart_blocks), sub)
         if o.restart_rows < 0 or o.restart_blocks < 0:
             raise ValueError("restart_rows and restart_blocks must be >= 0")
         if o.restart_rows and o.restart_blocks:
             raise ValueError("give restart_rows or restart_blocks, not both")
         return o
 
+    def luma_factors(self, channels: int):
+        """(h, v) sampling factors of the luma component: the MCU is 8h x 8v pixels"""
+        if channels != 3:
+            return 1, 1
+        return _FACTORS[_SUBSAMPLING[self.subsampling]] if self.subsampling is not None else (2, 2)
+
     def restart_interval(self, width: int, channels: int) -> int:
-        """MCUs per restart interval: jcmaster.c jinit_c_master_control's rows * MCUs per row capped at 65535; blocks as given"""
+        """MCUs per restart interval: jcmaster.c jinit_c_master_control's rows * MCUs per row capped at 65535 (on the grid of the chosen
+        subsampling: ceil(width / 8h) MCUs per row); blocks as given"""
         if self.restart_rows:
-            return min(self.restart_rows * (int(width) // (16 if channels == 3 else 8)), 65535)
+            m = 8 * self.luma_factors(channels)[0]
+            return min(self.restart_rows * ((int(width) + m - 1) // m if self.subsampling is not None else int(width) // m), 65535)
         return self.restart_blocks
 
 
+_FACTORS = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}
+_SUBSAMPLING = {"4:4:4": "4:4:4", "4:2:2": "4:2:2", "4:2:0": "4:2:0", 0: "4:4:4", 1: "4:2:2", 2: "4:2:0"}
+
+
 def _create(lib, width: int, height: int, channels: int, o: JpegOptions) -> ctypes.c_void_p:
-    """lspjpeg_create for plain options (the same handle, the parent's kernels), lspjpeg_create_opts otherwise"""
+    """lspjpeg_create for plain options (the same handle, the parent's kernels), lspjpeg_create_opts with optimize or restart intervals,
+    lspjpeg_create_format with a subsampling (any size; the geometry of the other two gives their handle)"""
     h = ctypes.c_void_p()
-    if not o.optimize and not o.restart_rows and not o.restart_blocks:
+    if o.subsampling is not None:
+        hs, vs = o.luma_factors(channels)
+        c = N.JpegEncFormat(N.JPEG_FORMAT_ABI_VERSION, int(width), int(height), int(channels), o.quality, int(o.optimize), o.restart_interval(width, channels), hs, vs)
+        N.check_jpeg(lib.lspjpeg_create_format(ctypes.byref(c), ctypes.byref(h)))
+    elif not o.optimize and not o.restart_rows and not o.restart_blocks:
         N.check_jpeg(lib.lspjpeg_create(int(width), int(height), int(channels), o.quality, ctypes.byref(h)))
     else:
         c = N.JpegEncOptions(N.JPEG_ABI_VERSION, int(width), int(height), int(channels), o.quality, int(o.optimize), o.restart_interval(width, channels))
@@ -78,11 +104,11 @@ def _create(lib, width: int, height: int, channels: int, o: JpegOptions) -> ctyp
 
 
 def file_header(width: int, height: int, channels: int = 3, quality: Union[int, JpegOptions] = 75, optimize: bool = False, restart_rows: int = 0,
-                restart_blocks: int = 0) -> bytes:
+                restart_blocks: int = 0, subsampling=None) -> bytes:
     """The bytes every file of that geometry and those options starts with, built on the host: no device needed.  SOI .. SOS; with
     ``optimize`` SOI .. SOF0 (the tables, DRI and SOS are then each frame's own)."""
     lib = N.load()
-    o = quality if isinstance(quality, JpegOptions) else JpegOptions(quality, optimize, restart_rows, restart_blocks)
+    o = quality if isinstance(quality, JpegOptions) else JpegOptions(quality, optimize, restart_rows, restart_blocks, subsampling)
     h = _create(lib, width, height, channels, JpegOptions.of(o))
     try:
         return _header_of(lib, h)
@@ -92,21 +118,22 @@ def file_header(width: int, height: int, channels: int = 3, quality: Union[int, 
 
 class JpegEncoder:
     """Baseline JPEG of ``[B, H, W, 3]`` uint8 RGB frames (``Engine.forward_image``; H, W multiples of 16) or ``[B, H, W]``
-    uint8 grayscale frames (``FeatureMapRasteriser.rasterise(..., as_uint8=True)``; multiples of 8), B <= ``max_batch``.
+    uint8 grayscale frames (``FeatureMapRasteriser.rasterise(..., as_uint8=True)``; multiples of 8), B <= ``max_batch``; with a
+    ``subsampling`` (``JpegOptions``) frames of any size, in 4:4:4, 4:2:2 or 4:2:0.
     ``size`` is the side of square frames or (H, W).  The device buffers (output at the documented worst-case bound per
     frame, sizes, workspace) are allocated once, here.  ``quality`` may be a ``JpegOptions``; ``optimize`` / ``restart_rows`` /
     ``restart_blocks`` are Pillow's ``optimize`` / ``restart_marker_rows`` / ``restart_marker_blocks``, and the files Pillow's with them."""
 
     def __init__(self, size: Union[int, Sequence[int]], channels: int = 3, quality: Union[int, JpegOptions] = 75, device="cuda:0", max_batch: int = 8,
-                 optimize: bool = False, restart_rows: int = 0, restart_blocks: int = 0):
+                 optimize: bool = False, restart_rows: int = 0, restart_blocks: int = 0, subsampling=None):
         self.lib = N.load()
         self.height, self.width = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
         if isinstance(quality, JpegOptions):
-            if optimize or restart_rows or restart_blocks:
+            if optimize or restart_rows or restart_blocks or subsampling is not None:
                 raise ValueError("give a JpegOptions or the keywords, not both")
             self.options = JpegOptions.of(quality)
         else:
-            self.options = JpegOptions.of(JpegOptions(quality, optimize, restart_rows, restart_blocks))
+            self.options = JpegOptions.of(JpegOptions(quality, optimize, restart_rows, restart_blocks, subsampling))
         self.channels, self.quality, self.max_batch = int(channels), self.options.quality, int(max_batch)
         if self.max_batch < 1:
             raise ValueError("max_batch must be >= 1")
@@ -148,7 +175,8 @@ class JpegEncoder:
         b = frames.shape[0]
         if not 1 <= b <= self.max_batch:
             raise ValueError("batch %d outside 1..max_batch=%d" % (b, self.max_batch))
-        if frames.data_ptr() % 16:
+        # (a format handle reads bytes unless its geometry is that of lspjpeg_create; the library then states the rule itself)
+        if self.options.subsampling is None and frames.data_ptr() % 16:
             raise ValueError("frames must start on a 16-byte boundary (a view with a storage offset does not)")
         return b
 

@@ -33,7 +33,7 @@ class LivePortraitPool:
     generator forward.  ``raster_chunk``: frames per rasteriser launch (one launch per tick unless a tick emits more: 1 MiB of map per
     frame).  A tick may bring a session at most ``max_tick_samples`` samples: what the stage's rings (its ``max_push``) can take.
 
-    ``record_quality`` (a JPEG quality or a ``jpeg.JpegOptions``) makes the pool able to record: it then keeps every session's last ``ring_samples`` samples on the
+    ``record_quality`` (a JPEG quality or a ``jpeg.JpegOptions``; with its ``subsampling`` set, an ``out_size`` that is no multiple of 16 records as well) makes the pool able to record: it then keeps every session's last ``ring_samples`` samples on the
     device, and ``open`` / ``record`` take AviWriters that ``tick`` appends the session's frames and their audio to.  ``record_route``
     "device" (one lspavi_pack_multi per group of frames) or "host" (JpegEncoder + append_jpegs per session); both write the same files.
 

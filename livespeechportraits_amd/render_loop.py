@@ -45,7 +45,7 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
     first measurements were not separated from that throttling).
     A model that cannot give a second handle (the `small` U-Net, several gpu_ids, stand-ins) gets one lane on the current stream: enqueue, wait, hand out.
 
-    ``jpeg_quality`` (1..100, Pillow's default is 75; or a ``jpeg.JpegOptions`` with Pillow's ``optimize`` / restart switches): every lane encodes its frames on its own stream right behind the generator (jpeg.JpegEncoder,
+    ``jpeg_quality`` (1..100, Pillow's default is 75; or a ``jpeg.JpegOptions`` with Pillow's ``optimize`` / restart switches and ``subsampling``, which also lifts the multiples-of-16 rule: any ``out_size`` then encodes): every lane encodes its frames on its own stream right behind the generator (jpeg.JpegEncoder,
     include/lspjpeg.h) and the frames are handed out as complete JPEG files (``bytes``, what demo.py:271's save_images writes as pred_<n>.jpg); only the
     compressed bytes cross PCIe.  There is no host encoder: a model on the host with ``jpeg_quality`` raises.
 

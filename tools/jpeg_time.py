@@ -10,7 +10,12 @@ With --options instead (default name jpeg_options_time), the encoder's options a
       the bytes per frame of each arm on the generator's own frames;
   (e) JpegDecoder.decode of 64 such files per arm (host clock, plan + upload + three stages + status): the decoder gives a wave to every
       restart interval.
-    python tools/jpeg_time.py --options [name] [output directory]"""
+    python tools/jpeg_time.py --options [name] [output directory]
+With --geometry instead (default name jpeg_geometry_time), the format handles (lspjpeg_create_format) against the plain handle, A-B-A-B:
+  (f) device time of lspjpeg_encode for 8 colour frames at q75: the plain 512^2 4:2:0 handle (the baseline: its kernels are untouched), 512^2
+      in 4:4:4 and 4:2:2, and 500 x 500 in 4:2:0 (the generator's frames cropped), and the bytes per frame of each subsampling on the
+      generator's own 512^2 frames.
+    python tools/jpeg_time.py --geometry [name] [output directory]"""
 import argparse
 import ctypes
 import io
@@ -33,9 +38,9 @@ from livespeechportraits_amd.jpeg import JpegEncoder  # noqa: E402
 from livespeechportraits_amd.render_loop import render_frames  # noqa: E402
 from livespeechportraits_amd.topology import build_topology  # noqa: E402
 
-OPTIONS = "--options" in sys.argv
-argv = [a for a in sys.argv[1:] if a != "--options"]
-name = argv[0] if len(argv) > 0 else ("jpeg_options_time" if OPTIONS else "jpeg_time")
+OPTIONS, GEOMETRY = "--options" in sys.argv, "--geometry" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--options", "--geometry")]
+name = argv[0] if len(argv) > 0 else ("jpeg_options_time" if OPTIONS else "jpeg_geometry_time" if GEOMETRY else "jpeg_time")
 out_dir = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles")
 dev = torch.device("cuda:0")
 B, S, Q = 8, 512, 75
@@ -130,6 +135,29 @@ if OPTIONS:
             rec["e"][a].append(round((time.perf_counter() - t0) / 10 * 1e3, 3))
     for a in arms:
         say("(e) JpegDecoder.decode of 64 colour files %d^2, %-14s: %s ms per call (host clock; the pixels equal the default arm's)" % (S, a, rec["e"][a]))
+    eng.close()
+    finish()
+    sys.exit(0)
+
+
+if GEOMETRY:
+    from livespeechportraits_amd.jpeg import JpegOptions
+    crop = u8[:, :500, :500].contiguous()
+    arms = {"plain 512^2 4:2:0": (JpegEncoder(S, 3, Q, dev, max_batch=B), u8),
+            "512^2 4:2:0 via subsampling=": (JpegEncoder(S, 3, JpegOptions(Q, subsampling="4:2:0"), dev, max_batch=B), u8),
+            "512^2 4:2:2": (JpegEncoder(S, 3, JpegOptions(Q, subsampling="4:2:2"), dev, max_batch=B), u8),
+            "512^2 4:4:4": (JpegEncoder(S, 3, JpegOptions(Q, subsampling="4:4:4"), dev, max_batch=B), u8),
+            "500x500 4:2:0": (JpegEncoder(500, 3, JpegOptions(Q, subsampling="4:2:0"), dev, max_batch=B), crop)}
+    rec["f"] = {a: {"us": []} for a in arms}
+    for rnd in range(2):                                   # A-B-A-B over the arms
+        for a, (enc, x) in arms.items():
+            rec["f"][a]["us"].append(round(device_us(lambda: launch(enc, x)), 2))
+    for a, (enc, x) in arms.items():
+        rec["f"][a]["bytes_per_frame"] = int(np.mean([len(f) for f in enc.encode(x)]))
+        say("(f) lspjpeg_encode, %d colour frames q%d, %-28s: %s us; mean file %d B" % (B, Q, a, rec["f"][a]["us"], rec["f"][a]["bytes_per_frame"]))
+    base = rec["f"]["plain 512^2 4:2:0"]
+    say("(f) against the plain handle: " + ", ".join("%s x%.2f time, %+.1f %% bytes" % (a, min(v["us"]) / min(base["us"]), 100.0 * (v["bytes_per_frame"] / base["bytes_per_frame"] - 1))
+                                                      for a, v in rec["f"].items() if a != "plain 512^2 4:2:0"))
     eng.close()
     finish()
     sys.exit(0)
