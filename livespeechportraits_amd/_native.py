@@ -349,11 +349,22 @@ class JpegDecSummary(ctypes.Structure):
                 ("total_blocks", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("workspace_bytes", ctypes.c_uint64), ("status_offset", ctypes.c_uint64)]
 
 
+class JpegDecScan(ctypes.Structure):
+    """lspjpeg_dec_scan"""
+    _fields_ = [("components", ctypes.c_int32), ("component", ctypes.c_uint8 * 4), ("dc_table", ctypes.c_uint8 * 4), ("ac_table", ctypes.c_uint8 * 4),
+                ("ss", ctypes.c_int32), ("se", ctypes.c_int32), ("ah", ctypes.c_int32), ("al", ctypes.c_int32), ("restart_interval", ctypes.c_int32),
+                ("units", ctypes.c_int32), ("segments", ctypes.c_int32), ("reserved", ctypes.c_int32), ("begin", ctypes.c_uint64), ("end", ctypes.c_uint64)]
+
+
 # every symbol include/lspjpegdec.h declares
 JPEGDEC_SIGNATURES = {
     "lspjpeg_dec_last_error": (c_char_p, []),
     "lspjpeg_dec_probe": (c_int, [c_void_p, c_size_t, POINTER(JpegDecInfo)]),
     "lspjpeg_dec_plan": (c_int64, [POINTER(c_void_p), POINTER(c_size_t), POINTER(JpegDecOutput), c_int, c_int, c_void_p, c_size_t]),
+    "lspjpeg_dec_probe_flags": (c_int, [c_void_p, c_size_t, ctypes.c_uint, POINTER(JpegDecInfo)]),
+    "lspjpeg_dec_plan_flags": (c_int64, [POINTER(c_void_p), POINTER(c_size_t), POINTER(JpegDecOutput), c_int, c_int, ctypes.c_uint, c_void_p, c_size_t]),
+    "lspjpeg_dec_plan_scans": (c_int, [c_void_p, c_int]),
+    "lspjpeg_dec_plan_scan": (c_int, [c_void_p, c_int, c_int, POINTER(JpegDecScan)]),
     "lspjpeg_dec_summary_of": (c_int, [c_void_p, POINTER(JpegDecSummary)]),
     "lspjpeg_dec_plan_file": (c_int, [c_void_p, c_int, POINTER(JpegDecInfo)]),
     "lspjpeg_dec_plan_qtable": (c_int, [c_void_p, c_int, c_int, c_void_p]),

@@ -35,14 +35,18 @@ def candidate_paths(data_root: str) -> list:
     return [os.path.join(data_root, "candidates", "normalized_full_%d.jpg" % j) for j in range(CANDIDATES)]
 
 
-def load_candidates(paths_or_data_root: Union[str, Sequence], device="cuda:0", size: int = 512, decoder=None, resize=None, resizer=None) -> torch.Tensor:
+def load_candidates(paths_or_data_root: Union[str, Sequence], device="cuda:0", size: int = 512, decoder=None, resize=None, resizer=None,
+                    progressive: bool = False) -> torch.Tensor:
     """float32 ``[1, 12, size, size]`` on ``device`` from four JPEG files: a data root (``<root>/candidates/normalized_full_{0..3}.jpg``), four
     paths, or four ``bytes`` objects.  Files that are not 3-component ``size`` x ``size`` are refused (ValueError); files the decoder
     cannot take raise jpeg.JpegError.
 
     ``resize`` ("box", "bilinear", "hamming", "bicubic" or "lanczos"; None: off): the files may have any geometry the decoder takes, each its
     own; a file that is not ``size`` x ``size`` is resampled to it as ``Image.resize((size, size), filter)`` does, one that is takes the path
-    above.  ``resizer``: a resize.Resizer to reuse."""
+    above.  ``resizer``: a resize.Resizer to reuse.
+
+    ``progressive``: complete progressive files (SOF2, what photo tools and the web mostly export) are taken as well, to the pixels Pillow
+    returns for them; handed on to the decoder this call creates (a ``decoder`` passed in decides for itself)."""
     from .jpeg import JpegDecoder, probe
     if resize is not None:
         from .resize import Resizer, check_filter
@@ -59,13 +63,13 @@ def load_candidates(paths_or_data_root: Union[str, Sequence], device="cuda:0", s
                 files.append(f.read())
     other = []                                                  # the files to resample
     for j, data in enumerate(files):
-        i = probe(data)
+        i = probe(data, progressive if decoder is None else getattr(decoder, "progressive", False))
         if i.status == 0 and (i.width, i.height, i.components) != (size, size, 3):
             if resize is None or i.components != 3:
                 raise ValueError("candidate %d is %dx%d with %d components, the generator takes %dx%d RGB" % (j, i.width, i.height, i.components, size, size))
             other.append((j, max(i.width, i.height)))
     device = torch.device(device)
-    decoder = decoder or JpegDecoder(device, max_side=max([size] + [side for _, side in other]), max_batch=CANDIDATES)
+    decoder = decoder or JpegDecoder(device, max_side=max([size] + [side for _, side in other]), max_batch=CANDIDATES, progressive=progressive)
     out = torch.empty((3 * CANDIDATES, size, size), dtype=torch.float32, device=device)
     table = torch.from_numpy(normalisation_table()).to(device)
     if not other:

@@ -1,5 +1,5 @@
-// jpegdec.hip -- the baseline JPEG decoder of include/lspjpegdec.h: three stages on the device (entropy decode, dequantise + IDCT, upsample +
-// colour + store) behind a host planner.  The arithmetic is libjpeg's integer arithmetic step by step (jdhuff.c, jidctint.c, jdsample.c,
+// jpegdec.hip -- the JPEG decoder of include/lspjpegdec.h: three stages on the device (entropy decode, dequantise + IDCT, upsample +
+// colour + store) behind a host planner; stage 1 has a second kernel for complete progressive files (LSPJPEG_DEC_FLAG_PROGRESSIVE).  The arithmetic is libjpeg's integer arithmetic step by step (jdhuff.c, jidctint.c, jdsample.c,
 // jdcolor.c): for a file Pillow can open the output equals Pillow's pixels.  The parser and the segment decoder live in jpegdec_core.h, which is
 // also built for the host alone and run under sanitizers (make check-jpegdec).
 #include <hip/hip_runtime.h>
@@ -31,6 +31,9 @@ struct Params {
     unsigned char *planes;
     unsigned nfiles, nsegs;
     unsigned long long bytes;               // of the block: no load reaches past it
+    const ScanDesc *scans;                  // progressive files: their scans, those scans' restart intervals and table snapshots
+    const SegDesc *psegs;
+    const HuffTable *ptables;
 };
 
 constexpr int kWave = 64;
@@ -94,6 +97,120 @@ __global__ __launch_bounds__(kWave) void jpegdec_entropy(Params p)
         }
     }
     if (st != ST_OK && lane == 0) atomicCAS(p.status + sg.file, 0u, st);
+}
+
+// ---- stage 1 of the progressive files: one wave per file, every scan of the file in file order over the same coefficients (a refinement reads
+// what the earlier scans left, so a file is one serial walk; files run beside each other).  The wave zeroes the file's coefficients, then for each
+// restart interval of each scan stages the stream through the LDS window as above and moves kStage blocks at a time between the workspace and LDS,
+// 16 bytes per lane, turning each block into zigzag order on the way in and back on the way out, so that lane 0, which runs the four procedures
+// (prog_units) on the staged blocks, indexes LDS by the band position and looks nothing up.  A scan of one component walks
+// that component's own raster, so each staged block's place comes from prog_block_index().  Reads are bounded by the interval's end (BitReader) and
+// the block's end (the refill); writes by the file's block count.  Every store of a block is separated from the next load of it by a barrier of the
+// (single-wave) workgroup, which also orders the zeroing before the first scan's loads.
+constexpr unsigned kStage = 64;             // blocks per barrier pair: 8 KiB of LDS
+constexpr unsigned kProgRing = 32768;       // the stream window: one stage's worst case behind a refill
+static_assert(kProgRing >= kStage * kBlockBytesBound + 2 * kWave * 16 && (kProgRing & (kProgRing - 1)) == 0, "the window holds one stage's worst case behind a refill");
+static_assert(kStage >= kMaxBlocksPerMcu && kStage * 8 % kWave == 0, "a stage holds at least one MCU, and the lanes move it in whole rounds");
+
+struct ProgRingSrc {
+    const unsigned char *ring;
+    __device__ uint8_t at(uint64_t pos) const { return ring[pos & (kProgRing - 1)]; }
+};
+
+__global__ __launch_bounds__(kWave) void jpegdec_progressive(Params p)
+{
+    __shared__ uint4 s_tab[4 * sizeof(HuffTable) / 16];
+    __shared__ uint4 s_ring[kProgRing / 16];
+    __shared__ short s_blk[kStage * 64];                                       // zigzag order inside a block
+    __shared__ unsigned long long s_pos;
+    __shared__ unsigned s_st;
+    const unsigned fi = blockIdx.x;
+    if (fi >= p.nfiles) return;
+    const FileDesc &gf = p.files[fi];
+    if (!gf.progressive || gf.status != ST_OK) return;
+    FileDesc f{};                                                              // the geometry in registers: the stores below may alias nothing of it
+    f.ncomp = gf.ncomp;
+    f.hs = gf.hs;
+    f.vs = gf.vs;
+    f.mcux = gf.mcux;
+    f.bpm = gf.bpm;
+    f.nblk = gf.nblk;
+    f.scan0 = gf.scan0;
+    f.nscan = gf.nscan;
+    const int lane = threadIdx.x;
+    uint4 *coef = reinterpret_cast<uint4 *>(p.coef + gf.coef_off * 64);
+    const unsigned nblk = f.nblk;
+    for (unsigned k = lane; k < nblk * 8; k += kWave) coef[k] = make_uint4(0, 0, 0, 0);
+    uint8_t comp_of[kMaxBlocksPerMcu];
+    int bpm;
+    block_components(f.ncomp, f.hs, f.vs, comp_of, &bpm);
+    const ProgRingSrc src{reinterpret_cast<const unsigned char *>(s_ring)};
+    int zz[8];                                                                 // a lane always moves the same eighth of a block: where its coefficients stand in LDS
+#pragma unroll
+    for (int i = 0; i < 8; ++i) zz[i] = natural_to_zigzag((lane & 7) * 8 + i);
+    unsigned st = ST_OK;
+    for (unsigned s = 0; s < f.nscan && st == ST_OK; ++s) {
+        const ScanDesc sc = p.scans[f.scan0 + s];
+        __syncthreads();                                                       // lane 0 is done with the last scan's tables; the zeroing has landed
+        const unsigned ntab = sc.ntab < 4 ? sc.ntab : 4;
+        const uint4 *tab = reinterpret_cast<const uint4 *>(p.ptables + sc.table0);
+        for (unsigned k = lane; k < ntab * (sizeof(HuffTable) / 16); k += kWave) s_tab[k] = tab[k];
+        const unsigned bpu = sc.ncomp > 1 ? (unsigned)bpm : 1u, per_stage = kStage / bpu;
+        unsigned long long filled = sc.begin & ~15ull;
+        ScanState state{};
+        for (unsigned g = 0; g < sc.nseg && st == ST_OK; ++g) {
+            const SegDesc sg = p.psegs[sc.seg0 + g];
+            BitReader<ProgRingSrc> br(src, sg.begin, sg.end);
+            state = ScanState{};
+            unsigned long long pos = sg.begin;
+            for (unsigned u0 = 0; u0 < sg.nmcu; u0 += per_stage) {
+                const unsigned nu = sg.nmcu - u0 < per_stage ? sg.nmcu - u0 : per_stage, nb = nu * bpu;
+                unsigned long long want = pos + (unsigned long long)nb * kBlockBytesBound;
+                if (want > sg.end) want = sg.end;
+                while (filled < want) {
+                    const unsigned long long off = filled + (unsigned long long)lane * 16;
+                    if (off + 16 <= p.bytes) s_ring[(off >> 4) & (kProgRing / 16 - 1)] = *reinterpret_cast<const uint4 *>(p.blob + off);
+                    filled += kWave * 16;
+                }
+                const unsigned first = (sg.mcu0 + u0) * bpu;
+                for (unsigned k = lane; k < nb * 8; k += kWave) {
+                    const unsigned at = prog_block_index(f, sc, first + (k >> 3));
+                    if (at < nblk) {
+                        const uint4 v = coef[(size_t)at * 8 + (k & 7)];
+                        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+                        short *blk = s_blk + (k >> 3) * 64;
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) blk[zz[i]] = (short)(w[i >> 1] >> (16 * (i & 1)));
+                    }
+                }
+                __syncthreads();
+                if (lane == 0) {
+                    unsigned r = prog_units<ZigzagOrder>(br, sc, reinterpret_cast<const HuffTable *>(s_tab), comp_of, (int)bpu, state, s_blk, nu);
+                    if (r == ST_OK && u0 + nu == sg.nmcu) {
+                        if (!br.drained()) r = ST_CORRUPT;
+                        else if (g + 1 == sc.nseg && state.eobrun) r = ST_CORRUPT;     // a run that reaches past the scan's last block
+                    }
+                    s_st = r;
+                    s_pos = br.pos;
+                }
+                __syncthreads();
+                st = s_st;
+                pos = s_pos;
+                if (st != ST_OK) break;
+                for (unsigned k = lane; k < nb * 8; k += kWave) {
+                    const unsigned at = prog_block_index(f, sc, first + (k >> 3));
+                    if (at < nblk) {
+                        const short *blk = s_blk + (k >> 3) * 64;
+                        unsigned w[4];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) w[i] = (unsigned)(unsigned short)blk[zz[2 * i]] | ((unsigned)(unsigned short)blk[zz[2 * i + 1]] << 16);
+                        coef[(size_t)at * 8 + (k & 7)] = make_uint4(w[0], w[1], w[2], w[3]);
+                    }
+                }
+            }
+        }
+    }
+    if (st != ST_OK && lane == 0) atomicCAS(p.status + fi, 0u, st);
 }
 
 // ---- stage 2: jidctint.c jpeg_idct_islow on one block per thread.
@@ -304,31 +421,63 @@ void fill_info(const Parsed &f, uint32_t status, uint32_t nseg, uint64_t scan_en
     info->scan_bytes = scan_end - f.scan_begin;
 }
 
+void fill_info_progressive(const ProgFile &f, uint32_t status, lspjpeg_dec_info *info)
+{
+    *info = lspjpeg_dec_info{};
+    info->status = (int32_t)status;
+    info->width = (int32_t)f.width;
+    info->height = (int32_t)f.height;
+    info->components = (int32_t)f.ncomp;
+    info->hsamp = (int32_t)f.hs;
+    info->vsamp = (int32_t)f.vs;
+    info->restart_interval = (int32_t)f.restart0;
+    if (status != ST_OK) return;
+    info->mcus = (int32_t)(((f.width + 8 * f.hs - 1) / (8 * f.hs)) * ((f.height + 8 * f.vs - 1) / (8 * f.vs)));
+    info->segments = (int32_t)f.nseg;
+    info->scan_offset = f.data_begin;
+    info->scan_bytes = f.data_end - f.data_begin;
+}
+
 }  // namespace
 
 extern "C" {
 
 const char *lspjpeg_dec_last_error(void) { return g_err.c_str(); }
 
-int lspjpeg_dec_probe(const unsigned char *bytes, size_t len, lspjpeg_dec_info *info)
+int lspjpeg_dec_probe(const unsigned char *bytes, size_t len, lspjpeg_dec_info *info) { return lspjpeg_dec_probe_flags(bytes, len, 0u, info); }
+
+int lspjpeg_dec_probe_flags(const unsigned char *bytes, size_t len, unsigned flags, lspjpeg_dec_info *info)
 {
     if (!bytes || !info) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "null argument");
+    if (flags & ~LSPJPEG_DEC_FLAG_PROGRESSIVE) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "unknown flag");
     Parsed f;
+    ProgFile pf;
     uint32_t nseg;
     uint64_t end;
-    const uint32_t st = examine(bytes, len, LSPJPEG_MAX_SIDE, &f, &nseg, &end);
-    fill_info(f, st, nseg, end, info);
+    bool prog;
+    const uint32_t st = examine_flags(bytes, len, LSPJPEG_MAX_SIDE, flags, &f, &nseg, &end, &pf, &prog);
+    if (prog)
+        fill_info_progressive(pf, st, info);
+    else
+        fill_info(f, st, nseg, end, info);
     return LSPJPEG_DEC_OK;
 }
 
 int64_t lspjpeg_dec_plan(const unsigned char *const *files, const size_t *lens, const lspjpeg_dec_output *outs, int n, int max_side, void *blob,
                          size_t cap)
 {
+    return lspjpeg_dec_plan_flags(files, lens, outs, n, max_side, 0u, blob, cap);
+}
+
+int64_t lspjpeg_dec_plan_flags(const unsigned char *const *files, const size_t *lens, const lspjpeg_dec_output *outs, int n, int max_side, unsigned flags,
+                               void *blob, size_t cap)
+{
+    if (flags & ~LSPJPEG_DEC_FLAG_PROGRESSIVE) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "unknown flag");
     if (!files || !lens || n < 1 || n > 65535) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "files, lens and 1..65535 files are required");
     if (max_side < 1 || max_side > LSPJPEG_MAX_SIDE) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "max_side must be in 1.." + std::to_string(LSPJPEG_MAX_SIDE));
     for (int i = 0; i < n; ++i)
         if (!files[i]) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "file " + std::to_string(i) + " is null");
-    const int64_t need = plan(files, lens, nullptr, n, (uint32_t)max_side, nullptr);
+    const int64_t need = plan(files, lens, nullptr, n, (uint32_t)max_side, nullptr, flags);
     if (need < 0) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "the batch needs a descriptor block of 4 GiB or more: split it");
     if (!blob) return need;
     if (cap < (size_t)need || reinterpret_cast<uintptr_t>(blob) % 16)
@@ -342,7 +491,7 @@ int64_t lspjpeg_dec_plan(const unsigned char *const *files, const size_t *lens, 
         od[i].plane_stride = outs[i].plane_stride;
         od[i].form = (uint32_t)outs[i].form;
     }
-    const int64_t got = plan(files, lens, od, n, (uint32_t)max_side, blob);
+    const int64_t got = plan(files, lens, od, n, (uint32_t)max_side, blob, flags);
     if (got == -1) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "an output's form does not fit its file (RGB8: 3 components, GRAY8: 1, PLANAR_F32: a table and plane_stride >= H * W)");
     return got;
 }
@@ -377,10 +526,51 @@ int lspjpeg_dec_plan_file(const void *blob, int i, lspjpeg_dec_info *info)
     info->vsamp = (int32_t)d.vs;
     info->restart_interval = (int32_t)d.restart;
     info->mcus = (int32_t)(d.mcux * d.mcuy);
+    if (d.progressive) {                                                       // every restart interval of every scan; the data from the first scan's up to the EOI
+        const ScanDesc *sc = scans_of(blob) + d.scan0;
+        for (uint32_t k = 0; k < d.nscan; ++k) info->segments += (int32_t)sc[k].nseg;
+        info->scan_offset = sc[0].begin;
+        info->scan_bytes = sc[d.nscan - 1].end - sc[0].begin;
+        return LSPJPEG_DEC_OK;
+    }
     info->segments = (int32_t)d.nseg;
     const SegDesc *s = segs_of(blob) + d.seg0;
     info->scan_offset = s[0].begin;
     info->scan_bytes = s[d.nseg - 1].end - s[0].begin;
+    return LSPJPEG_DEC_OK;
+}
+
+int lspjpeg_dec_plan_scans(const void *blob, int i)
+{
+    const BlobHeader *h = header_of(blob);
+    if (!h || i < 0 || (uint32_t)i >= h->nfiles) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "no such file in the block");
+    const FileDesc &d = files_of(blob)[i];
+    return d.status == ST_OK && d.progressive ? (int)d.nscan : 0;
+}
+
+int lspjpeg_dec_plan_scan(const void *blob, int i, int s, lspjpeg_dec_scan *out)
+{
+    const BlobHeader *h = header_of(blob);
+    if (!h || !out || i < 0 || (uint32_t)i >= h->nfiles) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "no such file in the block");
+    const FileDesc &d = files_of(blob)[i];
+    if (d.status != ST_OK || !d.progressive || s < 0 || (uint32_t)s >= d.nscan) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "no such scan of the file");
+    const ScanDesc &sc = scans_of(blob)[d.scan0 + s];
+    *out = lspjpeg_dec_scan{};
+    out->components = sc.ncomp;
+    for (int j = 0; j < 4; ++j) {
+        out->component[j] = sc.comp[j];
+        out->dc_table[j] = sc.td[j];
+        out->ac_table[j] = sc.ta[j];
+    }
+    out->ss = sc.ss;
+    out->se = sc.se;
+    out->ah = sc.ah;
+    out->al = sc.al;
+    out->restart_interval = (int32_t)sc.restart;
+    out->units = (int32_t)sc.units;
+    out->segments = (int32_t)sc.nseg;
+    out->begin = sc.begin;
+    out->end = sc.end;
     return LSPJPEG_DEC_OK;
 }
 
@@ -434,9 +624,13 @@ int lspjpeg_dec_decode(const void *blob_host, void *blob_dev, void *workspace_de
     p.nfiles = h->nfiles;
     p.nsegs = h->nsegs;
     p.bytes = h->bytes;
+    p.scans = reinterpret_cast<const ScanDesc *>(b + h->scans_off);
+    p.psegs = reinterpret_cast<const SegDesc *>(b + h->psegs_off);
+    p.ptables = reinterpret_cast<const HuffTable *>(b + h->ptables_off);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const auto grid = [](unsigned items, unsigned per) { return items ? (items + per - 1) / per : 1u; };     // a batch of refused files still launches
     hipLaunchKernelGGL(jpegdec_entropy, dim3(grid(h->nsegs, 1)), dim3(kWave), 0, st, p);
+    if (h->nprog) hipLaunchKernelGGL(jpegdec_progressive, dim3(h->nfiles), dim3(kWave), 0, st, p);     // the files of the two kinds are disjoint
     hipLaunchKernelGGL(jpegdec_idct, dim3(grid(h->max_blocks, kIdctThreads), h->nfiles), dim3(kIdctThreads), 0, st, p);
     hipLaunchKernelGGL(jpegdec_store, dim3(grid(h->max_pixels, kStoreThreads), h->nfiles), dim3(kStoreThreads), 0, st, p);
     const hipError_t e = hipGetLastError();

@@ -4,7 +4,9 @@
 //   jpegdec_check <bundle> <seed> <truncated files> <corruptions per file>
 //
 // The bundle (written by tests/test_jpeg_decode_cpu.py) is "LSDB", a uint32 count, then per file: uint32 length, uint32 expected status,
-// uint32 count of expected int16 coefficients, the file's bytes, the coefficients (MCU order, natural order inside a block).  The program
+// uint32 count of expected int16 coefficients, the file's bytes, the coefficients (MCU order, natural order inside a block).  A bundle that
+// starts with "LSDP" instead (tests/test_jpeg_progressive_cpu.py) has the same layout and is planned with kFlagProgressive throughout: its entries
+// are progressive files, baseline files beside them, and the refusals of that flag.  The program
 //   1. plans and decodes every file alone and all of them as one batch: status and coefficients must be the expected ones;
 //   2. does the same for every truncation length of the first <truncated files> files;
 //   3. and for <corruptions per file> single-byte changes of every file, positions and values from a 64-bit LCG started at <seed>.
@@ -33,6 +35,8 @@ struct Result {
 };
 
 // plan + stage 1 of a batch; every file lives in its own exact-size allocation
+uint32_t g_flags = 0;                                   // of the bundle: every plan of the run is made with them
+
 std::vector<Result> run(const std::vector<const std::vector<uint8_t> *> &batch)
 {
     std::vector<uint8_t *> copies;
@@ -46,14 +50,14 @@ std::vector<Result> run(const std::vector<const std::vector<uint8_t> *> &batch)
         lens.push_back(f->size());
     }
     const int n = (int)batch.size();
-    const int64_t need = plan(ptrs.data(), lens.data(), nullptr, n, 8192, nullptr);
+    const int64_t need = plan(ptrs.data(), lens.data(), nullptr, n, 8192, nullptr, g_flags);
     std::vector<Result> out(n);
     if (need < 0) {
         std::fprintf(stderr, "plan refused the batch (%lld)\n", (long long)need);
         std::exit(2);
     }
     void *blob = std::aligned_alloc(16, (size_t)need);
-    if (plan(ptrs.data(), lens.data(), nullptr, n, 8192, blob) != need) {
+    if (plan(ptrs.data(), lens.data(), nullptr, n, 8192, blob, g_flags) != need) {
         std::fprintf(stderr, "plan wrote another size than it announced\n");
         std::exit(2);
     }
@@ -96,10 +100,11 @@ int main(int argc, char **argv)
     uint64_t lcg = std::strtoull(argv[2], nullptr, 10);
     const size_t ntrunc = std::strtoul(argv[3], nullptr, 10), ncorrupt = std::strtoul(argv[4], nullptr, 10);
     char magic[4];
-    if (std::fread(magic, 1, 4, f) != 4 || std::memcmp(magic, "LSDB", 4)) {
+    if (std::fread(magic, 1, 4, f) != 4 || (std::memcmp(magic, "LSDB", 4) && std::memcmp(magic, "LSDP", 4))) {
         std::fprintf(stderr, "not a bundle\n");
         return 2;
     }
+    g_flags = std::memcmp(magic, "LSDP", 4) ? 0u : kFlagProgressive;
     std::vector<Entry> entries(read32(f));
     for (Entry &e : entries) {
         const uint32_t len = read32(f);

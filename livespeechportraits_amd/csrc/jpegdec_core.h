@@ -5,6 +5,10 @@
 //
 // What is decoded (jdhuff.c decode_mcu, jdmarker.c): SOF0, 8 bit, one interleaved scan, 1 component or YCbCr with luma 1x1 / 2x1 / 2x2, DRI,
 // the file's DHT tables or Annex K's where a table is absent.  Everything else is refused with a status, never decoded differently.
+//
+// Under kFlagProgressive also SOF2 (jdphuff.c): walk_progressive() is the parser and scan walker of such a file (every scan, the tables and the
+// restart interval in force at each, libjpeg's coef_bits bookkeeping), prog_units() the four procedures of ITU T.81 Annex G.  A progressive file
+// is decoded only when it is complete (every coefficient of every component refined down to bit 0): its coefficients are then a baseline file's.
 #ifndef LSPJPEGDEC_CORE_H
 #define LSPJPEGDEC_CORE_H
 
@@ -54,7 +58,8 @@ struct FileDesc {
     uint64_t table_ptr;        // device pointer of 256 floats (form 2)
     int64_t plane_stride;      // elements between the channels of a planar output (form 2)
     uint32_t form;             // 0: uint8 [H][W][3], 1: uint8 [H][W], 2: float32 planar through the table
-    uint32_t pad;
+    uint32_t progressive;      // 1: no segments of its own (nseg 0); stage 1 walks its scans instead
+    uint32_t scan0, nscan;     // its entries of the scan list
 };
 static_assert(sizeof(FileDesc) % 8 == 0, "FileDesc is part of the descriptor block's layout");
 
@@ -65,6 +70,26 @@ struct SegDesc {
     uint32_t pad;
     uint64_t begin, end;
 };
+
+// ---- progressive files (kFlagProgressive)
+constexpr uint32_t kFlagProgressive = 1u;           // include/lspjpegdec.h LSPJPEG_DEC_FLAG_PROGRESSIVE
+constexpr uint32_t kMaxScans = 64;                   // include/lspjpegdec.h LSPJPEG_DEC_MAX_SCANS: a file with more is ST_UNSUPPORTED
+constexpr uint32_t kBlockBytesBound = 448;           // >= 2 * ceil((64 * 26 + 30) / 8) + 8: no block of any scan codes more bytes than this (stuffed, reader's look-ahead included)
+
+// one scan of a progressive file.  Its restart intervals are entries seg0 .. seg0 + nseg - 1 of the progressive segment list (SegDesc with mcu0 / nmcu
+// counting the scan's own units: interleaved MCUs when the scan holds every component, blocks of the component's own extent when it holds one)
+struct ScanDesc {
+    uint32_t file;
+    uint32_t units;            // MCUs, or bw * bh blocks
+    uint32_t restart;          // the interval in force (DRI may change between scans), in units; 0 = none
+    uint32_t bw, bh;           // one component: blocks per row and rows of ITS extent, ceil(Wc / 8) x ceil(Hc / 8); all components: mcux, mcuy
+    uint32_t table0, ntab;     // its decode tables in the progressive table area: one per component of a first DC scan, one of an AC scan, none of a DC refinement
+    uint32_t seg0, nseg;
+    uint8_t ncomp, ss, se, ah, al, pad[3];
+    uint8_t comp[4], td[4], ta[4];   // component indices (frame order) and the table ids the SOS names
+    uint64_t begin, end;       // offsets into the descriptor block: the first entropy-coded byte, the marker that ends the scan
+};
+static_assert(sizeof(ScanDesc) == 72, "ScanDesc is part of the descriptor block's layout");
 
 // ---- what the marker parser extracts, fixed size (no allocation)
 struct Parsed {
@@ -85,6 +110,14 @@ LSPDEC_HD inline int zigzag_to_natural(int k)
     constexpr uint8_t t[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
                                35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
     return t[k];
+}
+
+// the inverse: where natural index n stands in the zigzag sequence
+LSPDEC_HD inline int natural_to_zigzag(int n)
+{
+    constexpr uint8_t t[64] = {0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53,
+                               10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+    return t[n];
 }
 
 LSPDEC_HD inline uint32_t be16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
@@ -387,6 +420,17 @@ struct BitReader {
         const int v = (int)((buf >> left) & ((1u << s) - 1u));
         return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
     }
+    // s plain bits (an EOBn run's appended bits, a correction bit); s in 1..16
+    LSPDEC_HD uint32_t bits(int s)
+    {
+        if (left < s) fill();
+        if (left < s) {
+            status = ST_CORRUPT;
+            return 0;
+        }
+        left -= s;
+        return (uint32_t)((buf >> left) & ((1u << s) - 1u));
+    }
     // after the last MCU: what is left is the padding of the last byte, nothing more
     LSPDEC_HD bool drained() const { return pos >= end && left < 8; }
 };
@@ -442,6 +486,431 @@ LSPDEC_HD inline void block_components(uint32_t ncomp, uint32_t hs, uint32_t vs,
     }
     for (int k = n; k < kMaxBlocksPerMcu; ++k) comp_of[k] = 0;
     *bpm = n;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// Progressive files (SOF2), jdphuff.c.  The four procedures of Annex G work on one block that already holds what the earlier scans left
+// (natural order), so the caller moves blocks in and out; prog_units() runs `n` units of one restart interval over contiguous blocks.
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+struct ScanState {
+    int pred[4];               // DC prediction per component, unshifted (jdphuff.c last_dc_val)
+    uint32_t eobrun;           // blocks still covered by the end-of-band run in force
+};
+
+LSPDEC_HD inline bool fits_int16(int v) { return v >= -32768 && v <= 32767; }
+
+// where coefficient k (zigzag index) of a block lives: natural order in memory; the kernel stages its blocks in zigzag order, so that the one lane
+// that walks the codes indexes LDS by k and looks nothing up
+struct NaturalOrder {
+    LSPDEC_HD static int at(int k) { return zigzag_to_natural(k); }
+};
+struct ZigzagOrder {
+    LSPDEC_HD static int at(int k) { return k; }
+};
+
+// G.1.2.1 first DC scan: the difference is coded as in a sequential file, the value is stored shifted by Al
+template <class Src>
+LSPDEC_HD inline uint32_t dc_first(BitReader<Src> &br, const HuffTable &dc, int al, int *pred, int16_t *blk)
+{
+    const int s = br.symbol(dc);
+    if (s < 0) return br.status;
+    if (s > 11) return ST_CORRUPT;
+    const int diff = s ? br.receive_extend(s) : 0;
+    if (br.status) return br.status;
+    *pred += diff;
+    if (!fits_int16(*pred)) return ST_RANGE;
+    const int v = *pred * (1 << al);
+    if (!fits_int16(v)) return ST_RANGE;
+    blk[0] = (int16_t)v;
+    return ST_OK;
+}
+
+// G.1.2.1 DC refinement: one bit per block
+template <class Src>
+LSPDEC_HD inline uint32_t dc_refine(BitReader<Src> &br, int al, int16_t *blk)
+{
+    const uint32_t b = br.bits(1);
+    if (br.status) return br.status;
+    if (b) blk[0] = (int16_t)(blk[0] | (1 << al));
+    return ST_OK;
+}
+
+// an EOBn symbol (run r < 15, size 0): 2^r blocks plus r appended bits, this block included
+template <class Src>
+LSPDEC_HD inline uint32_t eob_run(BitReader<Src> &br, int r, uint32_t *eobrun)
+{
+    *eobrun = 1u << r;
+    if (r) {
+        *eobrun += br.bits(r);
+        if (br.status) return br.status;
+    }
+    return ST_OK;
+}
+
+// G.1.2.2 first AC scan of the band ss..se
+template <class Order, class Src>
+LSPDEC_HD inline uint32_t ac_first(BitReader<Src> &br, const HuffTable &ac, int ss, int se, int al, uint32_t *eobrun, int16_t *blk)
+{
+    if (*eobrun) {
+        --*eobrun;
+        return ST_OK;
+    }
+    for (int k = ss; k <= se; ++k) {
+        const int rs = br.symbol(ac);
+        if (rs < 0) return br.status;
+        const int r = rs >> 4, s = rs & 15;
+        if (s == 0) {
+            if (r != 15) {
+                const uint32_t st = eob_run(br, r, eobrun);
+                if (st) return st;
+                --*eobrun;
+                return ST_OK;
+            }
+            k += 15;                                                       // ZRL: sixteen zeros with the loop's own step
+            if (k > se) return ST_CORRUPT;
+            continue;
+        }
+        if (s > 10) return ST_CORRUPT;
+        k += r;
+        if (k > se) return ST_CORRUPT;                                     // a coefficient index past Se
+        const int v = br.receive_extend(s) * (1 << al);
+        if (br.status) return br.status;
+        if (!fits_int16(v)) return ST_RANGE;
+        blk[Order::at(k)] = (int16_t)v;
+    }
+    return ST_OK;
+}
+
+// one correction bit for a coefficient with history (jdphuff.c decode_mcu_AC_refine): the magnitude grows by 1 << al when that bit is not set yet
+template <class Src>
+LSPDEC_HD inline uint32_t ac_correct(BitReader<Src> &br, int al, int16_t *c)
+{
+    const uint32_t b = br.bits(1);
+    if (br.status) return br.status;
+    if (b && ((int)*c & (1 << al)) == 0) {
+        const int v = *c >= 0 ? *c + (1 << al) : *c - (1 << al);
+        if (!fits_int16(v)) return ST_RANGE;
+        *c = (int16_t)v;
+    }
+    return ST_OK;
+}
+
+// G.1.2.3 AC refinement of the band ss..se
+template <class Order, class Src>
+LSPDEC_HD inline uint32_t ac_refine(BitReader<Src> &br, const HuffTable &ac, int ss, int se, int al, uint32_t *eobrun, int16_t *blk)
+{
+    int k = ss;
+    if (*eobrun == 0) {
+        for (; k <= se; ++k) {
+            const int rs = br.symbol(ac);
+            if (rs < 0) return br.status;
+            int r = rs >> 4, s = rs & 15;
+            if (s) {
+                if (s != 1) return ST_CORRUPT;
+                s = br.bits(1) ? (1 << al) : -(1 << al);                   // the new coefficient's value; its place comes after r zeros
+                if (br.status) return br.status;
+            } else if (r != 15) {
+                const uint32_t st = eob_run(br, r, eobrun);
+                if (st) return st;
+                break;                                                     // the rest of the band is handled below, as part of the run
+            }
+            // pass r coefficients without history (ZRL: r = 15 and the one the loop steps over), correcting the ones with history on the way
+            for (; k <= se; ++k) {
+                int16_t *c = blk + Order::at(k);
+                if (*c) {
+                    const uint32_t st = ac_correct(br, al, c);
+                    if (st) return st;
+                } else if (--r < 0) {
+                    break;
+                }
+            }
+            if (k > se) return ST_CORRUPT;                                 // the band ends before the coefficient's (or the sixteenth zero's) place
+            if (s) blk[Order::at(k)] = (int16_t)s;
+        }
+    }
+    if (*eobrun) {
+        for (; k <= se; ++k) {
+            int16_t *c = blk + Order::at(k);
+            if (*c) {
+                const uint32_t st = ac_correct(br, al, c);
+                if (st) return st;
+            }
+        }
+        --*eobrun;
+    }
+    return ST_OK;
+}
+
+// n units of a restart interval of scan sc: `blocks` holds n * bpu blocks in the scan's own order (bpu = the MCU's blocks, or 1), comp_of as for
+// decode_mcu, tabs the scan's tables, Order how a block is laid out.  The caller checks br.drained() after an interval's last unit and
+// st.eobrun == 0 after the scan's.
+template <class Order, class Src>
+LSPDEC_HD inline uint32_t prog_units(BitReader<Src> &br, const ScanDesc &sc, const HuffTable *tabs, const uint8_t *comp_of, int bpu, ScanState &st, int16_t *blocks,
+                                     uint32_t n)
+{
+    for (uint32_t u = 0; u < n; ++u)
+        for (int b = 0; b < bpu; ++b) {
+            int16_t *blk = blocks + ((size_t)u * bpu + b) * 64;
+            const int c = sc.ncomp == 1 ? 0 : comp_of[b];                  // a scan of all components names them in frame order (walk_progressive)
+            uint32_t r;
+            if (sc.ss == 0)
+                r = sc.ah == 0 ? dc_first(br, tabs[c], sc.al, &st.pred[c], blk) : dc_refine(br, sc.al, blk);
+            else
+                r = sc.ah == 0 ? ac_first<Order>(br, tabs[0], sc.ss, sc.se, sc.al, &st.eobrun, blk) : ac_refine<Order>(br, tabs[0], sc.ss, sc.se, sc.al, &st.eobrun, blk);
+            if (r != ST_OK) return r;
+        }
+    return ST_OK;
+}
+
+// where block `at` (unit * bpu + b in the scan's own order) lives in the file's MCU-ordered coefficients.  A scan of one component walks the
+// blocks of that component's own extent in raster order, which is narrower than the MCU grid when the image ends inside an MCU.
+LSPDEC_HD inline uint32_t prog_block_index(const FileDesc &f, const ScanDesc &sc, uint32_t at)
+{
+    if (sc.ncomp != 1 || f.ncomp == 1) return at;                          // interleaved, or one component: the raster is the MCU order
+    const uint32_t by = at / sc.bw, bx = at - by * sc.bw, c = sc.comp[0];
+    if (c) return (by * f.mcux + bx) * f.bpm + f.hs * f.vs + c - 1;
+    return ((by / f.vs) * f.mcux + bx / f.hs) * f.bpm + (by % f.vs) * f.hs + bx % f.hs;
+}
+
+// ---- the parser and scan walker of a progressive file: the whole file, marker by marker
+struct ProgFile {
+    uint32_t status;
+    uint32_t width, height, ncomp, hs, vs;
+    uint32_t restart0;                  // the interval in force at the first scan
+    uint32_t nscan, nseg, ntab;         // scans, restart intervals of all scans, table snapshots
+    uint8_t comp_id[4], comp_q[4], q_seen[4];
+    uint16_t q[4][64];                  // natural order
+    uint8_t huff_seen[2][4];
+    uint8_t huff_bits[2][4][17];
+    uint8_t huff_vals[2][4][256];
+    int8_t coef_al[3][64];              // jdphuff.c coef_bits: the Al each coefficient has reached, -1 before its first scan
+    uint64_t data_begin, data_end;      // the first entropy-coded byte of the first scan, the EOI marker
+};
+
+// Walks p[0, n).  scans / segs / tabs may be null (count only); otherwise they take at most the given counts and offsets are file offsets + base.
+// Host only (build_table).
+inline uint32_t walk_progressive(const uint8_t *p, size_t n, uint32_t max_side, ProgFile *o, uint64_t base, uint32_t file, ScanDesc *scans, uint32_t scan_cap,
+                                 SegDesc *segs, uint32_t seg_cap, HuffTable *tabs, uint32_t tab_cap)
+{
+    *o = ProgFile{};
+    for (int c = 0; c < 3; ++c)
+        for (int k = 0; k < 64; ++k) o->coef_al[c][k] = -1;
+    bool sof = false, adobe = false;
+    uint32_t adobe_transform = 0, restart = 0;
+    if (n < 4 || p[0] != 0xff || p[1] != 0xd8) return o->status = ST_CORRUPT;
+    size_t i = 2;
+    for (;;) {
+        if (i + 2 > n) return o->status = ST_CORRUPT;                          // data that ends early
+        if (p[i] != 0xff) return o->status = ST_CORRUPT;
+        while (i + 1 < n && p[i + 1] == 0xff) ++i;                             // fill bytes between segments
+        if (i + 2 > n) return o->status = ST_CORRUPT;
+        const uint32_t m = p[i + 1];
+        i += 2;
+        if (m == 0xd9) {                                                       // EOI
+            if (o->nscan == 0) return o->status = ST_CORRUPT;
+            for (uint32_t c = 0; c < o->ncomp; ++c)
+                for (int k = 0; k < 64; ++k)
+                    if (o->coef_al[c][k] != 0) return o->status = ST_UNSUPPORTED;     // incomplete: libjpeg would smooth, or show a coarser image
+            o->data_end = i - 2;
+            return o->status = ST_OK;
+        }
+        if (m == 0xd8 || (m >= 0xd0 && m <= 0xd7) || m == 0x01 || m == 0x00) return o->status = ST_CORRUPT;
+        if (i + 2 > n) return o->status = ST_CORRUPT;
+        const size_t len = be16(p + i);
+        if (len < 2 || i + len > n) return o->status = ST_CORRUPT;
+        const uint8_t *s = p + i + 2;
+        const size_t sl = len - 2;
+        if (m == 0xc2) {                                                       // SOF2
+            if (sof) return o->status = ST_CORRUPT;
+            if (sl < 6) return o->status = ST_CORRUPT;
+            const uint32_t nc = s[5];
+            if (sl != 6 + 3 * (size_t)nc) return o->status = ST_CORRUPT;
+            if (s[0] != 8) return o->status = ST_UNSUPPORTED;
+            o->height = be16(s + 1);
+            o->width = be16(s + 3);
+            if (o->width == 0) return o->status = ST_CORRUPT;
+            if (o->height == 0) return o->status = ST_UNSUPPORTED;             // the height comes in a DNL marker
+            if (o->width > max_side || o->height > max_side) return o->status = ST_UNSUPPORTED;
+            if (nc != 1 && nc != 3) return o->status = ST_UNSUPPORTED;
+            o->ncomp = nc;
+            for (uint32_t c = 0; c < nc; ++c) {
+                o->comp_id[c] = s[6 + 3 * c];
+                const uint32_t hv = s[7 + 3 * c], tq = s[8 + 3 * c];
+                if (tq > 3 || (hv >> 4) == 0 || (hv >> 4) > 4 || (hv & 15) == 0 || (hv & 15) > 4) return o->status = ST_CORRUPT;
+                o->comp_q[c] = (uint8_t)tq;
+                if (c == 0) {
+                    o->hs = hv >> 4;
+                    o->vs = hv & 15;
+                } else if (hv != 0x11) {
+                    return o->status = ST_UNSUPPORTED;
+                }
+            }
+            if (nc == 1 ? (o->hs != 1 || o->vs != 1) : !((o->hs == 1 || o->hs == 2) && (o->vs == 1 || (o->vs == 2 && o->hs == 2))))
+                return o->status = ST_UNSUPPORTED;
+            if (nc == 3 && o->comp_id[0] == 'R' && o->comp_id[1] == 'G' && o->comp_id[2] == 'B') return o->status = ST_UNSUPPORTED;
+            if (nc == 3 && (o->comp_id[0] == o->comp_id[1] || o->comp_id[0] == o->comp_id[2] || o->comp_id[1] == o->comp_id[2])) return o->status = ST_CORRUPT;
+            sof = true;
+        } else if (m >= 0xc0 && m <= 0xcf && m != 0xc4 && m != 0xc8) {         // SOF0 with several scans, extended, lossless, arithmetic (SOFn, DAC)
+            return o->status = ST_UNSUPPORTED;
+        } else if (m == 0xc4) {                                                // DHT: any number of tables, ids 0..3; a later one replaces an earlier one
+            size_t at = 0;
+            while (at < sl) {
+                if (at + 17 > sl) return o->status = ST_CORRUPT;
+                const uint32_t tc = s[at] >> 4, th = s[at] & 15;
+                if (tc > 1 || th > 3) return o->status = ST_CORRUPT;
+                uint32_t count = 0;
+                for (int l = 1; l <= 16; ++l) count += s[at + l];
+                if (count > 256 || at + 17 + count > sl) return o->status = ST_CORRUPT;
+                o->huff_bits[tc][th][0] = 0;
+                for (int l = 1; l <= 16; ++l) o->huff_bits[tc][th][l] = s[at + l];
+                for (uint32_t k = 0; k < 256; ++k) o->huff_vals[tc][th][k] = k < count ? s[at + 17 + k] : 0;
+                o->huff_seen[tc][th] = 1;
+                at += 17 + count;
+            }
+        } else if (m == 0xdb) {                                                // DQT
+            if (o->nscan) return o->status = ST_UNSUPPORTED;                   // libjpeg latches a component's table at its first scan
+            size_t at = 0;
+            while (at < sl) {
+                const uint32_t pq = s[at] >> 4, tq = s[at] & 15;
+                if (tq > 3) return o->status = ST_CORRUPT;
+                if (pq != 0) return o->status = pq == 1 ? ST_UNSUPPORTED : ST_CORRUPT;
+                if (at + 65 > sl) return o->status = ST_CORRUPT;
+                for (int k = 0; k < 64; ++k) o->q[tq][zigzag_to_natural(k)] = s[at + 1 + k];
+                o->q_seen[tq] = 1;
+                at += 65;
+            }
+        } else if (m == 0xdc) {                                                // DNL
+            return o->status = ST_UNSUPPORTED;
+        } else if (m == 0xdd) {                                                // DRI: holds for the scans that follow
+            if (sl != 2) return o->status = ST_CORRUPT;
+            restart = be16(s);
+        } else if (m == 0xee && o->nscan == 0) {                               // APP14: Adobe's colour transform flag
+            if (sl >= 12 && s[0] == 'A' && s[1] == 'd' && s[2] == 'o' && s[3] == 'b' && s[4] == 'e') {
+                adobe = true;
+                adobe_transform = s[11];
+            }
+        } else if (m == 0xda) {                                                // SOS
+            if (!sof) return o->status = ST_CORRUPT;
+            if (sl < 1) return o->status = ST_CORRUPT;
+            const uint32_t ns = s[0];
+            if (ns < 1 || ns > 4 || sl != 4 + 2 * (size_t)ns) return o->status = ST_CORRUPT;
+            if (o->nscan == kMaxScans) return o->status = ST_UNSUPPORTED;
+            ScanDesc sc{};
+            sc.file = file;
+            sc.ncomp = (uint8_t)ns;
+            for (uint32_t j = 0; j < ns; ++j) {
+                uint32_t c = 0;
+                while (c < o->ncomp && o->comp_id[c] != s[1 + 2 * j]) ++c;
+                if (c == o->ncomp) return o->status = ST_CORRUPT;              // an unknown component
+                for (uint32_t e = 0; e < j; ++e)
+                    if (sc.comp[e] == c) return o->status = ST_CORRUPT;        // a repeated one
+                sc.comp[j] = (uint8_t)c;
+                sc.td[j] = s[2 + 2 * j] >> 4;
+                sc.ta[j] = s[2 + 2 * j] & 15;
+                if (sc.td[j] > 3 || sc.ta[j] > 3) return o->status = ST_CORRUPT;
+            }
+            sc.ss = s[1 + 2 * ns];
+            sc.se = s[2 + 2 * ns];
+            sc.ah = s[3 + 2 * ns] >> 4;
+            sc.al = s[3 + 2 * ns] & 15;
+            // libjpeg's rules for a scan of a progressive file (jdphuff.c start_pass_phuff_decoder: "bad progression parameters")
+            if (sc.ss > sc.se || sc.se > 63 || (sc.ss == 0 && sc.se != 0) || (sc.ss != 0 && ns != 1) || (sc.ah != 0 && sc.al != sc.ah - 1) || sc.al > 13)
+                return o->status = ST_CORRUPT;
+            if (ns != 1 && ns != o->ncomp) return o->status = ST_UNSUPPORTED;  // an MCU of two components out of three
+            for (uint32_t j = 0; ns > 1 && j < ns; ++j)
+                if (sc.comp[j] != j) return o->status = ST_UNSUPPORTED;        // components out of frame order
+            if (o->nscan == 0) {
+                if (adobe && adobe_transform == 0 && o->ncomp == 3) return o->status = ST_UNSUPPORTED;    // RGB, not YCbCr
+                for (uint32_t c = 0; c < o->ncomp; ++c)
+                    if (!o->q_seen[o->comp_q[c]]) return o->status = ST_CORRUPT;
+            }
+            // the progression (coef_bits): libjpeg warns and decodes on, this decoder refuses
+            for (uint32_t j = 0; j < ns; ++j) {
+                int8_t *al = o->coef_al[sc.comp[j]];
+                if (sc.ss != 0 && al[0] < 0) return o->status = ST_UNSUPPORTED;             // AC before the component's DC
+                for (int k = sc.ss; k <= sc.se; ++k) {
+                    if (sc.ah == 0 ? al[k] != -1 : al[k] != (int8_t)sc.ah) return o->status = ST_UNSUPPORTED;
+                    al[k] = (int8_t)sc.al;
+                }
+            }
+            // the tables the scan decodes with, as they stand now
+            sc.table0 = o->ntab;
+            sc.ntab = sc.ss ? 1 : sc.ah ? 0 : ns;
+            for (uint32_t j = 0; j < sc.ntab; ++j) {
+                const int cls = sc.ss ? 1 : 0, id = sc.ss ? sc.ta[0] : sc.td[j];
+                if (!o->huff_seen[cls][id]) return o->status = ST_UNSUPPORTED;              // a table the file has not defined
+                HuffTable t;
+                if (!build_table(o->huff_bits[cls][id], o->huff_vals[cls][id], &t)) return o->status = ST_CORRUPT;
+                if (tabs) {
+                    if (o->ntab + j >= tab_cap) return o->status = ST_CORRUPT;
+                    tabs[o->ntab + j] = t;
+                }
+            }
+            o->ntab += sc.ntab;
+            // geometry of the scan
+            const uint32_t mcux = (o->width + 8 * o->hs - 1) / (8 * o->hs), mcuy = (o->height + 8 * o->vs - 1) / (8 * o->vs);
+            if (ns > 1 || o->ncomp == 1) {
+                sc.bw = mcux;
+                sc.bh = mcuy;
+            } else {
+                const uint32_t wc = sc.comp[0] ? (o->width + o->hs - 1) / o->hs : o->width, hc = sc.comp[0] ? (o->height + o->vs - 1) / o->vs : o->height;
+                sc.bw = (wc + 7) / 8;
+                sc.bh = (hc + 7) / 8;
+            }
+            sc.units = sc.bw * sc.bh;
+            sc.restart = restart;
+            if (o->nscan == 0) {
+                o->restart0 = restart;
+                o->data_begin = i + len;
+            }
+            // the entropy-coded data: restart intervals up to the next marker that is no RSTn
+            const uint32_t ri = restart, want = ri ? (sc.units + ri - 1) / ri : 1;
+            size_t pos = i + len, seg_begin = pos;
+            uint32_t k = 0;
+            sc.begin = base + pos;
+            sc.seg0 = o->nseg;
+            for (;;) {
+                while (pos < n && p[pos] != 0xff) ++pos;
+                if (pos + 1 >= n) return o->status = ST_CORRUPT;               // data that ends early
+                const uint32_t mm = p[pos + 1];
+                if (mm == 0x00) {
+                    pos += 2;
+                    continue;
+                }
+                if (mm == 0xff) return o->status = ST_UNSUPPORTED;             // fill bytes inside the scan
+                const bool rst = mm >= 0xd0 && mm <= 0xd7;
+                if (rst && ri == 0) return o->status = ST_UNSUPPORTED;
+                if (rst && mm != 0xd0 + (k & 7)) return o->status = ST_CORRUPT;            // a wrong RSTn: the numbering starts again at every scan
+                if (rst ? k + 1 >= want : k + 1 != want) return o->status = ST_CORRUPT;    // one too many, or one missing
+                if (segs) {
+                    if (o->nseg + k >= seg_cap) return o->status = ST_CORRUPT;
+                    SegDesc &g = segs[o->nseg + k];
+                    g.file = file;
+                    g.mcu0 = ri ? k * ri : 0;
+                    g.nmcu = ri ? (sc.units - g.mcu0 < ri ? sc.units - g.mcu0 : ri) : sc.units;
+                    g.pad = 0;
+                    g.begin = base + seg_begin;
+                    g.end = base + pos;
+                }
+                ++k;
+                if (!rst) break;
+                pos += 2;
+                seg_begin = pos;
+            }
+            sc.nseg = k;
+            sc.end = base + pos;
+            o->nseg += k;
+            if (scans) {
+                if (o->nscan >= scan_cap) return o->status = ST_CORRUPT;
+                scans[o->nscan] = sc;
+            }
+            ++o->nscan;
+            i = pos;                                                           // the marker that ended the scan is read next
+            continue;
+        }
+        // APPn, COM and the rest carry a length and are skipped
+        i += len;
+    }
 }
 
 }  // namespace lspdec

@@ -17,6 +17,9 @@ struct BlobHeader {
     uint64_t files_off, segs_off, tables_off, status_off, data_off;
     uint64_t planes_ws_off;                         // the plane area inside the workspace (the coefficients come first)
     uint64_t pad2;
+    // progressive files (kFlagProgressive): their scans, the restart intervals of those, and the table snapshots; all empty without the flag
+    uint32_t nprog, nscans, npsegs, nptabs;
+    uint64_t scans_off, psegs_off, ptables_off, pad3;
 };
 static_assert(sizeof(BlobHeader) % 16 == 0, "the areas behind the header stay 16-byte aligned");
 
@@ -36,6 +39,9 @@ inline const BlobHeader *header_of(const void *blob)
 inline const FileDesc *files_of(const void *blob) { return reinterpret_cast<const FileDesc *>(static_cast<const char *>(blob) + header_of(blob)->files_off); }
 inline const SegDesc *segs_of(const void *blob) { return reinterpret_cast<const SegDesc *>(static_cast<const char *>(blob) + header_of(blob)->segs_off); }
 inline const HuffTable *tables_of(const void *blob) { return reinterpret_cast<const HuffTable *>(static_cast<const char *>(blob) + header_of(blob)->tables_off); }
+inline const ScanDesc *scans_of(const void *blob) { return reinterpret_cast<const ScanDesc *>(static_cast<const char *>(blob) + header_of(blob)->scans_off); }
+inline const SegDesc *psegs_of(const void *blob) { return reinterpret_cast<const SegDesc *>(static_cast<const char *>(blob) + header_of(blob)->psegs_off); }
+inline const HuffTable *ptables_of(const void *blob) { return reinterpret_cast<const HuffTable *>(static_cast<const char *>(blob) + header_of(blob)->ptables_off); }
 
 // parser + scan walker: the status of a whole file, its segment count and where its entropy-coded data ends
 inline uint32_t examine(const uint8_t *p, size_t n, uint32_t max_side, Parsed *f, uint32_t *nseg, uint64_t *scan_end)
@@ -59,15 +65,37 @@ inline uint32_t examine(const uint8_t *p, size_t n, uint32_t max_side, Parsed *f
     return ST_OK;
 }
 
-// Returns the size of the block; writes it when blob is not null.  -1: an output form that does not fit its file; -2: past 4 GiB / 2^32 segments.
-inline int64_t plan(const uint8_t *const *files, const size_t *lens, const OutputDesc *outs, int n, uint32_t max_side, void *blob)
+// examine() under flags: a file the baseline parser calls UNSUPPORTED goes to the progressive walker when kFlagProgressive is set.  *progressive
+// says which of f / pf holds the answer.
+inline uint32_t examine_flags(const uint8_t *p, size_t n, uint32_t max_side, uint32_t flags, Parsed *f, uint32_t *nseg, uint64_t *scan_end, ProgFile *pf,
+                              bool *progressive)
 {
-    uint64_t nsegs = 0, data = 0;
+    *progressive = false;
+    const uint32_t st = examine(p, n, max_side, f, nseg, scan_end);
+    if (st != ST_UNSUPPORTED || !(flags & kFlagProgressive)) return st;
+    *progressive = true;
+    return walk_progressive(p, n, max_side, pf, 0, 0, nullptr, 0, nullptr, 0, nullptr, 0);
+}
+
+// Returns the size of the block; writes it when blob is not null.  -1: an output form that does not fit its file; -2: past 4 GiB / 2^32 segments.
+inline int64_t plan(const uint8_t *const *files, const size_t *lens, const OutputDesc *outs, int n, uint32_t max_side, void *blob, uint32_t flags = 0)
+{
+    uint64_t nsegs = 0, data = 0, nscans = 0, npsegs = 0, nptabs = 0;
+    uint32_t nprog = 0;
     Parsed f;
+    ProgFile pf;
+    bool prog;
     for (int i = 0; i < n; ++i) {
         uint32_t ns;
         uint64_t e;
-        if (examine(files[i], lens[i], max_side, &f, &ns, &e) == ST_OK) {
+        if (examine_flags(files[i], lens[i], max_side, flags, &f, &ns, &e, &pf, &prog) != ST_OK) continue;
+        if (prog) {
+            ++nprog;
+            nscans += pf.nscan;
+            npsegs += pf.nseg;
+            nptabs += pf.ntab;
+            data += pf.data_end - pf.data_begin;
+        } else {
             nsegs += ns;
             data += e - f.scan_begin;
         }
@@ -79,10 +107,17 @@ inline int64_t plan(const uint8_t *const *files, const size_t *lens, const Outpu
     h.segs_off = up(h.files_off + (uint64_t)n * sizeof(FileDesc), 16);
     h.tables_off = up(h.segs_off + nsegs * sizeof(SegDesc), 16);
     h.status_off = h.tables_off + (uint64_t)n * 4 * sizeof(HuffTable);
-    h.data_off = up(h.status_off + (uint64_t)n * 4, 16);
+    h.scans_off = up(h.status_off + (uint64_t)n * 4, 16);
+    h.psegs_off = up(h.scans_off + nscans * sizeof(ScanDesc), 16);
+    h.ptables_off = up(h.psegs_off + npsegs * sizeof(SegDesc), 16);
+    h.data_off = up(h.ptables_off + nptabs * sizeof(HuffTable), 16);
     h.bytes = up(h.data_off + data, 16) + 16;                                  // the kernel's 16-byte loads stay inside the block
-    if (h.bytes >> 32 || nsegs >> 32) return -2;
+    if (h.bytes >> 32 || nsegs >> 32 || npsegs >> 32) return -2;
     h.nsegs = (uint32_t)nsegs;
+    h.nprog = nprog;
+    h.nscans = (uint32_t)nscans;
+    h.npsegs = (uint32_t)npsegs;
+    h.nptabs = (uint32_t)nptabs;
     if (!blob) return (int64_t)h.bytes;
 
     char *b = static_cast<char *>(blob);
@@ -91,17 +126,35 @@ inline int64_t plan(const uint8_t *const *files, const size_t *lens, const Outpu
     SegDesc *sd = reinterpret_cast<SegDesc *>(b + h.segs_off);
     HuffTable *ht = reinterpret_cast<HuffTable *>(b + h.tables_off);
     uint32_t *status = reinterpret_cast<uint32_t *>(b + h.status_off);
+    ScanDesc *scd = reinterpret_cast<ScanDesc *>(b + h.scans_off);
+    SegDesc *psd = reinterpret_cast<SegDesc *>(b + h.psegs_off);
+    HuffTable *pht = reinterpret_cast<HuffTable *>(b + h.ptables_off);
     uint64_t at = h.data_off, planes = 0;
-    uint32_t seg = 0;
+    uint32_t seg = 0, scan = 0, pseg = 0, ptab = 0;
     h.has_outputs = 1;                                                         // until a decodable file turns up without one
     for (int i = 0; i < n; ++i) {
         FileDesc &d = fd[i];
         uint32_t ns;
         uint64_t e;
-        d.status = status[i] = examine(files[i], lens[i], max_side, &f, &ns, &e);
+        d.status = status[i] = examine_flags(files[i], lens[i], max_side, flags, &f, &ns, &e, &pf, &prog);
         d.table0 = 4 * (uint32_t)i;
         d.seg0 = seg;
+        d.scan0 = scan;
         if (d.status != ST_OK) continue;
+        if (prog) {                                                            // the fields both kinds of file share, out of the progressive walker's record
+            f = Parsed{};
+            f.width = pf.width;
+            f.height = pf.height;
+            f.ncomp = pf.ncomp;
+            f.hs = pf.hs;
+            f.vs = pf.vs;
+            f.restart = pf.restart0;
+            for (int c = 0; c < 4; ++c) {
+                f.comp_q[c] = pf.comp_q[c];
+                for (int k = 0; k < 64; ++k) f.q[c][k] = pf.q[c][k];
+            }
+            ns = 0;
+        }
         d.width = f.width;
         d.height = f.height;
         d.ncomp = f.ncomp;
@@ -123,26 +176,47 @@ inline int64_t plan(const uint8_t *const *files, const size_t *lens, const Outpu
             planes += up((uint64_t)d.plane_w[c] * d.plane_h[c], 16);
             for (int k = 0; k < 64; ++k) d.q[c][k] = f.q[f.comp_q[c]][k];
         }
-        for (int id = 0; id < 2; ++id)
-            for (int cls = 0; cls < 2; ++cls) {
-                uint8_t bits[17], vals[256];
-                if (f.huff_seen[cls][id]) {
-                    for (int l = 0; l < 17; ++l) bits[l] = f.huff_bits[cls][id][l];
-                    for (int k = 0; k < 256; ++k) vals[k] = f.huff_vals[cls][id][k];
-                } else {
-                    default_huffman(cls, id, bits, vals);
-                }
-                if (!build_table(bits, vals, &ht[d.table0 + 2 * id + cls]))    // an unused table of the file may be no prefix code: an empty table
-                    for (int l = 0; l < 17; ++l) ht[d.table0 + 2 * id + cls].maxcode[l] = -1;
+        if (prog) {
+            // the bytes from the first scan's data up to the EOI marker (the markers between the scans travel along), and the scans, their restart
+            // intervals and their tables with offsets into the block
+            const uint64_t nbytes = pf.data_end - pf.data_begin;
+            for (uint64_t k = 0; k < nbytes; ++k) b[at + k] = (char)files[i][pf.data_begin + k];
+            const uint64_t begin = pf.data_begin;
+            ProgFile again;
+            walk_progressive(files[i], lens[i], max_side, &again, at - begin, (uint32_t)i, scd + scan, h.nscans - scan, psd + pseg, h.npsegs - pseg, pht + ptab,
+                             h.nptabs - ptab);
+            d.progressive = 1;
+            d.nscan = again.nscan;
+            for (uint32_t s = 0; s < again.nscan; ++s) {                       // the walker counted from this file's first entry
+                scd[scan + s].seg0 += pseg;
+                scd[scan + s].table0 += ptab;
             }
-        // the entropy-coded bytes, and the segments with offsets into the block
-        const uint64_t nbytes = e - f.scan_begin;
-        for (uint64_t k = 0; k < nbytes; ++k) b[at + k] = (char)files[i][f.scan_begin + k];
-        uint32_t got;
-        uint64_t end;
-        walk_scan(files[i], lens[i], f, at - f.scan_begin, (uint32_t)i, sd + seg, ns, &got, &end);
-        seg += ns;
-        at += nbytes;
+            scan += again.nscan;
+            pseg += again.nseg;
+            ptab += again.ntab;
+            at += nbytes;
+        } else {
+            for (int id = 0; id < 2; ++id)
+                for (int cls = 0; cls < 2; ++cls) {
+                    uint8_t bits[17], vals[256];
+                    if (f.huff_seen[cls][id]) {
+                        for (int l = 0; l < 17; ++l) bits[l] = f.huff_bits[cls][id][l];
+                        for (int k = 0; k < 256; ++k) vals[k] = f.huff_vals[cls][id][k];
+                    } else {
+                        default_huffman(cls, id, bits, vals);
+                    }
+                    if (!build_table(bits, vals, &ht[d.table0 + 2 * id + cls]))    // an unused table of the file may be no prefix code: an empty table
+                        for (int l = 0; l < 17; ++l) ht[d.table0 + 2 * id + cls].maxcode[l] = -1;
+                }
+            // the entropy-coded bytes, and the segments with offsets into the block
+            const uint64_t nbytes = e - f.scan_begin;
+            for (uint64_t k = 0; k < nbytes; ++k) b[at + k] = (char)files[i][f.scan_begin + k];
+            uint32_t got;
+            uint64_t end;
+            walk_scan(files[i], lens[i], f, at - f.scan_begin, (uint32_t)i, sd + seg, ns, &got, &end);
+            seg += ns;
+            at += nbytes;
+        }
         h.total_blocks += d.nblk;
         if (d.nblk > h.max_blocks) h.max_blocks = d.nblk;
         if (d.width * d.height > h.max_pixels) h.max_pixels = d.width * d.height;
@@ -169,6 +243,35 @@ struct MemSrc {
     uint8_t at(uint64_t pos) const { return base[pos]; }
 };
 
+// stage 1 of a progressive file on the host: its scans in file order over the same coefficients, with the procedures the kernel runs
+inline uint32_t host_progressive(const void *blob, const FileDesc &d, int16_t *out)
+{
+    uint8_t comp_of[kMaxBlocksPerMcu];
+    int bpm;
+    block_components(d.ncomp, d.hs, d.vs, comp_of, &bpm);
+    const MemSrc src{static_cast<const uint8_t *>(blob)};
+    for (uint32_t s = 0; s < d.nscan; ++s) {
+        const ScanDesc &sc = scans_of(blob)[d.scan0 + s];
+        const HuffTable *tabs = ptables_of(blob) + sc.table0;
+        const int bpu = sc.ncomp > 1 ? bpm : 1;
+        ScanState st{};
+        for (uint32_t g = 0; g < sc.nseg; ++g) {
+            const SegDesc &sg = psegs_of(blob)[sc.seg0 + g];
+            BitReader<MemSrc> br(src, sg.begin, sg.end);
+            st = ScanState{};                                                  // predictions and the end-of-band run start again at every RSTn
+            for (uint32_t u = 0; u < sg.nmcu; ++u) {
+                const uint32_t at = prog_block_index(d, sc, (sg.mcu0 + u) * bpu);
+                if (at + bpu > d.nblk) return ST_CORRUPT;
+                const uint32_t r = prog_units<NaturalOrder>(br, sc, tabs, comp_of, bpu, st, out + (uint64_t)at * 64, 1);
+                if (r != ST_OK) return r;
+            }
+            if (!br.drained()) return ST_CORRUPT;
+        }
+        if (st.eobrun) return ST_CORRUPT;                                      // a run that reaches past the scan's last block
+    }
+    return ST_OK;
+}
+
 // stage 1 of file i on the host: the status the kernel would leave, and (on ST_OK only) the coefficients
 inline uint32_t host_coefficients(const void *blob, int i, int16_t *out)
 {
@@ -179,6 +282,7 @@ inline uint32_t host_coefficients(const void *blob, int i, int16_t *out)
     block_components(d.ncomp, d.hs, d.vs, comp_of, &bpm);
     const MemSrc src{static_cast<const uint8_t *>(blob)};
     for (uint64_t k = 0; k < (uint64_t)d.nblk * 64; ++k) out[k] = 0;
+    if (d.progressive) return host_progressive(blob, d, out);
     for (uint32_t s = 0; s < d.nseg; ++s) {
         const SegDesc &sg = segs_of(blob)[d.seg0 + s];
         BitReader<MemSrc> br(src, sg.begin, sg.end);

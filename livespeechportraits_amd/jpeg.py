@@ -14,7 +14,8 @@ them).  No default uses them.
 The way back is ``JpegDecoder`` (include/lspjpegdec.h): baseline files -- the candidate images of demo.py:88-95, the frames of an
 ``AviWriter`` recording, anything Pillow writes by default -- decoded on the device to the pixels Pillow returns, bit for bit.  The
 host does the marker parsing and the batch layout (``DecodePlan``, no device needed); the compressed bytes cross PCIe once, in one
-block with the tables.  ``probe`` reports a file's geometry and whether it can be decoded.
+block with the tables.  ``probe`` reports a file's geometry and whether it can be decoded.  With ``progressive=True`` (``probe``,
+``DecodePlan``, ``JpegDecoder``) complete progressive files are taken as well, scan by scan, to the same pixels; off by default.
 """
 from __future__ import annotations
 
@@ -257,6 +258,7 @@ UNSUPPORTED, CORRUPT, RANGE = 1, 2, 3                          # the per-file st
 STATUS_NAMES = {0: "OK", UNSUPPORTED: "UNSUPPORTED", CORRUPT: "CORRUPT", RANGE: "RANGE"}
 MAX_SIDE = 8192                                                # LSPJPEG_MAX_SIDE
 FORM_RGB8, FORM_GRAY8, FORM_PLANAR_F32 = 0, 1, 2
+FLAG_PROGRESSIVE = 1                                           # LSPJPEG_DEC_FLAG_PROGRESSIVE
 
 
 class JpegError(ValueError):
@@ -290,12 +292,30 @@ def _info(i: "N.JpegDecInfo") -> JpegInfo:
     return JpegInfo(*(int(getattr(i, name)) for name in JpegInfo._fields))
 
 
-def probe(data: bytes) -> JpegInfo:
-    """Geometry, sampling, restart interval and whether ``JpegDecoder`` takes the file (``status == 0``); host only."""
+class JpegScan(NamedTuple):
+    """one scan of a progressive file, as the planner recorded it (lspjpeg_dec_scan)"""
+    components: tuple           # indices in frame order: one, or all of the frame's
+    dc_tables: tuple            # the table ids the SOS names, per scan component
+    ac_tables: tuple
+    ss: int
+    se: int
+    ah: int
+    al: int
+    restart_interval: int       # the DRI in force, in units; 0 = none
+    units: int                  # interleaved MCUs, or the one component's own blocks
+    segments: int
+    begin: int                  # inside the block: the first entropy-coded byte, the marker that ends the scan
+    end: int
+
+
+def probe(data: bytes, progressive: bool = False) -> JpegInfo:
+    """Geometry, sampling, restart interval and whether ``JpegDecoder`` takes the file (``status == 0``); host only.  ``progressive``: the
+    answer of a decoder made with ``progressive=True`` (complete SOF2 files are taken; include/lspjpegdec.h says what the fields then mean)."""
     lib = N.load()
     data = bytes(data)
     info = N.JpegDecInfo()
-    N.check_jpeg_dec(lib.lspjpeg_dec_probe(ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p), len(data), ctypes.byref(info)))
+    N.check_jpeg_dec(lib.lspjpeg_dec_probe_flags(ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p), len(data), FLAG_PROGRESSIVE if progressive else 0,
+                                                 ctypes.byref(info)))
     return _info(info)
 
 
@@ -308,10 +328,12 @@ def _aligned(nbytes: int) -> np.ndarray:
 class DecodePlan:
     """The descriptor block of a batch (``lspjpeg_dec_plan``): per-file tables and output descriptions, the entropy-coded bytes, one
     entry per restart interval.  Host only.  ``outputs`` is a list of ``(ptr, table_ptr, plane_stride, form)`` per file (device
-    pointers), or None to plan for the host alone.  ``buffer(nbytes)`` supplies the memory (a pinned tensor's numpy view, say)."""
+    pointers), or None to plan for the host alone.  ``buffer(nbytes)`` supplies the memory (a pinned tensor's numpy view, say).
+    ``progressive``: complete progressive files are planned too, scan by scan (``scans(i)``); without it they are UNSUPPORTED."""
 
-    def __init__(self, files: Sequence[bytes], max_side: int = MAX_SIDE, outputs=None, buffer=None):
+    def __init__(self, files: Sequence[bytes], max_side: int = MAX_SIDE, outputs=None, buffer=None, progressive: bool = False):
         self.lib = N.load()
+        flags = FLAG_PROGRESSIVE if progressive else 0
         self.files = [bytes(f) for f in files]
         n = len(self.files)
         if n < 1:
@@ -324,12 +346,12 @@ class DecodePlan:
             for o, spec in zip(outs, outputs):
                 if spec is not None:
                     o.ptr, o.table, o.plane_stride, o.form = spec[0], spec[1] or None, int(spec[2]), int(spec[3])
-        need = N.check_jpeg_dec(self.lib.lspjpeg_dec_plan(ptrs, lens, outs, n, int(max_side), None, 0))
+        need = N.check_jpeg_dec(self.lib.lspjpeg_dec_plan_flags(ptrs, lens, outs, n, int(max_side), flags, None, 0))
         self.blob = buffer(need) if buffer is not None else _aligned(need)
         if self.blob.dtype != np.uint8 or self.blob.size < need or self.blob.ctypes.data % 16:
             raise ValueError("the plan needs a 16-byte aligned uint8 buffer of %d bytes" % need)
         self.ptr = ctypes.c_void_p(self.blob.ctypes.data)
-        self.bytes = N.check_jpeg_dec(self.lib.lspjpeg_dec_plan(ptrs, lens, outs, n, int(max_side), self.ptr, self.blob.size))
+        self.bytes = N.check_jpeg_dec(self.lib.lspjpeg_dec_plan_flags(ptrs, lens, outs, n, int(max_side), flags, self.ptr, self.blob.size))
         self.summary = N.JpegDecSummary()
         N.check_jpeg_dec(self.lib.lspjpeg_dec_summary_of(self.ptr, ctypes.byref(self.summary)))
 
@@ -355,6 +377,17 @@ class DecodePlan:
         N.check_jpeg_dec(self.lib.lspjpeg_dec_plan_segment(self.ptr, int(k), ctypes.byref(f), ctypes.byref(m0), ctypes.byref(nm), ctypes.byref(b), ctypes.byref(e)))
         return f.value, m0.value, nm.value, b.value, e.value
 
+    def scans(self, i: int) -> List[JpegScan]:
+        """the scans of file i in file order; empty for a file that was not planned as a progressive one"""
+        out = []
+        for k in range(N.check_jpeg_dec(self.lib.lspjpeg_dec_plan_scans(self.ptr, int(i)))):
+            s = N.JpegDecScan()
+            N.check_jpeg_dec(self.lib.lspjpeg_dec_plan_scan(self.ptr, int(i), k, ctypes.byref(s)))
+            nc = int(s.components)
+            out.append(JpegScan(tuple(s.component[:nc]), tuple(s.dc_table[:nc]), tuple(s.ac_table[:nc]), int(s.ss), int(s.se), int(s.ah), int(s.al),
+                                int(s.restart_interval), int(s.units), int(s.segments), int(s.begin), int(s.end)))
+        return out
+
     def host_coefficients(self, i: int):
         """stage 1 of file i on the host, with the code the kernel runs: (status, int16 [blocks, 64] or None)"""
         info = self.file(i)
@@ -369,16 +402,17 @@ class DecodePlan:
 class JpegDecoder:
     """Baseline JPEG files -> pixels on the device, equal to Pillow's (include/lspjpegdec.h states the arithmetic and what is refused).
     One call takes files of different sizes and kinds; batches above ``max_batch`` are split.  ``max_side`` bounds width and height
-    (larger files are UNSUPPORTED).  The device buffers grow to the largest batch seen and are kept."""
+    (larger files are UNSUPPORTED).  The device buffers grow to the largest batch seen and are kept.  ``progressive=True`` also takes complete
+    progressive files (SOF2), mixed freely with baseline ones: one more launch per call that holds any, one wave per such file."""
 
-    def __init__(self, device="cuda:0", max_side: int = 1024, max_batch: int = 64):
+    def __init__(self, device="cuda:0", max_side: int = 1024, max_batch: int = 64, progressive: bool = False):
         self.lib = N.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("the JPEG decoder runs on the MI355X only (no CPU path); the reference's host path is cv2.imread / Pillow")
         if not 1 <= int(max_side) <= MAX_SIDE or int(max_batch) < 1:
             raise ValueError("max_side must be in 1..%d and max_batch >= 1" % MAX_SIDE)
-        self.max_side, self.max_batch = int(max_side), int(max_batch)
+        self.max_side, self.max_batch, self.progressive = int(max_side), int(max_batch), bool(progressive)
         self._host = torch.empty(0, dtype=torch.uint8)
         self._dev = torch.empty(0, dtype=torch.uint8, device=self.device)
         self._ws = torch.empty(0, dtype=torch.uint8, device=self.device)
@@ -391,7 +425,7 @@ class JpegDecoder:
 
     def _run(self, files: Sequence[bytes], outputs) -> List[int]:
         """plan, upload, the three stages, and the status words back: the one synchronisation of a call"""
-        plan = DecodePlan(files, self.max_side, outputs, self._buffer)
+        plan = DecodePlan(files, self.max_side, outputs, self._buffer, self.progressive)
         if all(plan.statuses()):
             return plan.statuses()                             # nothing to decode: the parser refused every file
         n, ws = int(plan.bytes), int(plan.summary.workspace_bytes)
@@ -409,7 +443,7 @@ class JpegDecoder:
         return [int(v) for v in status.numpy().view(np.uint32)]
 
     def _infos(self, files: Sequence[bytes]) -> List[JpegInfo]:
-        infos = [probe(f) for f in files]
+        infos = [probe(f, self.progressive) for f in files]
         for i in infos:
             if i.status == 0 and max(i.width, i.height) > self.max_side:
                 raise ValueError("a %dx%d file: this decoder was made with max_side=%d" % (i.width, i.height, self.max_side))

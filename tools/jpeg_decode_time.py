@@ -13,7 +13,14 @@ runs every GPU step as a process of its own under `timeout`, one after the other
 Cases: `cand4` the four 512^2 quality-95 candidate files in one call; `rec8` / `rec64` 8 / 64 frames of 512^2 at quality 75 (the encoder
 fixtures' files, as a recording holds them: no restart markers, one wave per frame); `rst64` the same 64 frames re-encoded with
 restart_marker_rows=1 (32 waves per frame), to show what restart intervals buy -- needs Pillow for the re-encode, or the files as
-`--restart-npz FILE` (arrays named like the frames)."""
+`--restart-npz FILE` (arrays named like the frames).
+
+    python tools/jpeg_decode_time.py --progressive [output directory]
+
+is the progressive leg, recorded to profiles/jpeg_progressive_time.txt: `prog4`, the four 512^2 quality-95 candidates as progressive files
+(tests/golden/jpeg_prog_512.npz) through JpegDecoder(progressive=True), beside `cand4`, their baseline twins through the existing path, in the
+same session: the traces run prog4, cand4, prog4, cand4 (device time of jpegdec_progressive and of the whole call's kernels), then `--e2e` times
+both calls A-B-A-B against Pillow decoding the same progressive files on this host with 1 and 16 threads plus the upload."""
 import glob
 import io
 import json
@@ -38,6 +45,9 @@ def restart_npz():
 
 
 def files_of(case):
+    if case == "prog4":
+        z = np.load(os.path.join(GOLDEN, "jpeg_prog_512.npz"))
+        return [z[k].tobytes() for k in sorted(z.files) if k.startswith("candidate_")]
     z = np.load(os.path.join(GOLDEN, "jpeg_dec_512.npz"))
     cand = [z[k].tobytes() for k in sorted(z.files) if k.startswith("candidate_")]
     rec = [z[k].tobytes() for k in sorted(z.files) if k.startswith("smooth_")]
@@ -61,13 +71,13 @@ def trace(case, reps):
     import torch
     from livespeechportraits_amd.jpeg import JpegDecoder
     files = files_of(case)
-    dec = JpegDecoder("cuda:0", max_side=512, max_batch=64)
+    dec = JpegDecoder("cuda:0", max_side=512, max_batch=64, progressive=case == "prog4")
     for _ in range(reps + 2):
         dec.decode(files)
     torch.cuda.synchronize()
 
 
-def e2e(out_path):
+def e2e(out_path, cases=CASES):
     import torch
     from livespeechportraits_amd.jpeg import JpegDecoder
     try:
@@ -98,14 +108,14 @@ def e2e(out_path):
 
     from concurrent.futures import ThreadPoolExecutor
     pool = ThreadPoolExecutor(16) if Image is not None else None
-    for case in CASES:
+    for case in cases:
         if case == "rst64" and Image is None and not restart_npz():
             rec["cases"][case] = "skipped: the re-encode with restart markers needs Pillow or --restart-npz"
             continue
         files = files_of(case)
-        dec = JpegDecoder(dev, max_side=512, max_batch=64)
+        dec = JpegDecoder(dev, max_side=512, max_batch=64, progressive=case == "prog4")
         legs = {"device": lambda: dec.decode(files)}
-        if Image is not None:
+        if Image is not None and (cases is CASES or case == "prog4"):
             legs["pillow_1_thread_plus_upload"] = lambda: pil_batch(files, None)
             legs["pillow_16_threads_plus_upload"] = lambda: pil_batch(files, pool)
         for fn in legs.values():
@@ -128,24 +138,28 @@ def stage_times(db, calls):
 
 
 def main():
+    progressive = "--progressive" in sys.argv
     out_dir = next((a for a in sys.argv[1:] if not a.startswith("--") and a != restart_npz()), os.path.join(ROOT, "profiles"))
     work = tempfile.mkdtemp(prefix="jpeg_decode_time_")              # the traces' databases and the e2e record: read here, not kept
     extra = ["--restart-npz", restart_npz()] if restart_npz() else []
-    lines = ["# tools/jpeg_decode_time.py: device JPEG decoder, 512^2 files; stage times from rocprofv3 --kernel-trace (average per launch, us)"]
+    lines = ["# tools/jpeg_decode_time.py%s: device JPEG decoder, 512^2 files; stage times from rocprofv3 --kernel-trace (average per launch, us)"
+             % (" --progressive" if progressive else "")]
     reps = 20
-    for case in CASES:
-        cmd = ["timeout", "-k", "10", "240", "rocprofv3", "--kernel-trace", "--stats", "-d", work, "-o", case, "--", sys.executable, os.path.abspath(__file__),
+    for run, case in enumerate(("prog4", "cand4", "prog4", "cand4") if progressive else CASES):
+        tag = "%s_%d" % (case, run)
+        cmd = ["timeout", "-k", "10", "240", "rocprofv3", "--kernel-trace", "--stats", "-d", work, "-o", tag, "--", sys.executable, os.path.abspath(__file__),
                "--trace", case, str(reps)] + extra
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             lines.append("%s: the trace run ended with status %d; nothing after it was run\n%s" % (case, r.returncode, r.stderr[-800:]))
             break
-        db = sorted(glob.glob(os.path.join(work, "**", case + "_results.db"), recursive=True))
+        db = sorted(glob.glob(os.path.join(work, "**", tag + "_results.db"), recursive=True))
         st = stage_times(db[-1], reps + 2) if db else {}
         lines.append("%-6s %s   sum %.1f us" % (case, "  ".join("%s %.1f us" % (k, v[1]) for k, v in sorted(st.items())), sum(v[1] for v in st.values())))
     else:
         path = os.path.join(work, "e2e.json")
-        r = subprocess.run(["timeout", "-k", "10", "420", sys.executable, os.path.abspath(__file__), "--e2e", path] + extra, capture_output=True, text=True)
+        r = subprocess.run(["timeout", "-k", "10", "420", sys.executable, os.path.abspath(__file__), "--e2e", path] + (["--progressive"] if progressive else []) + extra,
+                           capture_output=True, text=True)
         if r.returncode != 0:
             lines.append("e2e: ended with status %d\n%s" % (r.returncode, r.stderr[-800:]))
         else:
@@ -157,7 +171,7 @@ def main():
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, "jpeg_decode_time.txt"), "w") as f:
+    with open(os.path.join(out_dir, "jpeg_progressive_time.txt" if progressive else "jpeg_decode_time.txt"), "w") as f:
         f.write(text)
     return 0 if "ended with status" not in text else 1
 
@@ -167,6 +181,6 @@ if __name__ == "__main__":
         i = sys.argv.index("--trace")
         trace(sys.argv[i + 1], int(sys.argv[i + 2]))
     elif "--e2e" in sys.argv:
-        e2e(sys.argv[sys.argv.index("--e2e") + 1])
+        e2e(sys.argv[sys.argv.index("--e2e") + 1], ("prog4", "cand4") if "--progressive" in sys.argv else CASES)
     else:
         sys.exit(main())
