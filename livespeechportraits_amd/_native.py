@@ -47,7 +47,7 @@ _RENAMED_ENV = {"LSP_HIP_XCD": "igemm_xcd", "LSP_HIP_FULLK_SPLIT_TILES": "fullk_
 # (LSP_HIP_CAND_CACHE, networks.py) or a typo: it is not handed to the library (a typo gets a warning)
 TUNE_KEYS = frozenset((
     "graph", "wino", "wino4", "wino_pre", "wino_ureg", "wino_prio", "in_wino_stats", "wino_xcd", "wino_il", "wino_rot", "winoup", "winoup_nb", "winoup_target", "igemm_xcd",
-    "bandconv", "bandconv_min_blocks", "bandconv_min_frames", "patch16", "patchup16", "patch16_deep", "patch16_min_blocks", "tail_prefetch", "tail_prefetch_at", "tail_prefetch_wgs", "tail_prefetch_mb", "rowup", "rowlast", "rowlast_fused", "rowconv", "fullk_split", "fullk_split_tiles", "fullk_s2",
+    "bandconv", "bandconv_min_blocks", "bandconv_min_frames", "patch16", "patchup16", "patch16_deep", "patch16_min_blocks", "rowup", "rowlast", "rowlast_fused", "rowconv", "fullk_split", "fullk_split_tiles", "fullk_s2",
     "all_forms", "blob_pad_kb", "fused_splitk", "fused_splitk16", "fullk16", "fullk16_min_frames", "out_wt", "prefetch", "smallm_dma", "smallm_kb", "in_small_regs", "in_smallm_fused", "in_small_max_hw", "lastconv_direct", "lastconv", "firstconv"))
 _HOST_ENV = frozenset(("LSP_HIP_CAND_CACHE", "LSP_HIP_TUNE"))
 
@@ -142,8 +142,6 @@ SIGNATURES = {
     "lspf2f_instance_norm": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] * 6 + [c_void_p] * 3 + [c_size_t, c_void_p]),
     "lspf2f_conv3x3_instnorm_scratch_bytes": (c_size_t, [c_int] * 13),
     "lspf2f_conv3x3_instnorm": (c_int, [c_void_p] * 6 + [c_int] * 14 + [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
-    "lspf2f_wino_chain_scratch_bytes": (c_size_t, [c_int] * 5),
-    "lspf2f_wino_chain": (c_int, [c_int] + [POINTER(c_void_p)] * 6 + [POINTER(c_int)] + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
     "lspf2f_unet_prepare": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
     "lspf2f_pixel_shuffle": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "lspf2f_clock_probe": (c_int, [c_void_p, c_uint32, c_void_p]),

@@ -59,13 +59,6 @@ struct lspf2f_handle {
     int last_route = 0;           // lastconv=<route>: forced direct last-conv kernel (LastConvParams::route; tests only)
     const void *cand_cached = nullptr;   // candidate stack whose first-conv contribution sits in the workspace cache
     hipStream_t cap_stream = nullptr;
-    // tail_prefetch (round 6, off by default): a side branch of the captured forward reads the weights of the <= 16x16 levels while the levels above compute
-    int tail_prefetch = 0;        // 0 off | 1 plain loads | 2 non-temporal loads
-    int tail_prefetch_at = -1;    // layer index the branch forks in front of (-1: the first layer)
-    int tail_prefetch_wgs = 32;   // workgroups of the touching kernel
-    int tail_prefetch_mb = 0;     // 0 = the whole range, else only its first MB
-    hipStream_t side_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::vector<CachedGraph> graphs;
     size_t next_victim = 0;
     void drop_graphs()
@@ -77,9 +70,6 @@ struct lspf2f_handle {
     {
         drop_graphs();
         if (cap_stream) (void)hipStreamDestroy(cap_stream);
-        if (side_stream) (void)hipStreamDestroy(side_stream);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
     }
 };
 
@@ -153,7 +143,10 @@ int lspf2f_create_tuned(const lspf2f_config *cfg, const char *tune, lspf2f_handl
         else if (k == "wino_pre") P.wino_pre = v != 0;
         else if (k == "wino_xcd") P.wino_xcd = v;
         else if (k == "wino_il") P.wino_il = v != 0;
-        else if (k == "wino_ureg") P.wino_ureg = v;
+        else if (k == "wino_ureg") {
+            if (v != 0 && v != 1) { delete h; return fail(LSPF2F_ERR_INVALID_ARGUMENT, "tune: wino_ureg takes 0 (U fragments through LDS) or 1 (in registers)"); }
+            P.wino_ureg = v;
+        }
         else if (k == "in_wino_stats") P.in_wino_stats = v != 0;
         else if (k == "wino_rot") P.wino_rot = v != 0;
         else if (k == "winoup") P.use_winoup = v != 0;
@@ -183,10 +176,6 @@ int lspf2f_create_tuned(const lspf2f_config *cfg, const char *tune, lspf2f_handl
         else if (k == "fullk16_min_frames") P.fullk16_min_frames = v;
         else if (k == "wino_prio") P.wino_prio = v;
         else if (k == "prefetch") h->prefetch = v != 0;
-        else if (k == "tail_prefetch") h->tail_prefetch = v;
-        else if (k == "tail_prefetch_at") h->tail_prefetch_at = v;
-        else if (k == "tail_prefetch_wgs") h->tail_prefetch_wgs = v;
-        else if (k == "tail_prefetch_mb") h->tail_prefetch_mb = v;
         else if (k == "smallm_dma") h->smallm_dma = v != 0;
         else if (k == "smallm_kb") P.smallm_kb = v;
         else if (k == "in_small_regs") h->in_small_regs = v != 0;
@@ -794,43 +783,12 @@ int lspf2f_forward_ex(lspf2f_handle *h, const float *feat_dev, const float *cand
         if (h->graphs.size() < kMaxCachedGraphs) h->graphs.emplace_back();
         g = &h->graphs[h->next_victim++ % h->graphs.size()];
         g->reset();
-        // tail_prefetch: the byte range of the blob the <= 16x16 levels read (the forms this batch's plan takes), walked by a side branch of the graph
-        const char *tp_lo = nullptr, *tp_hi = nullptr;
-        if (h->tail_prefetch) {
-            if (!h->side_stream && hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking) != hipSuccess) return fail(LSPF2F_ERR_HIP, "tail_prefetch: side stream");
-            if (!h->ev_fork && hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess) return fail(LSPF2F_ERR_HIP, "tail_prefetch: event");
-            if (!h->ev_join && hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) return fail(LSPF2F_ERR_HIP, "tail_prefetch: event");
-            for (const auto &l : h->plan.layers) {
-                if (l.kind != kIgemm || l.ho > 16) continue;
-                const size_t wb = (size_t)(l.up4 ? 16 : 9) * l.cin * l.cout * h->plan.elt();
-                const bool own = l.route == kRouteFullK || l.route == kRouteFullK16 || l.route == kRouteBand;      // (the other routes: their rows, when the blob carries them)
-                const int64_t off = l.form_off[own ? route_form(l) : kFormRows];
-                if (off < 0) continue;
-                const char *lo = h->blob + off, *hi = lo + wb;
-                if (!tp_lo || lo < tp_lo) tp_lo = lo;
-                if (!tp_hi || hi > tp_hi) tp_hi = hi;
-            }
-            if (tp_lo && h->tail_prefetch_mb > 0 && (size_t)(tp_hi - tp_lo) > ((size_t)h->tail_prefetch_mb << 20)) tp_hi = tp_lo + ((size_t)h->tail_prefetch_mb << 20);
-        }
         hipError_t e = hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal);
         if (e != hipSuccess) return hipfail(e, "hipStreamBeginCapture");
-        bool forked = false;
-        int li = 0;
         for (const auto &l : h->plan.layers) {
-            if (tp_lo && !forked && li >= h->tail_prefetch_at) {
-                e = hipEventRecord(h->ev_fork, h->cap_stream);
-                if (e == hipSuccess) e = hipStreamWaitEvent(h->side_stream, h->ev_fork, 0);
-                if (e == hipSuccess) e = launch_touch_range(tp_lo, (size_t)(tp_hi - tp_lo) & ~(size_t)15, h->tail_prefetch, h->tail_prefetch_wgs,
-                                                            reinterpret_cast<unsigned *>(h->ws + h->plan.counters_offset()), h->side_stream);
-                if (e == hipSuccess) e = hipEventRecord(h->ev_join, h->side_stream);
-                if (e != hipSuccess) { rc = hipfail(e, "tail_prefetch fork"); break; }
-                forked = true;
-            }
             rc = run_layer(h, l, feat_dev, cand_dev, cand_batch, out_dev, out_u8_dev, batch, h->cap_stream);
             if (rc) break;
-            ++li;
         }
-        if (forked) (void)hipStreamWaitEvent(h->cap_stream, h->ev_join, 0);      // the branch joins at the end: it never holds a layer up
         e = hipStreamEndCapture(h->cap_stream, &g->graph);
         if (rc) { g->reset(); return rc; }
         if (e != hipSuccess) { g->reset(); return hipfail(e, "hipStreamEndCapture"); }
@@ -990,8 +948,8 @@ size_t lspf2f_conv3x3_scratch_bytes(int batch, int hs, int ws, int c0, int c1, i
         if (sp == 1) return 0;
         return (size_t)sp * batch * hs * ws * cout * sizeof(float) + (size_t)batch * (hs / 16) * (ws / 32) * (cout / 32) * sizeof(unsigned);
     }
-    if ((tile_m == 4001 || tile_m == 4002 || tile_m == 4003 || tile_m == 4004) && k_group == -1) {      // Winograd kernel: slabs + one arrival counter per (tile-block, channel group)
-        if (tile_m == 4003 || tile_m == 4004) tile_m = 4001;         // (the register forms of nb = 1)
+    if ((tile_m == 4001 || tile_m == 4002 || tile_m == 4003) && k_group == -1) {      // Winograd kernel: slabs + one arrival counter per (tile-block, channel group)
+        if (tile_m == 4003) tile_m = 4001;         // (the register form of nb = 1)
         const int sp = split_k > 0 ? split_k : 1;
         if (sp == 1) return 0;
         return (size_t)sp * batch * hs * ws * cout * sizeof(float) + (size_t)batch * (hs / 8) * (ws / 16) * (cout / (32 * (tile_m - 4000))) * sizeof(unsigned);
@@ -1039,7 +997,7 @@ static int conv3x3_run(const void *src0, const void *src1, const void *w_packed,
     const int ktc = dtype ? 64 : 32;
     if (!src0 || !w_packed || !out) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "null argument");
     if (hs != ws) return fail(LSPF2F_ERR_UNSUPPORTED, "square tensors only");
-    const bool wino_tile = (tile_m == 4001 || tile_m == 4002 || tile_m == 4003 || tile_m == 4004 || tile_m == 5001 || tile_m == 5002 || tile_m == 6001) && k_group == -1;     // its K-step is 8 channels, checked by wino_supported()
+    const bool wino_tile = (tile_m == 4001 || tile_m == 4002 || tile_m == 4003 || tile_m == 5001 || tile_m == 5002 || tile_m == 6001) && k_group == -1;     // its K-step is 8 channels, checked by wino_supported()
     if (!wino_tile && ((c0 % ktc) || (c1 % ktc) || c0 <= 0 || c1 < 0 || (c1 > 0 && !src1)))
         return fail(LSPF2F_ERR_UNSUPPORTED, "channel counts must be multiples of 32 (fp32) / 64 (bf16, fp16)");
     if (cout % 4) return fail(LSPF2F_ERR_UNSUPPORTED, "cout must be a multiple of 4");
@@ -1131,8 +1089,8 @@ static int conv3x3_run(const void *src0, const void *src1, const void *w_packed,
             if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (wino4) launch");
             return LSPF2F_OK;
         }
-        if ((tile_m == 4001 || tile_m == 4002 || tile_m == 4003 || tile_m == 4004) && k_group == -1) {   // 4000 + nb: the Winograd kernel, w_packed in its fragment order; split_k = K splits (0: 1)
-            const int ureg = tile_m == 4003 ? 1 : tile_m == 4004 ? 2 : 0;      // 4003: nb = 1 with the U fragments in registers (the form the plans take; 4004: four register sets), 4001: through LDS
+        if ((tile_m == 4001 || tile_m == 4002 || tile_m == 4003) && k_group == -1) {   // 4000 + nb: the Winograd kernel, w_packed in its fragment order; split_k = K splits (0: 1)
+            const int ureg = tile_m == 4003 ? 1 : 0;      // 4003: nb = 1 with the U fragments in registers (the form the plans take), 4001: through LDS
             if (ureg) tile_m = 4001;
             const int sp = split_k > 0 ? split_k : 1;
             const size_t slab = sp > 1 ? (size_t)sp * batch * hs * ws * cout * sizeof(float) : 0;
@@ -1435,78 +1393,5 @@ int lspf2f_conv3x3_instnorm(const void *src0, const void *src1, const void *w_pa
     return LSPF2F_OK;
 }
 
-
-// scratch of lspf2f_wino_chain: [split-K slabs][one arrival counter per (tile-block, channel group)][(nlayers - 1) x tile-blocks gate counters][1 give-up word]
-static void wino_chain_scratch_layout(int nlayers, int batch, int hs, int c, int sp, size_t *slab, size_t *ncnt, size_t *narr)
-{
-    *slab = sp > 1 ? (size_t)sp * batch * hs * hs * c * sizeof(float) : 0;
-    *ncnt = sp > 1 ? (size_t)batch * (hs / 8) * (hs / 16) * (c / 32) : 0;
-    *narr = (size_t)(nlayers > 1 ? nlayers - 1 : 0) * batch * (hs / 8) * (hs / 16) * kWinoArriveStride;
-}
-
-size_t lspf2f_wino_chain_scratch_bytes(int nlayers, int batch, int hs, int c, int split_k)
-{
-    if (nlayers < 1 || batch < 1 || hs < 16 || c < 32) return 0;
-    size_t slab, ncnt, narr;
-    wino_chain_scratch_layout(nlayers, batch, hs, c, split_k > 0 ? split_k : 1, &slab, &ncnt, &narr);
-    return slab + (ncnt + narr + 1) * sizeof(unsigned);
-}
-
-int lspf2f_wino_chain(int nlayers, const float *const *src, const float *const *u_packed, const float *const *scale, const float *const *shift,
-                      const float *const *residual, float *const *out, const int *relu, int batch, int hs, int c, int split_k, int mode,
-                      void *scratch, size_t scratch_bytes, void *hip_stream)
-{
-    if (nlayers < 1 || nlayers > kWinoChainMax) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "wino_chain: 1..4 layers");
-    if (!src || !u_packed || !scale || !shift || !residual || !out || !relu) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "null argument");
-    if (mode < 0 || mode > 4) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "wino_chain: mode 0 (one launch per layer), 1 (one launch), 2 (one one-layer chain launch per layer), 3 (one launch, sc1 loads), 4 (one launch, plain loads and NO acquire: measurements only)");
-    const int sp = split_k > 0 ? split_k : 1;
-    size_t slab, ncnt, narr;
-    wino_chain_scratch_layout(nlayers, batch, hs, c, sp, &slab, &ncnt, &narr);
-    if (!scratch || scratch_bytes < slab + (ncnt + narr + 1) * sizeof(unsigned)) return fail(LSPF2F_ERR_STATE, "wino_chain: scratch missing or too small (lspf2f_wino_chain_scratch_bytes)");
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    WinoParams q{};
-    q.B = batch; q.H = hs; q.W = hs; q.C = c; q.N = c; q.splits = sp; q.ureg = 1; q.out_wt = 1; q.prio = 1;
-    if (sp > 1) {
-        q.partial = static_cast<float *>(scratch);
-        q.tile_cnt = reinterpret_cast<unsigned *>(static_cast<char *>(scratch) + slab);
-    }
-    unsigned *arrive = reinterpret_cast<unsigned *>(static_cast<char *>(scratch) + slab) + ncnt;
-    if (!wino_supported(q, 1)) return fail(LSPF2F_ERR_UNSUPPORTED, "the Winograd kernel does not support this shape");
-    hipError_t e = hipSuccess;
-    if (mode == 0) {
-        for (int k = 0; k < nlayers && e == hipSuccess; ++k) {
-            WinoParams p = q;
-            p.src = src[k]; p.u = u_packed[k]; p.scale = scale[k]; p.shift = shift[k]; p.residual = residual[k]; p.out = out[k]; p.relu = relu[k];
-            e = launch_wino(p, 1, s);
-        }
-    } else {
-        WinoChainParams pc{};
-        pc.c = q;
-        pc.arrive = arrive; pc.fail = arrive + narr;
-#ifdef LSPF2F_WINO_STAMPS
-        {   // stamps live behind the counters when the caller's scratch has room for them: [blocks][4 waves][8]
-            const size_t used = (slab + (ncnt + narr + 1) * sizeof(unsigned) + 255) / 256 * 256;
-            const size_t blocks = (size_t)nlayers * batch * (hs / 8) * (hs / 16) * (c / 32) * sp;
-            if (scratch_bytes >= used + blocks * 4 * 8 * 8) pc.c.stamps = reinterpret_cast<unsigned long long *>(static_cast<char *>(scratch) + used);
-        }
-#endif
-        auto fill = [&](int slot, int k) {
-            WinoChainLayer &l = pc.L[slot];
-            l.src = src[k]; l.u = u_packed[k]; l.scale = scale[k]; l.shift = shift[k]; l.residual = residual[k]; l.out = out[k]; l.relu = relu[k];
-        };
-        pc.sc1_loads = mode == 3 ? 1 : mode == 4 ? 2 : 0;
-        if (mode == 1 || mode == 3 || mode == 4) {
-            pc.nlayers = nlayers;
-            for (int k = 0; k < nlayers; ++k) fill(k, k);
-            if (!wino_chain_supported(pc)) return fail(LSPF2F_ERR_UNSUPPORTED, "wino_chain: layer k must read layer k - 1's output, and no output may alias another tensor of the chain");
-            e = launch_wino_chain(pc, s);
-        } else {
-            pc.nlayers = 1;
-            for (int k = 0; k < nlayers && e == hipSuccess; ++k) { fill(0, k); e = launch_wino_chain(pc, s); }
-        }
-    }
-    if (e != hipSuccess) return hipfail(e, "lspf2f_wino_chain launch");
-    return LSPF2F_OK;
-}
 
 }  // extern "C"

@@ -123,7 +123,7 @@ struct WinoParams {
     // (0 dispatch order, 1 tile-block-major, 2 channel-group-major) instead of by operand size; copies as one block ahead of the MFMAs
     // instead of between them; the four MFMAs of an accumulator back to back instead of rotating over the accumulators
     int nopre, xcd_force, no_il, no_rot;
-    int ureg;                   // one channel block per wave: U fragments by plain loads into registers instead of LDS-DMA + ds_read (wino.hip, UR form); 2: four register sets
+    int ureg;                   // one channel block per wave: U fragments by plain loads into registers instead of LDS-DMA + ds_read (wino.hip, UR form)
     int out_wt;                 // tune key `out_wt`: the output leaves through write-through (sc1) stores (wino.hip WT instances; A-B runs)
     int prio;                   // tune key `wino_prio`: wave priority by K-loop progress (ProgressPrio, wino_common.h): 1..3 = scheme on the register form only, 4..6 = scheme 1..3 on every Winograd loop
     float *psum, *psq, *pshift; // InstanceNorm plans: per (frame, tile-block, channel) sums of (x - c), (x - c)^2 and the shift c (the tile-block's first pixel) of the
@@ -137,33 +137,6 @@ struct WinoParams {
 bool wino_supported(const WinoParams &p, int nb);
 hipError_t launch_wino(const WinoParams &p, int nb, hipStream_t s);
 
-// Round 6: 2..4 consecutive wino3x3<1> layers of ONE shape (the convs of one or two ResidualBlocks, models/networks.py:650-675) as ONE launch of
-// nlayers x (workgroups of a layer) workgroups: blockIdx / wgs = the layer.  A workgroup of layer k > 0 requests its weights, then waits on the arrival
-// counters of the <= 9 tile-blocks of layer k - 1 its raw patch reads (wino.hip, wino3x3_chain).  Same arithmetic in the same order as nlayers launches
-// of wino3x3<1>: bit-identical.  The layers must not alias each other's outputs (a buffer is written once per launch).
-static const int kWinoChainMax = 4;
-static const int kWinoArriveStride = 32;      // 32-bit words between two gate counters (one per 128-byte line)
-struct WinoChainLayer {
-    const float *src, *u, *scale, *shift, *residual;
-    float *out;
-    int relu;
-    int res_fresh;                // the residual was written by an earlier layer of THIS launch (read behind the gate, past the L1)
-};
-struct WinoChainParams {
-    WinoParams c;                 // the shared shape: B, H, W, C, N, splits, partial, tile_cnt, prio (src / u / scale / shift / residual / out / relu unused)
-    WinoChainLayer L[kWinoChainMax];
-    int nlayers;
-    unsigned *arrive;             // [nlayers - 1][ntb][kWinoArriveStride] arrival counters (word 0 of each line), zero between launches: += 1 per finished (tile-block, channel group) of layer k, then += 1 per
-                                  // workgroup of layer k + 1 that has read it; the last reader resets it
-    unsigned *fail;               // one word, |= 1 when a gate gave up (spin_limit polls): the launch then finishes with garbage instead of hanging
-    unsigned spin_limit;
-    int sc1_loads;                // A-B arm: read what the previous layer wrote with sc1 loads (past the L1) instead of one acquire at the gate + plain loads
-    // filled by launch_wino_chain
-    int wgs;                      // workgroups per layer
-    FastDiv div_wgs;
-};
-bool wino_chain_supported(const WinoChainParams &p);
-hipError_t launch_wino_chain(const WinoChainParams &p, hipStream_t s);
 void pack_wino_weights(const float *oihw, int cin, int cout, float *out);   // host: OIHW [cout][cin][3][3] -> [cout/32][4][cin/8][4][64][4]
 
 // Winograd F(4x4, 3x3) form of the same conv (wino4.hip): H % 16 == 0, W % 32 == 0, C % 8 == 0, N % 32 == 0.  A workgroup owns 4 x 8 tiles of
@@ -404,8 +377,6 @@ hipError_t launch_pixel_shuffle(const ShuffleParams &p, hipStream_t s);
 hipError_t launch_clock_probe(unsigned long long *out, unsigned duration_us, hipStream_t s);
 // dst[0 .. bytes) = src[0 .. bytes) by a kernel (16-byte aligned pointers and size); either side may be pinned host memory
 hipError_t launch_copy16(void *dst, const void *src, size_t bytes, hipStream_t s);
-// read [src, src + bytes) with `blocks` workgroups and drop it (policy 1 plain loads, 2 non-temporal): the graph side branch of tune key `tail_prefetch`
-hipError_t launch_touch_range(const void *src, size_t bytes, int policy, int blocks, unsigned *sink, hipStream_t s);
 
 // InstanceNorm2d(affine=False, eps=1e-5) after a conv, fp32 NHWC (instnorm.hip).  `x` holds the raw conv output (bias included)
 // and is normalised in place: x = relu?((x - mean[b][c]) * rstd[b][c] + residual?).

@@ -139,9 +139,6 @@ def test_winograd_kernel_instances_do_not_spill(tmp_path):
         if "wino4_3x3" in name:            # one workgroup per CU by design (two ring slots of 56 KB): 400 registers, no scratch
             assert scratch == 0 and occ == 1, (name, scratch, occ)
             continue
-        if "wino3x3_chain" in name:        # the probe instance of round 6 (2..4 layers in one launch, nb = 1): same budget as wino3x3<1>
-            assert scratch == 0 and occ >= 2, (name, scratch, occ)
-            continue
         nb = int(re.search(r"wino(?:up)?3x3ILi(\d)E", name).group(1))
         assert scratch == 0, (name, scratch)
         assert occ >= 2, (name, occ)          # two workgroups per CU share every SIMD (nb = 2: 79 KB of LDS each; nb = 1: up to three)
@@ -352,6 +349,8 @@ def test_tune_string_reaches_the_library_and_unknown_keys_are_errors(monkeypatch
     monkeypatch.delenv("LSP_HIP_WINOUP")
     with pytest.raises(N.Lspf2fError, match="unknown key"):
         Engine("normal", tune={"no_such_switch": 1})
+    with pytest.raises(N.Lspf2fError, match="wino_ureg takes 0 .* or 1"):  # the four-register-set arm (value 2) is gone
+        Engine("normal", tune={"wino_ureg": 2})
     # switches of the Python host share the prefix and never reach the library; a typo in the environment is a warning, not a broken run
     monkeypatch.setenv("LSP_HIP_CAND_CACHE", "0")
     assert N.tune_string() == b""
@@ -417,10 +416,8 @@ def _ur_loop_model(nsteps, ns, epl):
     issue(0)
     if nsteps > 1:
         issue(1)
-    if ns == 4 and nsteps > 2:
-        issue(2)
     q.extend([("e", -1)] * epl)                                    # epilogue operands, requested behind the first steps
-    wait(12 + epl if ns == 4 and nsteps > 2 else 6 + epl if nsteps > 1 else epl)
+    wait(6 + epl if nsteps > 1 else epl)
     ahead = ns - 1
     t = 0
     while t < nsteps:
@@ -434,10 +431,7 @@ def _ur_loop_model(nsteps, ns, epl):
             log.append((cur, len(inflight), s, (s + ahead) % ns if will_issue else None))
             if will_issue:
                 issue(cur + ahead)
-            if ns == 3:
-                wait(6 if will_issue else 0)
-            else:
-                wait(12 if will_issue else 6 if cur + 2 < nsteps else 0)
+            wait(6 if will_issue else 0)
             # after the wait (and the barrier): step cur + 1 must have landed
             assert not [x for x in q if x == ("s", cur + 1)], (nsteps, ns, cur, q)
         t += ns
@@ -445,10 +439,10 @@ def _ur_loop_model(nsteps, ns, epl):
     return log
 
 
-def test_register_form_wait_protocol_for_three_and_four_sets():
+def test_register_form_wait_protocol_for_three_sets():
     """every step's operands have landed when its MFMAs start, the set it refills is the one read one step earlier, nothing is left in flight at the end -- for the
-    shipped three-set form and the four-set A-B arm (tile 4004 / wino_ureg=2), any step count (split-K slices of 2..64 steps), any number of epilogue loads"""
-    for ns in (3, 4):
+    three register sets of the kernel, any step count (split-K slices of 2..64 steps), any number of epilogue loads"""
+    for ns in (3,):
         for nsteps in range(1, 40):
             for epl in (0, 6, 12):
                 log = _ur_loop_model(nsteps, ns, epl)
