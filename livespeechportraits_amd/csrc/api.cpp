@@ -430,6 +430,107 @@ static hipError_t in_standalone(InstNormParams &q, bool small, float *st, size_t
     return r == hipSuccess ? in_finalize_apply(q, s) : r;
 }
 
+// ---- a body layer's kernel arguments, stated once per kernel family.  Both callers know a ConvIO and a LayerDesc: run_layer (a plan's layer: workspace tensors,
+// blob offsets) and conv3x3_run (lspf2f_conv3x3's arguments; conv3x3_layer() + the decoded tile code).  The builders fill the pointers and the shape; what only one
+// caller knows -- the plan's tune knobs, the tool builds' stamps, the statistics pointers of an InstanceNorm behind the conv -- that caller sets on the result ----
+struct ConvIO {
+    const void *src0, *src1, *w;          // src1 == nullptr when the layer has one source
+    const float *scale, *shift;
+    const void *residual;
+    void *out;
+    float *partial;                       // split-K slabs and, behind them, the arrival counters of an in-launch combine (bound when the layer's splits > 1;
+    unsigned *tile_cnt;                   //   the implicit GEMM binds its own counters: plans only)
+    int batch, dtype, relu;
+    int kernel_order;                     // w is in the kernel's own (fragment / tile-blocked) order -- the plans' blob always -- not rows [cout][9][cin]
+};
+static const float *f32(const void *p) { return static_cast<const float *>(p); }
+
+static SmallMParams smallm_params(const ConvIO &io, const LayerDesc &l)
+{
+    SmallMParams p{};
+    p.src = io.src0; p.w = io.w; p.scale = io.scale; p.shift = io.shift; p.residual = io.residual; p.out = io.out;
+    p.B = io.batch; p.Hs = p.Ws = l.hs; p.Ho = p.Wo = l.ho; p.Cin = l.cin; p.Cout = l.cout;
+    p.stride = l.stride; p.up = l.up; p.relu = io.relu; p.M = io.batch * l.ho * l.ho; p.dtype = io.dtype;
+    return p;
+}
+static WinoUpParams winoup_params(const ConvIO &io, const LayerDesc &l)
+{
+    WinoUpParams p{};
+    p.src0 = f32(io.src0); p.src1 = f32(io.src1); p.u = f32(io.w); p.scale = io.scale; p.shift = io.shift; p.out = static_cast<float *>(io.out);
+    p.B = io.batch; p.Hs = p.Ws = l.hs; p.C0 = l.c0; p.C1 = l.c1; p.N = l.cout; p.relu = io.relu; p.splits = l.splits;
+    if (l.splits > 1) { p.partial = io.partial; p.tile_cnt = io.tile_cnt; }      // the counters must be zero on entry; every launch leaves them zero
+    return p;
+}
+static WinoParams wino_params(const ConvIO &io, const LayerDesc &l)          // wino3x3 and wino4_3x3
+{
+    WinoParams p{};
+    p.src = f32(io.src0); p.u = f32(io.w); p.scale = io.scale; p.shift = io.shift; p.residual = f32(io.residual); p.out = static_cast<float *>(io.out);
+    p.B = io.batch; p.H = p.W = l.ho; p.C = l.cin; p.N = l.cout; p.relu = io.relu; p.splits = l.splits;
+    if (l.splits > 1) { p.partial = io.partial; p.tile_cnt = io.tile_cnt; }
+    return p;
+}
+static RowUpParams rowup_params(const ConvIO &io, const LayerDesc &l)
+{
+    RowUpParams p{};
+    p.src0 = io.src0; p.src1 = io.src1; p.w = io.w; p.scale = io.scale; p.shift = io.shift; p.out = io.out;
+    p.B = io.batch; p.H = p.W = l.hs; p.R = l.route_arg; p.relu = io.relu; p.dtype = io.dtype;
+    return p;
+}
+static PatchConvParams patch_params(const ConvIO &io, const LayerDesc &l)    // conv3x3_patch16 (one source) and conv3x3_patchup16 (H x W = the LOW-res extent)
+{
+    PatchConvParams p{};
+    p.src = io.src0; p.src1 = io.src1; p.w = io.w; p.scale = io.scale; p.shift = io.shift; p.residual = io.residual; p.out = io.out;
+    p.B = io.batch; p.H = p.W = l.up4 ? l.hs : l.ho; p.C = l.c0; p.C1 = l.c1; p.Cout = l.cout; p.relu = io.relu; p.dtype = io.dtype;
+    return p;
+}
+static BandConvParams band_params(const ConvIO &io, const LayerDesc &l)
+{
+    BandConvParams p{};
+    p.src = io.src0; p.w = io.w; p.scale = io.scale; p.shift = io.shift; p.residual = io.residual; p.out = io.out;
+    p.B = io.batch; p.W = l.ho; p.Cout = l.cout; p.relu = io.relu; p.dtype = io.dtype;
+    return p;
+}
+static RowConvParams rowconv_params(const ConvIO &io, const LayerDesc &l)
+{
+    RowConvParams p{};
+    p.src = io.src0; p.w = io.w; p.scale = io.scale; p.shift = io.shift; p.residual = io.residual; p.out = io.out;
+    p.B = io.batch; p.H = p.W = l.ho; p.C = l.c0; p.R = l.route_arg; p.relu = io.relu; p.dtype = io.dtype; p.wfrag = io.kernel_order;
+    return p;
+}
+static FullK16Params fullk16_params(const ConvIO &io, const LayerDesc &l)
+{
+    FullK16Params p{};
+    p.src0 = io.src0; p.src1 = io.src1; p.w = io.w; p.scale = io.scale; p.shift = io.shift; p.residual = io.residual; p.out = io.out;
+    p.B = io.batch; p.Hs = p.Ws = l.hs; p.Ho = p.Wo = l.ho; p.C0 = l.c0; p.C1 = l.c1; p.Cout = l.cout;
+    p.up = l.up; p.relu = io.relu; p.stride = l.stride; p.dtype = io.dtype; p.wtile = io.kernel_order;
+    return p;
+}
+static FullKParams fullk_params(const ConvIO &io, const LayerDesc &l)
+{
+    FullKParams p{};
+    p.src0 = f32(io.src0); p.src1 = f32(io.src1); p.w = f32(io.w); p.scale = io.scale; p.shift = io.shift; p.residual = f32(io.residual); p.out = static_cast<float *>(io.out);
+    p.B = io.batch; p.Hs = p.Ws = l.hs; p.Ho = p.Wo = l.ho; p.C0 = l.c0; p.C1 = l.c1; p.Cout = l.cout;
+    p.up = l.up; p.relu = io.relu; p.stride = l.stride; p.wtile = io.kernel_order;
+    if (l.splits == 2) {          // K in two halves, combined in the launch; a single source is then read (and its weights packed) as two half-sources: route_form
+        p.split = 2; p.partial = io.partial; p.tile_cnt = io.tile_cnt;
+    }
+    return p;
+}
+static IgemmParams igemm_params(const ConvIO &io, const LayerDesc &l)
+{
+    IgemmParams p{};
+    p.src0 = io.src0; p.src1 = io.src1; p.w = io.w; p.scale = io.scale; p.shift = io.shift; p.residual = io.residual; p.out = io.out;
+    p.partial = io.partial;
+    p.B = io.batch; p.Hs = p.Ws = l.hs; p.Ho = p.Wo = l.ho; p.C0 = l.c0; p.C1 = l.c1; p.Cin = l.cin; p.Cout = l.cout;
+    p.stride = l.stride; p.up = l.up; p.up4 = l.up4; p.relu = io.relu; p.dtype = io.dtype;
+    p.Mout = io.batch * l.ho * l.ho;
+    p.M = l.up4 ? io.batch * l.hs * l.hs : p.Mout;
+    p.ktiles_total = (l.up4 ? 4 : 9) * l.cin / (io.dtype ? 64 : 32);
+    p.splits = l.splits;
+    p.ktiles_per_split = (p.ktiles_total + l.splits - 1) / l.splits;
+    return p;
+}
+
 static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, const float *cand, int cand_batch,
                      float *out, unsigned char *out_u8, int batch, hipStream_t s)
 {
@@ -466,8 +567,14 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
         const hipError_t r = launch();
         return r == hipSuccess ? in_finalize_apply(q, s) : r;
     };
-    // the blob address of the form this layer's route reads
-    const float *const w = l.kind == kIgemm ? bptr(l.form_off[route_form(l)]) : nullptr;
+    // A body layer's tensors, the blob address of the form its route reads, and the plan's split-K scratch.  InstanceNorm plans: the conv writes its raw output (+ bias);
+    // the residual add and the ReLU move behind the normalisation -- except in the tiny-M kernel, whose workgroup holds every pixel of its channels and normalises in its
+    // own epilogue (`in_smallm_fused`)
+    const bool in_fused = l.inorm && l.route == kRouteSmallM && P.in_smallm_fused;
+    const bool raw = l.inorm && !in_fused;
+    const ConvIO io{tptr(l.src0), tptr(l.src1), l.kind == kIgemm ? bptr(l.form_off[route_form(l)]) : nullptr, bptr(l.scale_off), bptr(l.shift_off),
+                    raw ? nullptr : tptr(l.res), tptr(l.out), reinterpret_cast<float *>(h->ws + P.partial_offset),
+                    reinterpret_cast<unsigned *>(h->ws + P.counters_offset()), batch, P.dtype, raw ? 0 : (int)l.relu, 1};
     const bool main_part = (h->timing_part & 1) != 0;      // lspf2f_subset_timed may leave the main kernel out
     if (l.kind == kFirstConv) {
         FirstConvParams p{};
@@ -540,12 +647,7 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
         e = launch_last_conv(p, s);
     } else switch (l.route) {
     case kRouteSmallM: {
-        SmallMParams p{};
-        p.src = tptr(l.src0); p.w = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
-        const bool in_fused = l.inorm && P.in_smallm_fused;      // InstanceNorm plans: the workgroup holds every pixel of its channels -> normalisation in the epilogue
-        p.residual = (l.inorm && !in_fused) ? nullptr : tptr(l.res); p.out = tptr(l.out);
-        p.B = batch; p.Hs = l.hs; p.Ws = l.hs; p.Ho = l.ho; p.Wo = l.ho; p.Cin = l.cin; p.Cout = l.cout;
-        p.stride = l.stride; p.up = l.up; p.relu = (l.inorm && !in_fused) ? 0 : l.relu; p.M = batch * l.ho * l.ho; p.dtype = P.dtype;
+        SmallMParams p = smallm_params(io, l);
         p.in_fused = in_fused ? 1 : 0;
         p.stage_regs = h->smallm_dma ? 0 : 1;
         if (h->prefetch && P.dtype == 0 && !l.inorm) {
@@ -562,28 +664,14 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
         break;
     }
     case kRouteWinoUp: {
-        WinoUpParams p{};
-        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.u = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
-        p.out = tptr(l.out);
-        p.B = batch; p.Hs = l.hs; p.Ws = l.hs; p.C0 = l.c0; p.C1 = l.c1; p.N = l.cout; p.relu = l.inorm ? 0 : l.relu; p.splits = l.splits;
+        WinoUpParams p = winoup_params(io, l);
         p.out_wt = P.out_wt; p.prio = P.wino_prio;
-        if (l.splits > 1) {
-            p.partial = reinterpret_cast<float *>(h->ws + P.partial_offset);
-            p.tile_cnt = reinterpret_cast<unsigned *>(h->ws + P.counters_offset());
-        }
         e = wino_with_in(p, [&] { return main_part ? launch_winoup(p, l.route_arg, s) : hipSuccess; });
         break;
     }
     case kRouteWino4:
     case kRouteWino: {
-        WinoParams p{};
-        p.src = tptr(l.src0); p.u = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
-        p.residual = l.inorm ? nullptr : tptr(l.res); p.out = tptr(l.out);
-        p.B = batch; p.H = l.ho; p.W = l.ho; p.C = l.cin; p.N = l.cout; p.relu = l.inorm ? 0 : l.relu; p.splits = l.splits;
-        if (l.splits > 1) {
-            p.partial = reinterpret_cast<float *>(h->ws + P.partial_offset);
-            p.tile_cnt = reinterpret_cast<unsigned *>(h->ws + P.counters_offset());
-        }
+        WinoParams p = wino_params(io, l);
         if (l.route == kRouteWino4) {          // (never kInWino: F(4x4,3x3) leaves no epilogue sums)
             e = wino_with_in(p, [&] { return main_part ? launch_wino4(p, s) : hipSuccess; });
             break;
@@ -592,91 +680,25 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
         e = wino_with_in(p, [&] { return main_part ? launch_wino(p, l.route_arg, s) : hipSuccess; });
         break;
     }
-    case kRouteRowUp: {
-        RowUpParams p{};
-        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
-        p.out = tptr(l.out);
-        p.B = batch; p.H = l.hs; p.W = l.hs; p.R = l.route_arg; p.relu = l.relu; p.dtype = P.dtype;
-        e = launch_rowup(p, s);
-        break;
-    }
-    case kRoutePatchUp16: {
-        PatchConvParams p{};
-        p.src = tptr(l.src0); p.src1 = tptr(l.src1); p.w = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
-        p.residual = tptr(l.res); p.out = tptr(l.out);
-        p.B = batch; p.H = l.hs; p.W = l.hs; p.C = l.c0; p.C1 = l.c1; p.Cout = l.cout; p.relu = l.relu; p.dtype = P.dtype;
-        e = launch_patchup16(p, l.route_arg, l.bn, s);
-        break;
-    }
+    case kRouteRowUp: e = launch_rowup(rowup_params(io, l), s); break;
+    case kRoutePatchUp16: e = launch_patchup16(patch_params(io, l), l.route_arg, l.bn, s); break;
     case kRoutePatch16: {
-        PatchConvParams p{};
-        p.src = tptr(l.src0); p.w = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
-        p.residual = tptr(l.res); p.out = tptr(l.out);
-        p.B = batch; p.H = l.ho; p.W = l.ho; p.C = l.c0; p.Cout = l.cout; p.relu = l.relu; p.dtype = P.dtype;
+        PatchConvParams p = patch_params(io, l);
         p.deep = P.patch16_deep;
         e = launch_patch16(p, l.route_arg, l.bn, s);
         break;
     }
-    case kRouteBand: {
-        BandConvParams p{};
-        p.src = tptr(l.src0); p.w = w; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
-        p.residual = tptr(l.res); p.out = tptr(l.out);
-        p.B = batch; p.W = l.ho; p.Cout = l.cout; p.relu = l.relu; p.dtype = P.dtype;
-        e = launch_bandconv(p, s);
-        break;
-    }
-    case kRouteRowConv: {
-        RowConvParams p{};
-        p.src = tptr(l.src0); p.w = w; p.wfrag = 1; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
-        p.residual = tptr(l.res); p.out = tptr(l.out);
-        p.B = batch; p.H = l.ho; p.W = l.ho; p.C = l.c0; p.R = l.route_arg; p.relu = l.relu; p.dtype = P.dtype;
-        e = launch_rowconv(p, s);
-        break;
-    }
-    case kRouteFullK16: {
-        FullK16Params p{};
-        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = w; p.wtile = 1; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
-        p.residual = tptr(l.res); p.out = tptr(l.out);
-        p.B = batch; p.Hs = l.hs; p.Ws = l.hs; p.Ho = l.ho; p.Wo = l.ho; p.C0 = l.c0; p.C1 = l.c1; p.Cout = l.cout;
-        p.up = l.up; p.relu = l.relu; p.stride = l.stride; p.dtype = P.dtype;
-        e = launch_fullk16(p, l.route_arg, s);
-        break;
-    }
-    case kRouteFullK: {
-        FullKParams p{};
-        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = w; p.wtile = 1; p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
-        p.residual = l.inorm ? nullptr : tptr(l.res); p.out = tptr(l.out);
-        p.B = batch; p.Hs = l.hs; p.Ws = l.hs; p.Ho = l.ho; p.Wo = l.ho; p.C0 = l.c0; p.C1 = l.c1; p.Cout = l.cout;
-        p.up = l.up; p.relu = l.inorm ? 0 : l.relu; p.stride = l.stride;
-        if (l.splits == 2) {                       // K in two halves, combined in the launch (a single source read as two half-sources: route_form)
-            p.split = 2;
-            p.partial = reinterpret_cast<float *>(h->ws + P.partial_offset);
-            p.tile_cnt = reinterpret_cast<unsigned *>(h->ws + P.counters_offset());
-        }
-        e = launch_fullk(p, l.route_arg, s);
+    case kRouteBand: e = launch_bandconv(band_params(io, l), s); break;
+    case kRouteRowConv: e = launch_rowconv(rowconv_params(io, l), s); break;
+    case kRouteFullK16: e = launch_fullk16(fullk16_params(io, l), l.route_arg, s); break;
+    case kRouteFullK:
+        e = launch_fullk(fullk_params(io, l), l.route_arg, s);
         if (l.inorm) e = in_after_complete_output(e, true);          // InstanceNorm plans: H*W <= 256 here, the one-launch statistics route
         break;
-    }
     case kRouteIgemm: {
-        IgemmParams p{};
-        p.src0 = tptr(l.src0); p.src1 = tptr(l.src1); p.w = w;
-        p.scale = bptr(l.scale_off); p.shift = bptr(l.shift_off);
-        p.residual = tptr(l.res); p.out = tptr(l.out);
-        p.partial = reinterpret_cast<float *>(h->ws + P.partial_offset);
-        p.B = batch; p.Hs = l.hs; p.Ws = l.hs; p.Ho = l.ho; p.Wo = l.ho;
-        p.C0 = l.c0; p.C1 = l.c1; p.Cin = l.cin; p.Cout = l.cout;
-        p.stride = l.stride; p.up = l.up; p.relu = l.relu;
-        p.up4 = l.up4;
-        p.Mout = batch * l.ho * l.ho;
-        p.M = l.up4 ? batch * l.hs * l.hs : p.Mout;
-        p.dtype = P.dtype;
-        p.ktiles_total = (l.up4 ? 4 : 9) * l.cin / P.ktile_channels();
-        p.splits = l.splits;
-        p.ktiles_per_split = (p.ktiles_total + l.splits - 1) / l.splits;
+        IgemmParams p = igemm_params(io, l);
         if (l.inorm) {
-            // InstanceNorm follows: the conv writes its raw output (+ bias); residual add and ReLU move behind the normalisation
             InstNormParams q = in_of_output();
-            p.residual = nullptr; p.relu = 0;
             if (l.in_route == kInFused) {
                 in_bind_stats(q, st, slab);
                 in_groups_igemm(q, l.bm, l.up4, l.up4 ? l.hs * l.hs : l.ho * l.ho);      // one group per wave
@@ -693,8 +715,8 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
         } else {
             const bool fused = l.fused_splitk && h->fuse_splitk;
             if (fused) {
-                p.tile_cnt = reinterpret_cast<unsigned *>(h->ws + P.counters_offset());
-                p.slab_bytes = (size_t)l.splits * p.Mout * l.cout * sizeof(float);
+                p.tile_cnt = io.tile_cnt;
+                p.slab_bytes = igemm_scratch(p.Mout, l.cout, l.splits).slab_bytes;
             }
             p.xcd_force = P.igemm_xcd + 1;
             if (main_part) e = launch_igemm(p, l.bm, l.bn, l.group, s);
@@ -934,55 +956,78 @@ int lspf2f_forward_timed(lspf2f_handle *h, const float *feat_dev, const float *c
     return rc;
 }
 
-size_t lspf2f_conv3x3_scratch_bytes(int batch, int hs, int ws, int c0, int c1, int cout, int stride, int upsample,
-                                    int tile_m, int tile_n, int split_k, int k_group, int dtype)
+// ---- lspf2f_conv3x3: one conv on the kernel its tile code names (include/lspf2f.h) ----
+// The code, decoded once for lspf2f_conv3x3_scratch_bytes, conv3x3_run and conv3x3_in_shape.  Precedence = the order of the lines of decode_tile().
+struct TileCode {
+    ConvRoute route;      // the kernel the code forces; kRouteIgemm = the implicit GEMM on tile_m x tile_n tiles (0 x 0: the planner's tiling)
+    int arg;              // that kernel's LayerDesc::route_arg
+    int bn;               // conv3x3_patch16: channels per workgroup = tile_n, with 65 = 64 in its FIRST form
+    bool planner;         // tile 0 x 0 with split_k 0: the planner's rules may also give the call to the tiny-M or the full-K kernel
+    bool kernel_order;    // k_group -1: w_packed is in the kernel's own (fragment / tile-blocked) order, not rows [cout][9][cin]
+    bool k8;              // a Winograd code: the K step is 8 channels (checked by *_supported()), not a K-tile of 32 | 64
+};
+static TileCode decode_tile(int tile_m, int tile_n, int split_k, int k_group, int dtype)
 {
-    const int ktc = dtype ? 64 : 32;
-    if ((tile_m == 5001 || tile_m == 5002) && k_group == -1) {      // up-conv Winograd kernel: slabs at OUTPUT resolution + arrival counters
-        const int sp = split_k > 0 ? split_k : 1;
-        if (sp == 1) return 0;
-        return (size_t)sp * batch * 4 * hs * hs * cout * sizeof(float) + (size_t)batch * (hs / 4) * (hs / 8) * (cout / (32 * (tile_m - 5000))) * sizeof(unsigned);
-    }
-    if (tile_m == 6001 && k_group == -1) {                           // Winograd F(4x4, 3x3) kernel: slabs + one arrival counter per (tile-block of 16 x 32 pixels, 32 channels)
-        const int sp = split_k > 0 ? split_k : 1;
-        if (sp == 1) return 0;
-        return (size_t)sp * batch * hs * ws * cout * sizeof(float) + (size_t)batch * (hs / 16) * (ws / 32) * (cout / 32) * sizeof(unsigned);
-    }
-    if ((tile_m == 4001 || tile_m == 4002 || tile_m == 4003) && k_group == -1) {      // Winograd kernel: slabs + one arrival counter per (tile-block, channel group)
-        if (tile_m == 4003) tile_m = 4001;         // (the register form of nb = 1)
-        const int sp = split_k > 0 ? split_k : 1;
-        if (sp == 1) return 0;
-        return (size_t)sp * batch * hs * ws * cout * sizeof(float) + (size_t)batch * (hs / 8) * (ws / 16) * (cout / (32 * (tile_m - 4000))) * sizeof(unsigned);
-    }
-    if (tile_m == 7064 || tile_m == 7032 || tile_m == 7164 || tile_m == 7132 || tile_m == 7116) return 0;      // patch-staged 16-bit kernels: no scratch
-    (void)ws;
-    const int ho = upsample ? 2 * hs : (stride == 2 ? (hs + 1) / 2 : hs);
-    if ((tile_m == 16 || tile_m == 32) && tile_n == 16 && split_k == 2) {      // K-split full-K kernel: two partial tiles per tile + arrival counters
-        const size_t pbk = tile_m / 16;
-        return (size_t)batch * (ho * ho / (16 * pbk)) * (cout / 16) * (2 * pbk * 256 * sizeof(float) + sizeof(unsigned));
-    }
-    const int Mout = batch * ho * ho;
-    const bool up4 = upsample == 2;
-    const int M = up4 ? batch * hs * hs : Mout;
-    int bm = tile_m, bn = tile_n, sp = split_k;
-    if (!bm || !bn || !sp) {
-        int a, b, c, g;
-        const int kt = k_group == -4 ? 16 * (c0 / 4) / ktc : (up4 ? 4 : 9) * (c0 + c1) / ktc;      // -4: the 16 live (tap, quarter) pairs of a space-to-depth 4x4 / s2 conv
-        choose_tiling(M, cout, kt, up4 ? 4 : 1, upsample == 1, dtype, &a, &b, &c, &g);
-        if (!bm || !bn) { bm = a; bn = b; }
-        if (!sp) sp = c;
-    }
-    (void)k_group;
-    return sp > 1 ? (size_t)sp * Mout * cout * sizeof(float) : 0;
+    const bool own = k_group == -1;
+    TileCode t{kRouteIgemm, 0, tile_n == 65 ? 64 : tile_n, false, own, own && ((tile_m >= 4001 && tile_m <= 4003) || tile_m == 5001 || tile_m == 5002 || tile_m == 6001)};
+    auto is = [&t](ConvRoute r, int arg) { t.route = r; t.arg = arg; return t; };
+    if (tile_m == 1 && tile_n == 1) return is(kRouteSmallM, 1);                                    // tiny-M single-launch kernel
+    if (tile_m > 3000 && tile_n == 64 && own) return is(kRouteRowUp, tile_m - 3000);               // 3000 + R: sub-pixel up-conv row kernel, R low-res rows per strip
+    if ((tile_m == 5001 || tile_m == 5002) && own) return is(kRouteWinoUp, tile_m - 5000);         // 5000 + nb: up-conv Winograd kernel; split_k = K splits (0: 1)
+    if (tile_m == 6001 && own) return is(kRouteWino4, 1);                                          // Winograd F(4x4, 3x3), weights as pack_wino4_weights(); split_k likewise
+    if (t.k8) return is(kRouteWino, tile_m == 4002 ? 2 : 1);                                       // 4000 + nb: Winograd F(2x2, 3x3); 4003 = nb 1 with the U fragments in registers
+    if (tile_m == 7164 || tile_m == 7132 || tile_m == 7116) return is(kRoutePatchUp16, tile_m - 7100);   // 7100 + tile width: conv3x3_patchup16 (upsample 2, w_packed = [4][cout][2][2][c0 + c1])
+    if (tile_m == 7064 || tile_m == 7032) return is(kRoutePatch16, tile_m - 7000);                 // 7000 + tile width: conv3x3_patch16, tile_n = 128 | 64 | 65 channels per workgroup; igemm weight rows
+    if (tile_m == 2000 && own) return is(kRouteBand, 1);                                           // activation-stationary 16-bit kernel of the 16x16 / 8x8 levels
+    if (tile_m > 1000 && (tile_n == 64 || tile_n == 128)) return is(kRouteRowConv, tile_m - 1000); // 1000 + R: weights-stationary 16-bit kernel, tile_n channels in and out, R output rows per strip
+    if ((tile_m == 16 || tile_m == 32) && tile_n == 16) return is(dtype ? kRouteFullK16 : kRouteFullK, tile_m / 16);   // full-K single-launch kernels, tile_m / 16 pixel blocks per tile
+    t.planner = tile_m == 0 && tile_n == 0 && split_k == 0 && k_group != -4;
+    return t;
 }
 
-// the layer lspf2f_conv3x3's arguments describe, for the planner's predicates (upsample 1 = nearest x2 in front of the 9 taps, 2 = the sub-pixel form)
+// the layer lspf2f_conv3x3's arguments describe, for the planner's predicates and the builders above (upsample 1 = nearest x2 in front of the 9 taps, 2 = the sub-pixel form)
 static LayerDesc conv3x3_layer(int hs, int c0, int c1, int cout, int stride, int upsample)
 {
     LayerDesc l;
     l.hs = hs; l.ho = upsample ? 2 * hs : (stride == 2 ? (hs + 1) / 2 : hs);
     l.c0 = c0; l.c1 = c1; l.cin = c0 + c1; l.cout = cout; l.stride = stride; l.up = upsample == 1; l.up4 = upsample == 2;
     return l;
+}
+// its tiling on the implicit GEMM (bm, bn, splits, group): tile 0 x 0, split_k 0 and k_group 0 each take the planner's value.  Returns the K-tiles: k_group -4 keeps
+// the 16 live (tap, quarter) pairs of a space-to-depth 4x4 / s2 conv
+static int conv3x3_tiling(LayerDesc &l, int batch, int tile_m, int tile_n, int split_k, int k_group, int dtype)
+{
+    const int ktc = dtype ? 64 : 32, ktiles = k_group == -4 ? 16 * (l.c0 / 4) / ktc : (l.up4 ? 4 : 9) * l.cin / ktc;
+    l.bm = tile_m; l.bn = tile_n; l.splits = split_k; l.group = k_group == -4 ? 0 : k_group;
+    if (!l.bm || !l.bn || !l.splits) {
+        int bm, bn, splits, group;
+        choose_tiling(l.up4 ? batch * l.hs * l.hs : batch * l.ho * l.ho, l.cout, ktiles, l.up4 ? 4 : 1, l.up, dtype, &bm, &bn, &splits, &group);
+        if (!l.bm || !l.bn) { l.bm = bm; l.bn = bn; if (!l.group) l.group = group; }
+        if (!l.splits) l.splits = splits;
+    }
+    if (!l.group) l.group = 1;
+    return ktiles;
+}
+
+size_t lspf2f_conv3x3_scratch_bytes(int batch, int hs, int ws, int c0, int c1, int cout, int stride, int upsample,
+                                    int tile_m, int tile_n, int split_k, int k_group, int dtype)
+{
+    const TileCode t = decode_tile(tile_m, tile_n, split_k, k_group, dtype);
+    LayerDesc L = conv3x3_layer(hs, c0, c1, cout, stride, upsample);
+    const int sp = split_k > 0 ? split_k : 1;
+    switch (t.route) {
+    case kRouteWinoUp: return sp > 1 ? winoup_scratch(batch, hs, hs, cout, t.arg, sp).bytes() : 0;      // (slabs at OUTPUT resolution)
+    case kRouteWino4: return sp > 1 ? wino4_scratch(batch, hs, ws, cout, sp).bytes() : 0;
+    case kRouteWino: return sp > 1 ? wino_scratch(batch, hs, ws, cout, t.arg, sp).bytes() : 0;
+    case kRoutePatch16: case kRoutePatchUp16: return 0;
+    case kRouteFullK: case kRouteFullK16:
+        if (split_k == 2) return fullk_split_scratch(batch, L.ho, cout, t.arg).bytes();
+        break;
+    default: break;
+    }
+    // every other selection: the implicit GEMM's slabs for the K splits asked for (0: the planner's count) -- enough for whichever kernel then takes the call
+    conv3x3_tiling(L, batch, tile_m, tile_n, split_k, k_group, dtype);
+    return igemm_scratch(batch * L.ho * L.ho, cout, L.splits).bytes();
 }
 
 // lspf2f_conv3x3, and with `in` the conv of lspf2f_conv3x3_instnorm: the producer then also leaves the statistics InstanceNorm plans take from it -- per-group sums at
@@ -997,8 +1042,8 @@ static int conv3x3_run(const void *src0, const void *src1, const void *w_packed,
     const int ktc = dtype ? 64 : 32;
     if (!src0 || !w_packed || !out) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "null argument");
     if (hs != ws) return fail(LSPF2F_ERR_UNSUPPORTED, "square tensors only");
-    const bool wino_tile = (tile_m == 4001 || tile_m == 4002 || tile_m == 4003 || tile_m == 5001 || tile_m == 5002 || tile_m == 6001) && k_group == -1;     // its K-step is 8 channels, checked by wino_supported()
-    if (!wino_tile && ((c0 % ktc) || (c1 % ktc) || c0 <= 0 || c1 < 0 || (c1 > 0 && !src1)))
+    const TileCode t = decode_tile(tile_m, tile_n, split_k, k_group, dtype);
+    if (!t.k8 && ((c0 % ktc) || (c1 % ktc) || c0 <= 0 || c1 < 0 || (c1 > 0 && !src1)))
         return fail(LSPF2F_ERR_UNSUPPORTED, "channel counts must be multiples of 32 (fp32) / 64 (bf16, fp16)");
     if (cout % 4) return fail(LSPF2F_ERR_UNSUPPORTED, "cout must be a multiple of 4");
     if (stride != 1 && stride != 2) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "stride must be 1 or 2");
@@ -1012,254 +1057,130 @@ static int conv3x3_run(const void *src0, const void *src1, const void *w_packed,
         const bool gemm_tile = (tile_m == 0 && tile_n == 0) || ((tile_m == 32 || tile_m == 64 || tile_m == 128) && (tile_n == 64 || tile_n == 128));
         if (!gemm_tile) return fail(LSPF2F_ERR_UNSUPPORTED, "k_group -4 runs on the implicit GEMM only: tile 0x0 (planner's choice) or one of its tiles");
     }
-    const LayerDesc L = conv3x3_layer(hs, c0, c1, cout, stride, upsample);
-    hipError_t e = hipSuccess;
-    {
-        // tile 1x1 forces the tiny-M single-launch kernel; tile 0x0 lets the planner's rule pick it
-        SmallMParams q{};
-        q.src = src0; q.w = w_packed; q.scale = scale; q.shift = shift; q.residual = residual; q.out = out;
-        q.B = batch; q.Hs = hs; q.Ws = ws; q.Ho = upsample ? 2 * hs : (stride == 2 ? (hs + 1) / 2 : hs); q.Wo = q.Ho;
-        q.Cin = c0; q.Cout = cout; q.stride = stride; q.up = upsample == 1; q.relu = relu; q.M = batch * q.Ho * q.Wo;
-        q.dtype = dtype;
+    if (upsample < 0 || upsample > 2) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "upsample must be 0, 1 or 2");
+    LayerDesc L = conv3x3_layer(hs, c0, c1, cout, stride, upsample);
+    L.route = t.route; L.route_arg = t.arg; L.splits = split_k > 0 ? split_k : 1;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    ConvIO io{src0, c1 ? src1 : nullptr, w_packed, scale, shift, residual, out, nullptr, nullptr, batch, dtype, relu, t.kernel_order};
+    // a route's split-K scratch: bounds-checked, then bound -- the slabs, and behind them the arrival counters (zero on entry; every launch leaves them zero)
+    auto bind_scratch = [&](const SplitKScratch &k) {
+        if (!scratch || scratch_bytes < k.bytes()) return false;
+        io.partial = static_cast<float *>(scratch);
+        io.tile_cnt = reinterpret_cast<unsigned *>(static_cast<char *>(scratch) + k.slab_bytes);
+        return true;
+    };
+    auto launched = [](hipError_t e, const char *what) { return e == hipSuccess ? (int)LSPF2F_OK : hipfail(e, what); };
+    if (t.route == kRouteSmallM || t.planner) {
+        SmallMParams q = smallm_params(io, L);
         q.in_fused = in ? 1 : 0;
-        const bool want = (tile_m == 1 && tile_n == 1) || (tile_m == 0 && tile_n == 0 && split_k == 0 && k_group != -4);
-        if (want && c1 == 0 && upsample != 2 && smallm_supported(q)) {
-            e = launch_smallm(q, static_cast<hipStream_t>(hip_stream));
-            if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (tiny-M) launch");
-            return LSPF2F_OK;
-        }
-        if (tile_m == 1 && tile_n == 1) return fail(LSPF2F_ERR_UNSUPPORTED, "tiny-M kernel does not support this shape");
+        if (c1 == 0 && upsample != 2 && smallm_supported(q)) return launched(launch_smallm(q, s), "lspf2f_conv3x3 (tiny-M) launch");
+        if (!t.planner) return fail(LSPF2F_ERR_UNSUPPORTED, "tiny-M kernel does not support this shape");
     }
-    {
-        // tile (16 | 32) x 16 forces the full-K single-launch kernel; tile 0x0 + split 0 lets the planner's rule pick it
-        const int ho_ = L.ho;
-        if (tile_m > 3000 && tile_n == 64 && k_group == -1) {     // 3000 + R: the sub-pixel up-conv row kernel, weights in its fragment order
-            RowUpParams q{};
-            q.src0 = src0; q.src1 = src1; q.w = w_packed; q.scale = scale; q.shift = shift; q.out = out;
-            q.B = batch; q.H = hs; q.W = ws; q.R = tile_m - 3000; q.relu = relu; q.dtype = dtype;
-            if (!rowup_layer(L, dtype) || residual || hs != ws || !rowup_supported(q) || (q.R & 1))
-                return fail(LSPF2F_ERR_UNSUPPORTED, "the bf16 up-conv row kernel does not support this shape");
-            e = launch_rowup(q, static_cast<hipStream_t>(hip_stream));
-            if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (rowup) launch");
-            return LSPF2F_OK;
-        }
-        if ((tile_m == 5001 || tile_m == 5002) && k_group == -1) {   // 5000 + nb: the up-conv Winograd kernel, w_packed in its fragment order; split_k = K splits
-            const int sp = split_k > 0 ? split_k : 1, nbk = tile_m - 5000;
-            const size_t slab = sp > 1 ? (size_t)sp * batch * 4 * hs * ws * cout * sizeof(float) : 0;
-            WinoUpParams q{};
-            q.src0 = static_cast<const float *>(src0); q.src1 = c1 ? static_cast<const float *>(src1) : nullptr; q.u = static_cast<const float *>(w_packed);
-            q.scale = scale; q.shift = shift; q.out = static_cast<float *>(out);
-            q.B = batch; q.Hs = hs; q.Ws = ws; q.C0 = c0; q.C1 = c1; q.N = cout; q.relu = relu; q.splits = sp;
-            if (sp > 1) {
-                const size_t ncnt = (size_t)batch * (hs / 4) * (ws / 8) * (cout / (32 * nbk));
-                if (!scratch || scratch_bytes < slab + ncnt * sizeof(unsigned)) return fail(LSPF2F_ERR_STATE, "split-K scratch missing or too small");
-                q.partial = static_cast<float *>(scratch);
-                q.tile_cnt = reinterpret_cast<unsigned *>(static_cast<char *>(scratch) + slab);   // must be zero on entry; every launch leaves it zero
-            }
-            if (in) { q.psum = in->psum; q.psq = in->psq; q.pshift = in->pshift; }
-            if (dtype != 0 || stride != 1 || !upsample || residual || hs != ws || !winoup_supported(q, nbk))
-                return fail(LSPF2F_ERR_UNSUPPORTED, "the up-conv Winograd kernel does not support this shape");
-            e = launch_winoup(q, nbk, static_cast<hipStream_t>(hip_stream));
-            if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (winoup) launch");
-            return LSPF2F_OK;
-        }
-        if (tile_m == 6001 && k_group == -1) {                        // the Winograd F(4x4, 3x3) kernel, w_packed in the order of pack_wino4_weights(); split_k = K splits (0: 1)
-            const int sp = split_k > 0 ? split_k : 1;
-            const size_t slab = sp > 1 ? (size_t)sp * batch * hs * ws * cout * sizeof(float) : 0;
-            const size_t ncnt = (size_t)batch * (hs / 16) * (ws / 32) * (cout / 32);
-            WinoParams q{};
-            q.src = static_cast<const float *>(src0); q.u = static_cast<const float *>(w_packed); q.scale = scale; q.shift = shift;
-            q.residual = static_cast<const float *>(residual); q.out = static_cast<float *>(out);
-            q.B = batch; q.H = hs; q.W = ws; q.C = c0; q.N = cout; q.relu = relu; q.splits = sp;
-            if (sp > 1) {
-                if (!scratch || scratch_bytes < slab + ncnt * sizeof(unsigned)) return fail(LSPF2F_ERR_STATE, "split-K scratch missing or too small");
-                q.partial = static_cast<float *>(scratch);
-                q.tile_cnt = reinterpret_cast<unsigned *>(static_cast<char *>(scratch) + slab);   // must be zero on entry; every launch leaves it zero
-            }
+    switch (t.route) {
+    case kRouteRowUp: {
+        const RowUpParams q = rowup_params(io, L);
+        if (!rowup_layer(L, dtype) || residual || !rowup_supported(q) || (q.R & 1))
+            return fail(LSPF2F_ERR_UNSUPPORTED, "the bf16 up-conv row kernel does not support this shape");
+        return launched(launch_rowup(q, s), "lspf2f_conv3x3 (rowup) launch");
+    }
+    case kRouteWinoUp: {
+        if (L.splits > 1 && !bind_scratch(winoup_scratch(batch, hs, ws, cout, t.arg, L.splits))) return fail(LSPF2F_ERR_STATE, "split-K scratch missing or too small");
+        WinoUpParams q = winoup_params(io, L);
+        if (in) { q.psum = in->psum; q.psq = in->psq; q.pshift = in->pshift; }
+        if (dtype != 0 || stride != 1 || !upsample || residual || !winoup_supported(q, t.arg))
+            return fail(LSPF2F_ERR_UNSUPPORTED, "the up-conv Winograd kernel does not support this shape");
+        return launched(launch_winoup(q, t.arg, s), "lspf2f_conv3x3 (winoup) launch");
+    }
+    case kRouteWino4:
+    case kRouteWino: {
+        const bool f4 = t.route == kRouteWino4;
+        const SplitKScratch k = f4 ? wino4_scratch(batch, hs, ws, cout, L.splits) : wino_scratch(batch, hs, ws, cout, t.arg, L.splits);
+        if (L.splits > 1 && !bind_scratch(k)) return fail(LSPF2F_ERR_STATE, "split-K scratch missing or too small");
+        WinoParams q = wino_params(io, L);
+        q.ureg = tile_m == 4003;      // 4003: nb = 1 with the U fragments in registers (the form the plans take), 4001: through LDS
 #ifdef LSPF2F_WINO_STAMPS
-            {   // stamps live behind slabs and counters when the caller's scratch has room for them
-                const size_t used = (slab + ncnt * sizeof(unsigned) + 255) / 256 * 256;
-                const size_t blocks = ncnt * (size_t)sp;
-                if (scratch && scratch_bytes >= used + blocks * 4 * 8 * 8) q.stamps = reinterpret_cast<unsigned long long *>(static_cast<char *>(scratch) + used);
-            }
+        {   // stamps live behind slabs and counters when the caller's scratch has room for them
+            const size_t used = (k.bytes() + 255) / 256 * 256;
+            const size_t blocks = k.counters * (size_t)L.splits;
+            if (scratch && scratch_bytes >= used + blocks * 4 * 8 * 8) q.stamps = reinterpret_cast<unsigned long long *>(static_cast<char *>(scratch) + used);
+        }
 #endif
-            if (dtype != 0 || c1 != 0 || stride != 1 || upsample != 0 || hs != ws || !wino4_supported(q))
-                return fail(LSPF2F_ERR_UNSUPPORTED, "the Winograd F(4x4,3x3) kernel does not support this shape");
-            e = launch_wino4(q, static_cast<hipStream_t>(hip_stream));
-            if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (wino4) launch");
-            return LSPF2F_OK;
-        }
-        if ((tile_m == 4001 || tile_m == 4002 || tile_m == 4003) && k_group == -1) {   // 4000 + nb: the Winograd kernel, w_packed in its fragment order; split_k = K splits (0: 1)
-            const int ureg = tile_m == 4003 ? 1 : 0;      // 4003: nb = 1 with the U fragments in registers (the form the plans take), 4001: through LDS
-            if (ureg) tile_m = 4001;
-            const int sp = split_k > 0 ? split_k : 1;
-            const size_t slab = sp > 1 ? (size_t)sp * batch * hs * ws * cout * sizeof(float) : 0;
-            const size_t ncnt = (size_t)batch * (hs / 8) * (ws / 16) * (cout / (32 * (tile_m - 4000)));
-            WinoParams q{};
-            q.src = static_cast<const float *>(src0); q.u = static_cast<const float *>(w_packed); q.scale = scale; q.shift = shift;
-            q.residual = static_cast<const float *>(residual); q.out = static_cast<float *>(out);
-            q.B = batch; q.H = hs; q.W = ws; q.C = c0; q.N = cout; q.relu = relu; q.splits = sp; q.ureg = ureg;
-            if (sp > 1) {
-                if (!scratch || scratch_bytes < slab + ncnt * sizeof(unsigned)) return fail(LSPF2F_ERR_STATE, "split-K scratch missing or too small");
-                q.partial = static_cast<float *>(scratch);
-                q.tile_cnt = reinterpret_cast<unsigned *>(static_cast<char *>(scratch) + slab);   // must be zero on entry; every launch leaves it zero
-            }
-#ifdef LSPF2F_WINO_STAMPS
-            {   // stamps live behind slabs and counters when the caller's scratch has room for them
-                const size_t used = (slab + ncnt * sizeof(unsigned) + 255) / 256 * 256;
-                const size_t blocks = ncnt * (size_t)sp;
-                if (scratch && scratch_bytes >= used + blocks * 4 * 8 * 8) q.stamps = reinterpret_cast<unsigned long long *>(static_cast<char *>(scratch) + used);
-            }
-#endif
-            if (in) { q.psum = in->psum; q.psq = in->psq; q.pshift = in->pshift; }
-            if (dtype != 0 || c1 != 0 || stride != 1 || upsample != 0 || hs != ws || !wino_supported(q, tile_m - 4000))
-                return fail(LSPF2F_ERR_UNSUPPORTED, "the Winograd kernel does not support this shape");
-            e = launch_wino(q, tile_m - 4000, static_cast<hipStream_t>(hip_stream));
-            if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (wino) launch");
-            return LSPF2F_OK;
-        }
-        if ((tile_m == 7164 || tile_m == 7132 || tile_m == 7116) && k_group != -4) {   // 7100 + tile width: the patch-staged kernel's sub-pixel up-conv form (conv3x3_patchup16); upsample == 2, w_packed = [4][cout][2][2][c0 + c1]
-            PatchConvParams q{};
-            q.src = src0; q.src1 = c1 ? src1 : nullptr; q.w = w_packed; q.scale = scale; q.shift = shift; q.residual = residual; q.out = out;
-            q.B = batch; q.H = hs; q.W = ws; q.C = c0; q.C1 = c1; q.Cout = cout; q.relu = relu; q.dtype = dtype;
-            if (stride != 1 || upsample != 2 || !patchup16_supported(q, tile_m - 7100, tile_n))
-                return fail(LSPF2F_ERR_UNSUPPORTED, "the patch-staged 16-bit up-conv kernel does not support this shape");
-            e = launch_patchup16(q, tile_m - 7100, tile_n, static_cast<hipStream_t>(hip_stream));
-            if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (patchup16) launch");
-            return LSPF2F_OK;
-        }
-        if ((tile_m == 7064 || tile_m == 7032) && k_group != -4) {   // 7000 + tile width: the patch-staged 16-bit kernel (patch16.hip), tile_n = 128 | 64 channels per workgroup; igemm weight rows
-            PatchConvParams q{};
-            q.src = src0; q.w = w_packed; q.scale = scale; q.shift = shift; q.residual = residual; q.out = out;
-            q.B = batch; q.H = hs; q.W = ws; q.C = c0; q.Cout = cout; q.relu = relu; q.dtype = dtype;
-            q.deep = tile_n == 64;                  // tile_n 65 = 64 channels per workgroup in the FIRST form (copies in the load segment, 3-slot ring; A-B runs, the ablation and stamp builds)
-            if (tile_n == 65) tile_n = 64;
+        if (in) { q.psum = in->psum; q.psq = in->psq; q.pshift = in->pshift; }
+        if (dtype != 0 || c1 != 0 || stride != 1 || upsample != 0 || !(f4 ? wino4_supported(q) : wino_supported(q, t.arg)))
+            return fail(LSPF2F_ERR_UNSUPPORTED, f4 ? "the Winograd F(4x4,3x3) kernel does not support this shape" : "the Winograd kernel does not support this shape");
+        return f4 ? launched(launch_wino4(q, s), "lspf2f_conv3x3 (wino4) launch") : launched(launch_wino(q, t.arg, s), "lspf2f_conv3x3 (wino) launch");
+    }
+    case kRoutePatchUp16: {
+        const PatchConvParams q = patch_params(io, L);
+        if (stride != 1 || upsample != 2 || !patchup16_supported(q, t.arg, tile_n))
+            return fail(LSPF2F_ERR_UNSUPPORTED, "the patch-staged 16-bit up-conv kernel does not support this shape");
+        return launched(launch_patchup16(q, t.arg, tile_n, s), "lspf2f_conv3x3 (patchup16) launch");
+    }
+    case kRoutePatch16: {
+        PatchConvParams q = patch_params(io, L);
+        q.deep = tile_n == 64;                  // tile_n 65 = 64 channels per workgroup in the FIRST form (copies in the load segment, 3-slot ring; A-B runs, the ablation and stamp builds)
 #ifdef LSPF2F_ABLATE
-            q.dbg = ablate_dbg();
+        q.dbg = ablate_dbg();
 #endif
 #ifdef LSPF2F_PATCH_STAMPS
-            if (scratch && scratch_bytes >= (size_t)4096 * 8 * 8 * 8) q.stamps = static_cast<unsigned long long *>(scratch);
+        if (scratch && scratch_bytes >= (size_t)4096 * 8 * 8 * 8) q.stamps = static_cast<unsigned long long *>(scratch);
 #endif
-            if (c1 != 0 || stride != 1 || upsample != 0 || !patch16_supported(q, tile_m - 7000, tile_n))
-                return fail(LSPF2F_ERR_UNSUPPORTED, "the patch-staged 16-bit kernel does not support this shape");
-            e = launch_patch16(q, tile_m - 7000, tile_n, static_cast<hipStream_t>(hip_stream));
-            if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (patch16) launch");
-            return LSPF2F_OK;
-        }
-        if (tile_m == 2000 && k_group == -1) {     // the activation-stationary bf16 kernel of the 16x16 / 8x8 levels; weights in its fragment order
-            BandConvParams q{};
-            q.src = src0; q.w = w_packed; q.scale = scale; q.shift = shift; q.residual = residual; q.out = out;
-            q.B = batch; q.W = hs; q.Cout = cout; q.relu = relu; q.dtype = dtype;
-            if (!bandconv_layer(L, dtype) || hs != ws || !bandconv_supported(q))
-                return fail(LSPF2F_ERR_UNSUPPORTED, "the bf16 band kernel does not support this shape");
-            e = launch_bandconv(q, static_cast<hipStream_t>(hip_stream));
-            if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (bandconv) launch");
-            return LSPF2F_OK;
-        }
-        if (tile_m > 1000 && (tile_n == 64 || tile_n == 128) && k_group != -4) {   // 1000 + R: the weights-stationary bf16 kernel (tile_n channels in and out) with R output rows per strip
-            RowConvParams q{};
-            q.src = src0; q.w = w_packed; q.scale = scale; q.shift = shift; q.residual = residual; q.out = out;
-            q.B = batch; q.H = hs; q.W = ws; q.C = tile_n; q.R = tile_m - 1000; q.relu = relu; q.dtype = dtype;
-            q.wfrag = k_group == -1 ? 1 : 0;     // -1: w_packed is already in the row kernel's fragment order
-            if (!rowconv_layer(L, dtype) || c0 != tile_n || hs != ws || !rowconv_supported(q))
-                return fail(LSPF2F_ERR_UNSUPPORTED, "the bf16 row kernel does not support this shape");
-            e = launch_rowconv(q, static_cast<hipStream_t>(hip_stream));
-            if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (rowconv) launch");
-            return LSPF2F_OK;
-        }
-        if (dtype != 0 && (tile_m == 16 || tile_m == 32) && tile_n == 16 && k_group != -4) {      // the 16-bit full-K kernel (fullk16.hip); k_group -1: w_packed in its tile-blocked order
-            FullK16Params q{};
-            q.src0 = src0; q.src1 = c1 ? src1 : nullptr; q.w = w_packed; q.scale = scale; q.shift = shift; q.residual = residual; q.out = out;
-            q.B = batch; q.Hs = hs; q.Ws = ws; q.Ho = ho_; q.Wo = ho_; q.C0 = c0; q.C1 = c1; q.Cout = cout;
-            q.up = upsample == 1; q.relu = relu; q.stride = stride; q.dtype = dtype; q.wtile = k_group == -1 ? 1 : 0;
-            if (upsample == 2 || hs != ws || !fullk16_supported(q, tile_m / 16)) return fail(LSPF2F_ERR_UNSUPPORTED, "the 16-bit full-K kernel does not support this shape");
-            e = launch_fullk16(q, tile_m / 16, static_cast<hipStream_t>(hip_stream));
-            if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (full-K, 16-bit) launch");
-            return LSPF2F_OK;
-        }
-        int pb = 0;
-        if ((tile_m == 16 || tile_m == 32) && tile_n == 16) pb = tile_m / 16;
-        else if (tile_m == 0 && tile_n == 0 && split_k == 0 && k_group != -4)
-            pb = fullk_choice(L, batch, dtype);
-        if (pb) {
-            FullKParams q{};
-            q.src0 = static_cast<const float *>(src0); q.src1 = c1 ? static_cast<const float *>(src1) : nullptr;
-            q.w = static_cast<const float *>(w_packed); q.scale = scale; q.shift = shift;
-            q.residual = static_cast<const float *>(residual); q.out = static_cast<float *>(out);
-            q.B = batch; q.Hs = hs; q.Ws = ws; q.Ho = ho_; q.Wo = ho_; q.C0 = c0; q.C1 = c1; q.Cout = cout;
-            q.up = upsample == 1; q.relu = relu; q.stride = stride;
-            q.wtile = k_group == -1 ? 1 : 0;       // -1: w_packed is already in the full-K kernel's tile-blocked layout
-            if (split_k == 2) {    // K halves: scratch = [2][tiles][256] floats + one zeroed counter per tile; a single source's w_packed is
-                                                   // packed as two half-sources
-                const size_t ntile = (size_t)batch * (ho_ * ho_ / (16 * pb)) * (cout / 16);     // 16 pb-pixel tiles x 16-channel slices
-                const size_t slab = 2 * ntile * pb * 256 * sizeof(float);
-                if (!scratch || scratch_bytes < slab + ntile * sizeof(unsigned))
-                    return fail(LSPF2F_ERR_INVALID_ARGUMENT, "scratch too small for the K-split full-K kernel");
-                q.split = 2; q.partial = static_cast<float *>(scratch);
-                q.tile_cnt = reinterpret_cast<unsigned *>(static_cast<char *>(scratch) + slab);
-            }
-#ifdef LSPF2F_FULLK_STAMPS
-            q.stamps = scratch_bytes >= (size_t)512 * 4 * 16 * 8 ? static_cast<unsigned long long *>(scratch) : nullptr;
-#endif
-            if (dtype != 0 || (stride != 1 && !(stride == 2 && q.split == 2)) || upsample == 2 || !fullk_supported(q, pb))
-                return fail(LSPF2F_ERR_UNSUPPORTED, "full-K kernel does not support this shape");
-            e = launch_fullk(q, pb, static_cast<hipStream_t>(hip_stream));
-            if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 (full-K) launch");
-            return LSPF2F_OK;
-        }
+        if (c1 != 0 || stride != 1 || upsample != 0 || !patch16_supported(q, t.arg, t.bn))
+            return fail(LSPF2F_ERR_UNSUPPORTED, "the patch-staged 16-bit kernel does not support this shape");
+        return launched(launch_patch16(q, t.arg, t.bn, s), "lspf2f_conv3x3 (patch16) launch");
     }
-    IgemmParams p{};
-    p.src0 = src0; p.src1 = c1 ? src1 : nullptr; p.w = w_packed; p.scale = scale; p.shift = shift;
-    p.residual = residual; p.out = out;
-    p.B = batch; p.Hs = hs; p.Ws = ws;
-    p.Ho = upsample ? 2 * hs : (stride == 2 ? (hs + 1) / 2 : hs);
-    p.Wo = p.Ho;
-    if (upsample < 0 || upsample > 2) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "upsample must be 0, 1 or 2");
-    p.C0 = c0; p.C1 = c1; p.Cin = c0 + c1; p.Cout = cout; p.stride = stride; p.relu = relu;
-    p.up = upsample == 1; p.up4 = upsample == 2;
-    p.Mout = batch * p.Ho * p.Wo;
-    p.M = p.up4 ? batch * hs * ws : p.Mout;
-    p.dtype = dtype;
-    p.ktiles_total = (p.up4 ? 4 : 9) * p.Cin / ktc;
+    case kRouteBand: {
+        const BandConvParams q = band_params(io, L);
+        if (!bandconv_layer(L, dtype) || !bandconv_supported(q)) return fail(LSPF2F_ERR_UNSUPPORTED, "the bf16 band kernel does not support this shape");
+        return launched(launch_bandconv(q, s), "lspf2f_conv3x3 (bandconv) launch");
+    }
+    case kRouteRowConv: {
+        const RowConvParams q = rowconv_params(io, L);
+        if (!rowconv_layer(L, dtype) || c0 != tile_n || !rowconv_supported(q)) return fail(LSPF2F_ERR_UNSUPPORTED, "the bf16 row kernel does not support this shape");
+        return launched(launch_rowconv(q, s), "lspf2f_conv3x3 (rowconv) launch");
+    }
+    case kRouteFullK16: {
+        const FullK16Params q = fullk16_params(io, L);
+        if (upsample == 2 || !fullk16_supported(q, t.arg)) return fail(LSPF2F_ERR_UNSUPPORTED, "the 16-bit full-K kernel does not support this shape");
+        return launched(launch_fullk16(q, t.arg, s), "lspf2f_conv3x3 (full-K, 16-bit) launch");
+    }
+    default: break;
+    }
+    // the fp32 full-K kernel: forced by its tile, or picked by the planner's rule (tile 0x0 + split 0).  split_k 2 = K halves; a single source's w_packed is then packed as two half-sources
+    if (const int pb = t.route == kRouteFullK ? t.arg : t.planner ? fullk_choice(L, batch, dtype) : 0) {
+        if (L.splits == 2 && !bind_scratch(fullk_split_scratch(batch, L.ho, cout, pb))) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "scratch too small for the K-split full-K kernel");
+        FullKParams q = fullk_params(io, L);
+#ifdef LSPF2F_FULLK_STAMPS
+        q.stamps = scratch_bytes >= (size_t)512 * 4 * 16 * 8 ? static_cast<unsigned long long *>(scratch) : nullptr;
+#endif
+        if (dtype != 0 || (stride != 1 && !(stride == 2 && q.split == 2)) || upsample == 2 || !fullk_supported(q, pb))
+            return fail(LSPF2F_ERR_UNSUPPORTED, "full-K kernel does not support this shape");
+        return launched(launch_fullk(q, pb, s), "lspf2f_conv3x3 (full-K) launch");
+    }
+    // the implicit GEMM on the tiles asked for; 0 x 0, split_k 0 and k_group 0 each take the planner's value
+    const int kt = conv3x3_tiling(L, batch, tile_m, tile_n, split_k, k_group, dtype);
+    if (!igemm_group_supported(L.bm, L.bn, L.group, L.up)) return fail(LSPF2F_ERR_UNSUPPORTED, "tile shape / k_group not instantiated");
+    if (L.splits < 1 || L.splits > kt) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "bad split_k");
+    const int per = (kt + L.splits - 1) / L.splits, sp = L.splits = (kt + per - 1) / per;      // no empty slice
+    if (in) {
+        // epilogue sums: the planner's own precondition (a wave's rows inside one frame, one K slice), and the group count the caller sized the statistics for
+        const int rhw = L.up4 ? hs * hs : L.ho * L.ho;
+        if (!in_fused_eligible(L.bm, sp, rhw) || in->groups != (L.up4 ? 4 : 1) * rhw / in_fused_wave_rows(L.bm))
+            return fail(LSPF2F_ERR_UNSUPPORTED, "the implicit GEMM gathers InstanceNorm statistics in its epilogue only with one K slice, >= 1024 pixels per frame and whole waves per frame");
+    }
+    if (sp > 1 && !bind_scratch(igemm_scratch(batch * L.ho * L.ho, cout, sp))) return fail(LSPF2F_ERR_STATE, "split-K scratch missing or too small");
+    IgemmParams p = igemm_params(io, L);
+    if (in) { p.psum = in->psum; p.psq = in->psq; p.pshift = in->pshift; p.in_groups = in->groups; }
     if (k_group == -4) {
         // Conv2d(k4, s2, p1) as a 3x3 conv on the space-to-depth image (c0 = 4 ci, channel = (dy * 2 + dx) * ci + c): tap row ty reads sub-rows {1}, {0, 1}, {0} for
         // ty = 0, 1, 2 (columns alike), so 16 of the 36 (tap, quarter) pairs carry weights; w_packed = [cout][those 16 in tap-major order][ci]
-        if (dtype != 0 || stride != 1 || upsample || c1 || c0 % 4 || (c0 / 4) % ktc) return fail(LSPF2F_ERR_UNSUPPORTED, "k_group -4 (space-to-depth 4x4 / s2 taps): fp32, one source of 4 x ci channels, ci a multiple of 32");
         static const unsigned sub[3] = {2u, 3u, 1u};          // live sub-rows of tap row 0, 1, 2 as a bit set over dy
-        p.kmask = 0;
         for (int ty = 0; ty < 3; ++ty)
             for (int tx = 0; tx < 3; ++tx)
                 for (int dy = 0; dy < 2; ++dy)
                     for (int dx = 0; dx < 2; ++dx)
                         if (((sub[ty] >> dy) & 1u) && ((sub[tx] >> dx) & 1u)) p.kmask |= 1ull << ((ty * 3 + tx) * 4 + dy * 2 + dx);
-        p.kblk = c0 / 4;
-        p.ktiles_total = 16 * p.kblk / ktc;
-        k_group = 0;
-    }
-    int bm = tile_m, bn = tile_n, sp = split_k, grp = k_group;
-    {
-        int a, b, c, g;
-        choose_tiling(p.M, cout, p.ktiles_total, p.up4 ? 4 : 1, p.up != 0, dtype, &a, &b, &c, &g);
-        if (!bm || !bn) { bm = a; bn = b; if (!grp) grp = g; }
-        if (!sp) sp = c;
-        if (!grp) grp = 1;
-    }
-    if (!igemm_group_supported(bm, bn, grp, p.up != 0)) return fail(LSPF2F_ERR_UNSUPPORTED, "tile shape / k_group not instantiated");
-    if (sp < 1 || sp > p.ktiles_total) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "bad split_k");
-    p.ktiles_per_split = (p.ktiles_total + sp - 1) / sp;
-    sp = (p.ktiles_total + p.ktiles_per_split - 1) / p.ktiles_per_split;
-    p.splits = sp;
-    if (in) {
-        // epilogue sums: the planner's own precondition (a wave's rows inside one frame, one K slice), and the group count the caller sized the statistics for
-        const int rhw = p.up4 ? hs * ws : p.Ho * p.Wo;
-        if (!in_fused_eligible(bm, sp, rhw) || in->groups != (p.up4 ? 4 : 1) * rhw / in_fused_wave_rows(bm))
-            return fail(LSPF2F_ERR_UNSUPPORTED, "the implicit GEMM gathers InstanceNorm statistics in its epilogue only with one K slice, >= 1024 pixels per frame and whole waves per frame");
-        p.psum = in->psum; p.psq = in->psq; p.pshift = in->pshift; p.in_groups = in->groups;
-    }
-    if (sp > 1) {
-        if (!scratch || scratch_bytes < (size_t)sp * p.Mout * cout * sizeof(float))
-            return fail(LSPF2F_ERR_STATE, "split-K scratch missing or too small");
-        p.partial = static_cast<float *>(scratch);
+        p.kblk = c0 / 4; p.ktiles_total = kt; p.ktiles_per_split = per;
     }
 #ifdef LSPF2F_ABLATE
     p.dbg = ablate_dbg();   // tools/ablate.sh builds only
@@ -1267,11 +1188,9 @@ static int conv3x3_run(const void *src0, const void *src1, const void *w_packed,
 #ifdef LSPF2F_IGEMM_STAMPS
     if (sp == 1 && scratch && scratch_bytes >= (size_t)2048 * 4 * 16 * 8) p.stamps = static_cast<unsigned long long *>(scratch);
 #endif
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    e = launch_igemm(p, bm, bn, grp, s);
+    hipError_t e = launch_igemm(p, L.bm, L.bn, L.group, s);
     if (e == hipSuccess && sp > 1) e = launch_splitk_reduce(p, s);
-    if (e != hipSuccess) return hipfail(e, "lspf2f_conv3x3 launch");
-    return LSPF2F_OK;
+    return launched(e, "lspf2f_conv3x3 launch");
 }
 
 int lspf2f_conv3x3(const void *src0, const void *src1, const void *w_packed, const float *scale,
@@ -1318,32 +1237,25 @@ int lspf2f_instance_norm(float *x, const float *partial, int splits, const float
     return LSPF2F_OK;
 }
 
-// the statistics producer a (tile, k_group) selection of lspf2f_conv3x3 names under InstanceNorm plans
-enum InProducer { kProdNone = 0, kProdIgemm, kProdWino, kProdWinoUp, kProdTiny };
-static InProducer in_producer(int tile_m, int tile_n, int k_group)
-{
-    if (tile_m == 1 && tile_n == 1) return kProdTiny;
-    if ((tile_m == 4001 || tile_m == 4002 || tile_m == 4003) && k_group == -1) return kProdWino;
-    if ((tile_m == 5001 || tile_m == 5002) && k_group == -1) return kProdWinoUp;
-    if ((tile_m == 128 || tile_m == 64 || tile_m == 32) && tile_n == 64 && k_group >= 0) return kProdIgemm;
-    return kProdNone;
-}
-// B, hw, C, groups and rows_per_group of the InstanceNorm behind that conv; "" or why the selection is refused
+// B, hw, C, groups and rows_per_group of the InstanceNorm behind the conv a tile code of lspf2f_conv3x3 names, and the kernel that produces its statistics; "" or why
+// the selection is refused
 static const char *conv3x3_in_shape(int batch, int hs, int ws, int cout, int stride, int upsample, int tile_m, int tile_n, int split_k, int k_group, int dtype,
-                                    InProducer *prod, InstNormParams *q)
+                                    ConvRoute *prod, InstNormParams *q)
 {
-    *prod = in_producer(tile_m, tile_n, k_group);
-    if (*prod == kProdNone) return "conv3x3_instnorm: the statistics producers are the implicit GEMM (tile 128 | 64 | 32 x 64), wino3x3 (4001 .. 4003), winoup3x3 (5001, 5002) and the tiny-M kernel (1 x 1)";
+    *prod = decode_tile(tile_m, tile_n, split_k, k_group, dtype).route;
+    const bool gemm_stats = (tile_m == 128 || tile_m == 64 || tile_m == 32) && tile_n == 64 && k_group >= 0;      // (of the implicit GEMM's tiles, the 64-column ones)
+    if (*prod != kRouteSmallM && *prod != kRouteWino && *prod != kRouteWinoUp && !(*prod == kRouteIgemm && gemm_stats))
+        return "conv3x3_instnorm: the statistics producers are the implicit GEMM (tile 128 | 64 | 32 x 64), wino3x3 (4001 .. 4003), winoup3x3 (5001, 5002) and the tiny-M kernel (1 x 1)";
     if (dtype != 0) return "conv3x3_instnorm: InstanceNorm plans are fp32 only";
     if (batch < 1 || hs < 1 || hs != ws || cout < 4 || cout % 4 || (stride != 1 && stride != 2) || upsample < 0 || upsample > 2) return "conv3x3_instnorm: bad shape";
     const int ho = upsample ? 2 * hs : (stride == 2 ? (hs + 1) / 2 : hs);
     q->B = batch; q->hw = ho * ho; q->C = cout; q->groups = 0; q->rows_per_group = 0;
-    if (*prod == kProdIgemm) {
+    if (*prod == kRouteIgemm) {
         const int rhw = upsample == 2 ? hs * hs : ho * ho;
         if (split_k != 1 || !in_fused_eligible(tile_m, split_k, rhw))
             return "conv3x3_instnorm: the implicit GEMM gathers InstanceNorm statistics in its epilogue only with split_k 1, >= 1024 pixels per frame and whole waves per frame";
         in_groups_igemm(*q, tile_m, upsample == 2, rhw);
-    } else if (*prod != kProdTiny) {
+    } else if (*prod != kRouteSmallM) {
         if (q->hw % 128) return "conv3x3_instnorm: the Winograd kernels leave one group per tile-block of 128 output pixels";
         in_groups_wino(*q);
     }
@@ -1354,10 +1266,10 @@ size_t lspf2f_conv3x3_instnorm_scratch_bytes(int batch, int hs, int ws, int c0, 
                                              int dtype)
 {
     (void)c0; (void)c1;
-    InProducer prod;
+    ConvRoute prod;
     InstNormParams q{};
     if (*conv3x3_in_shape(batch, hs, ws, cout, stride, upsample, tile_m, tile_n, split_k, k_group, dtype, &prod, &q)) return 0;
-    const size_t stats = prod == kProdTiny ? 0 : ((size_t)3 * q.groups + 2) * batch * cout;
+    const size_t stats = prod == kRouteSmallM ? 0 : ((size_t)3 * q.groups + 2) * batch * cout;
     return ((size_t)cout + stats) * sizeof(float);
 }
 
@@ -1366,7 +1278,7 @@ int lspf2f_conv3x3_instnorm(const void *src0, const void *src1, const void *w_pa
                             void *scratch, size_t scratch_bytes, void *stats, size_t stats_bytes, void *hip_stream)
 {
     if (!src0 || !w_packed || !out) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "null argument");
-    InProducer prod;
+    ConvRoute prod;
     InstNormParams q{};
     const char *why = conv3x3_in_shape(batch, hs, ws, cout, stride, upsample, tile_m, tile_n, split_k, k_group, dtype, &prod, &q);
     if (*why) return fail(LSPF2F_ERR_UNSUPPORTED, why);
@@ -1383,7 +1295,7 @@ int lspf2f_conv3x3_instnorm(const void *src0, const void *src1, const void *w_pa
     q.x = static_cast<float *>(out); q.residual = static_cast<const float *>(residual); q.relu = relu; q.partial = nullptr; q.splits = 1; q.bias = nullptr;
     in_bind_stats(q, ones + cout, (size_t)batch * q.groups);
     // the tiny-M kernel normalises (+ residual, ReLU) in its own epilogue; behind the others the residual add and the ReLU follow the normalisation, in in_apply
-    const bool tiny = prod == kProdTiny;
+    const bool tiny = prod == kRouteSmallM;
     const int rc = conv3x3_run(src0, src1, w_packed, bias ? ones : nullptr, bias, tiny ? residual : nullptr, out, batch, hs, ws, c0, c1, cout, stride, upsample, tiny ? relu : 0,
                                tile_m, tile_n, split_k, k_group, dtype, scratch, scratch_bytes, hip_stream, &q);
     if (rc != LSPF2F_OK || tiny) return rc;

@@ -102,7 +102,7 @@ static int wino_choice(const LayerDesc &l, int batch, int *splits_out)
     // A workgroup = 32 Winograd tiles (8 x 16 output pixels) x 32 nb channels over the whole K (or a slice).  Two channel blocks per wave halve
     // the fragment reads per MFMA but cost half the workgroups: used when that still leaves two workgroups per CU.  Below ~1.5 workgroups
     // per CU the input channels are split (combined inside the launch), keeping >= 4 eight-channel steps per slice.
-    const long ntb = (long)batch * (ho / 8) * (ho / 16);
+    const long ntb = (long)wino_tile_blocks(batch, ho, ho);
     // 16x16 frames (2 tile-blocks each): measured 18.9 us against 17.4 us for the full-K kernel at 1 frame, 48.9 against 89.4 us for
     // igemm + split-K at 8 frames (tools/wino_sweep.py); the full-K kernel covers <= 2 frames, Winograd takes over from 4
     if (ho < 32 && ntb * (cout / 32) < 128) return 0;
@@ -122,7 +122,7 @@ static int wino4_choice(const LayerDesc &l, int batch, int *splits_out)
     const int ho = l.ho, cin = l.cin, cout = l.cout;
     // A workgroup = 32 tiles of 4 x 4 outputs (16 x 32 pixels) x 32 channels, ONE per CU (its ring slots take 112 KB of LDS): below ~one
     // workgroup per CU the input channels are split (combined inside the launch), keeping >= 4 eight-channel steps per slice.
-    const long wgs = (long)batch * (ho / 16) * (ho / 32) * (cout / 32);
+    const long wgs = (long)wino4_tile_blocks(batch, ho, ho) * (cout / 32);
     const int splits = wgs < 192 ? wino_k_splits(wgs, 256, cin / 8, 4) : 1;
     WinoParams q{};
     q.B = batch; q.H = ho; q.W = ho; q.C = cin; q.N = cout; q.splits = 1;
@@ -144,7 +144,7 @@ static int winoup_choice(const Plan &P, const LayerDesc &l, int batch, int *spli
     // waves, four give every SIMD three.  So: one channel block per wave (115 registers, 28 KB of LDS: five fit) and K splits -- >= 8 eight-channel
     // steps each -- until there are ~4 workgroups per CU.  Measured, `large` fp32 (A-B-A-B, one session): nb 1 / 1024 workgroups 610.6 frames/s,
     // nb 1 / 512 605.6, nb 2 / 512 602.5, nb 2 / 1024 580.8, nb 1 / 1536 602.0, nb 1 / 2048 599.8; batch 8: nb 1 967.4, nb 2 945.8
-    const long ntb = (long)batch * (hs / 4) * (hs / 8);
+    const long ntb = (long)winoup_tile_blocks(batch, hs, hs);
     const int nb = force_nb ? force_nb : 1;
     if ((nb != 1 && nb != 2) || cout % (32 * nb)) return 0;     // a forced nb the shape cannot take: the implicit GEMM keeps the layer
     const long wgs = ntb * (cout / (32 * nb));

@@ -203,6 +203,33 @@ void choose_tiling(int M, int N, int ktiles, int par, bool up9, int dtype, int *
 inline int in_fused_wave_rows(int bm) { return bm == 32 ? 32 : bm / 2; }
 inline bool in_fused_eligible(int bm, int splits, int rhw) { return splits == 1 && rhw >= 1024 && rhw % in_fused_wave_rows(bm) == 0; }
 
+// Split-K scratch of one conv launch: fp32 partial slabs, then one arrival counter per tile the in-launch combine owns.  Each layout is stated here once:
+// lspf2f_conv3x3_scratch_bytes sizes it, lspf2f_conv3x3 bounds-checks and binds it, and the planner's Winograd rules test the same tile-block counts against
+// Plan::kTileCounters.
+struct SplitKScratch {
+    size_t slab_bytes, counters;
+    size_t bytes() const { return slab_bytes + counters * sizeof(unsigned); }
+};
+inline size_t wino_tile_blocks(int batch, int h, int w) { return (size_t)batch * (h / 8) * (w / 16); }        // wino3x3: 8 x 16 output pixels
+inline size_t wino4_tile_blocks(int batch, int h, int w) { return (size_t)batch * (h / 16) * (w / 32); }      // wino4_3x3: 16 x 32 output pixels
+inline size_t winoup_tile_blocks(int batch, int hs, int ws) { return (size_t)batch * (hs / 4) * (ws / 8); }   // winoup3x3: 4 x 8 SOURCE pixels
+// the Winograd kernels: [splits][pixels][cout] floats, a counter per (tile-block, 32 nb channels)
+inline SplitKScratch wino_family_scratch(size_t tile_blocks, size_t pixels, int cout, int nb, int splits)
+{
+    return {splits > 1 ? (size_t)splits * pixels * cout * sizeof(float) : 0, tile_blocks * (cout / (32 * nb))};
+}
+inline SplitKScratch wino_scratch(int batch, int h, int w, int cout, int nb, int splits) { return wino_family_scratch(wino_tile_blocks(batch, h, w), (size_t)batch * h * w, cout, nb, splits); }
+inline SplitKScratch wino4_scratch(int batch, int h, int w, int cout, int splits) { return wino_family_scratch(wino4_tile_blocks(batch, h, w), (size_t)batch * h * w, cout, 1, splits); }
+inline SplitKScratch winoup_scratch(int batch, int hs, int ws, int cout, int nb, int splits) { return wino_family_scratch(winoup_tile_blocks(batch, hs, ws), (size_t)batch * 4 * hs * ws, cout, nb, splits); }
+// K-split full-K kernel: [2][tiles][pb * 256] floats, a counter per tile of 16 pb pixels x 16 channels
+inline SplitKScratch fullk_split_scratch(int batch, int ho, int cout, int pb)
+{
+    const size_t tiles = (size_t)batch * (ho * ho / (16 * pb)) * (cout / 16);
+    return {2 * tiles * pb * 256 * sizeof(float), tiles};
+}
+// implicit GEMM: [splits][Mout][cout] floats; its in-launch combine (plans only) counts in the workspace's counters
+inline SplitKScratch igemm_scratch(int mout, int cout, int splits) { return {splits > 1 ? (size_t)splits * mout * cout * sizeof(float) : 0, 0}; }
+
 // Who gets a weight form at pack time: the batch-independent half of each kernel family's rule (the blob layout must not depend on the batch).
 // Policy only -- which layers a family is FOR; extents, alignments and LDS bounds are the kernel's own *_supported() (kernels.h), asked here
 // for one frame and by choose_route() for the batch.  Also used by lspf2f_conv3x3 on a LayerDesc filled from its arguments.

@@ -435,6 +435,8 @@ def test_conv3x3_rejects_bad_arguments(gpu_device):
     w = rnd(64, 48, 3, 3)
     with pytest.raises(N.Lspf2fError):
         run_conv(gpu_device, x, None, w, None, None, None, 1, False, False)
+    with pytest.raises(N.Lspf2fError, match="upsample must be 0, 1 or 2"):      # on every route, not only the implicit GEMM (here: the tiny-M kernel's tile)
+        run_conv(gpu_device, rnd(1, 32, 2, 2), None, rnd(64, 32, 3, 3), None, None, None, 1, 3, False, (1, 1))
 
 
 def bf16r(t):
