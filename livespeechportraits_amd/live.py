@@ -4,8 +4,10 @@ WaveNet, demo.py:183-216) fed with audio as it arrives instead of a whole clip.
 Every network of that chain is causal apart from a fixed lookahead, so a chunked run gives the bits of the whole-clip run: the GRU and
 LSTM carry their state between calls (lsprnn_forward_state), the WaveNet carries its dilation queues (lspa2h_generate_resume), the mel
 front-end computes a window range (lspmel_compute_range), and every row-wise stage reduces in an order that does not depend on how many
-rows a call has.  What becomes final when is decided by ``LiveScheduler``, pure Python with no device code; ``run_plan`` drives any
-backend with its plans (``LiveAudioFrontEnd`` on the device, a provenance fake in tests/test_live_cpu.py).
+rows a call has.  What becomes final when is decided by ``LiveScheduler``, and when the head-pose WaveNet's priming steps run by
+``PrimingPlanner``: both pure Python with no device code (``run_plan`` drives a provenance fake with their plans in tests/test_live_cpu.py).  The
+device side is written once, in live_pool.py: ``LiveSessionPool`` runs the stages for 1..16 streams per call, and
+``LiveAudioFrontEnd`` here is the one session of a pool of one, so priming is spread over the pushes for it too.
 
 Lookahead, derived from the finality rules (DESIGN.md "Live audio"): mouth frame t needs pair row t + 18, i.e. mel window 2t + 37,
 whose clip ends at sample int((2t + 37) * 133.33) + 266 -- about 5 200 samples (325 ms) after the start of frame t (t * 266.67);
@@ -14,8 +16,6 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 from typing import List, NamedTuple
-
-import numpy as np
 
 SAMPLE_RATE = 16000
 MEL_WIN = 266                          # int(16000 / 60): the clip of one mel window
@@ -126,7 +126,7 @@ class PrimingPlanner:
     steps per tick (``begin_tick`` refills the budget); when poses are due, every step up to the last of them runs at once, whatever
     is left of the priming included (a whole clip pushed at once primes in one go).  Pair rows are handed to the generator when steps
     run, all that exist: until pose 0 the rows 0..ff_head must stay in the generator's ring, which therefore holds at least
-    ff_head + (pair rows one step of work can add) rows -- ``ring_rows_needed``; LiveAudioFrontEnd's ring is one row longer."""
+    ff_head + (pair rows one step of work can add) rows -- ``ring_rows_needed``."""
 
     def __init__(self, field: int, ff_head: int, prime_steps_per_tick: int = 16):
         if field < 1 or ff_head < 0 or prime_steps_per_tick < 1:
@@ -164,7 +164,9 @@ class PrimingPlanner:
 
 
 def run_plan(backend, plan: LivePlan, samples) -> None:
-    """The order every step runs in; ``backend`` provides the stages (LiveAudioFrontEnd, or a test double):
+    """The order every step of ONE session runs in, stated without a device; ``backend`` provides the stages.  The device runs
+    live_pool.run_pool_round, the same order for several sessions, and is held to this statement by tests/test_live_pool_cpu.py
+    (a provenance double behind both):
     feed(samples, first_sample, keep_from)  append the new samples; samples before `keep_from` are no longer read
     mel(w0, w1, ended) / apc(w0, w1) / lle(w0, w1)   windows == rows [w0, w1)
     pairs(p0, p1)                            pair rows [p0, p1) from LLE rows [2 p0, 2 p1)
@@ -195,218 +197,41 @@ class LiveFrames(NamedTuple):
 
 
 class LiveAudioFrontEnd:
-    """demo.py's audio stages for audio that arrives in pieces, on the device.
+    """demo.py's audio stages for one stream of audio that arrives in pieces, on the device: the one session of a LiveSessionPool of one
+    (live_pool.py, which holds the stages, the carried state and the device memory -- there is no second implementation here).
 
     Built from what demo.py:146-166 builds and reads from the config: the APC_encoder, the Audio2FeatureModel and the
     Audio2HeadposeModel (the drop-ins of this package), APC_feat_database, use_LLE, Knear, LLE_percent, pre_headpose, sigma_scale, and
     both frame_future values (taken from the option objects: ``feature_opt`` / ``headpose_opt``, default the models' own ``opt``).
-    ``push(samples)`` returns the frames that became final; ``finish()`` flushes the end of the clip.  Pushed in any pieces, the
-    outputs are bit for bit those of the whole-clip path (mel.compute_mel -> APC_encoder -> manifold.project -> generate_sequences).
-    GMM noise is drawn per head-pose frame, in frame order, from ``generator`` (default: the global one) in draw_gmm_noise's order.
-    Device memory is fixed at construction; a push longer than ``max_chunk_samples`` is split internally.  The status words are read
-    once per push; a lost inter-workgroup hand-off (another stream holding the CUs for the whole time-out) ends the session with an error.
-    Every stage keeps its input state in a buffer of its own (two per stage, used in turn), so a caller that drives the C entry points
-    directly can run a failed call again from the same state."""
+    ``push(samples)`` returns the frames that became final; ``finish()`` flushes the end of the clip, after which the stream has ended
+    for good (a pool session's slot can be reopened; this object cannot).  Pushed in any pieces, the outputs are bit for bit those of
+    the whole-clip path (mel.compute_mel -> APC_encoder -> manifold.project -> generate_sequences).  GMM noise is drawn per head-pose
+    frame, in frame order, from ``generator`` (default: the global one) in draw_gmm_noise's order.  Everything else -- fixed device
+    memory, pushes longer than ``max_chunk_samples``, the head-pose priming spread ``prime_steps_per_tick`` steps per push, the status
+    words -- is LiveSessionPool's, and is described there.  So are the refusals of the constructor and of the samples: they are
+    raised by the pool and name it (and the session, 0) in their messages."""
 
     def __init__(self, APC_model, Audio2Feature, Audio2Headpose, APC_feat_database, use_LLE: bool, Knear: int, LLE_percent: float,
                  pre_headpose, sigma_scale: float, device="cuda:0", max_chunk_samples: int = 16000, feature_opt=None, headpose_opt=None,
-                 generator=None):
-        import torch
-        self.torch = torch
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("LiveAudioFrontEnd runs on the MI355X only: device must be a GPU (there is no CPU path)")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if getattr(APC_model, "rnn_residual", False):
-            raise NotImplementedError("residual APC stacks are not supported (no shipped config enables them)")
-        fo = feature_opt if feature_opt is not None else Audio2Feature.opt
-        ho = headpose_opt if headpose_opt is not None else Audio2Headpose.opt
-        if getattr(ho, "feature_decoder", "WaveNet") != "WaveNet":
-            raise NotImplementedError("the live path generates head poses with the WaveNet decoder only (the LSTM decoder is in no shipped config)")
-        if max_chunk_samples < 1:
-            raise ValueError("max_chunk_samples must be >= 1")
-        self.device = dev
-        self.ff_mouth, self.ff_head = int(fo.frame_future), int(ho.frame_future)
-        self.sched = LiveScheduler(self.ff_mouth, self.ff_head, max_chunk_samples)
-        self.use_lle, self.knear, self.lle_percent = bool(use_LLE), int(Knear), float(LLE_percent)
-        self.sigma_scale = float(sigma_scale)
-        self.generator = generator
-        self.nd, self.nc, self.gmm = int(ho.A2H_GMM_ndim), int(ho.A2H_GMM_ncenter), ho.loss == "GMM"
-        f32 = dict(dtype=torch.float32, device=dev)
-        # the stages' engines (built, bound and sized here, once)
-        max_win = 2 * (max_chunk_samples // MEL_WIN + 2) + 2                   # windows that one step can make final
-        max_pairs = max_win // 2 + 1
-        self.apc_eng = APC_model._get_engine(dev, max_win)
-        a2f = Audio2Feature.Audio2Feature
-        a2f = a2f.module if hasattr(a2f, "module") else a2f
-        self.a2f_pk = a2f._pack(dev, max_pairs + self.ff_mouth)
-        net = Audio2Headpose._net()
-        # a head-pose engine of its own: its workspace is this session's projection ring (whole-clip calls would overwrite a shared one)
-        from .a2h_engine import HeadposeEngine
-        o = net.opt
-        self.a2h_eng = HeadposeEngine(o.A2H_wavenet_residual_layers, o.A2H_wavenet_residual_blocks, o.A2H_wavenet_residual_channels,
-                                  o.A2H_wavenet_dilation_channels, o.A2H_wavenet_skip_channels, o.A2H_wavenet_kernel_size,
-                                  o.A2H_wavenet_input_channels, o.A2H_wavenet_cond_channels, o.APC_hidden_size,
-                                  o.A2H_GMM_ncenter, o.A2H_GMM_ndim, o.loss, max_audio_frames=max_pairs + self.ff_head + 1)
-        self.a2h_eng.load_state_dict({k: v for k, v in net.state_dict().items() if not k.endswith("num_batches_tracked")})
-        self.a2h_eng.bind(dev)
-        self.db = torch.as_tensor(np.ascontiguousarray(APC_feat_database, np.float32)).to(dev) if self.use_lle else None
-        self.pre = torch.as_tensor(np.ascontiguousarray(np.asarray(pre_headpose, np.float32).reshape(-1))).to(dev)
-        from . import _native as N
-        lib = N.load()
-        self.mel_ws = torch.empty(int(lib.lspmel_workspace_bytes(max_win)), dtype=torch.uint8, device=dev)
-        self.scap = max_chunk_samples + 4 * MEL_WIN                              # samples not yet consumed + one step
-        self.sbuf = torch.empty(self.scap, **f32)
-        self.sbase = self.slen = 0                                               # sbuf[j] = stream sample sbase + j
-        self.apc_state = [torch.zeros(self.apc_eng.state_floats(), **f32) for _ in range(2)]
-        self.lstm_state = [torch.zeros(self.a2f_pk["lstm"].state_floats(), **f32) for _ in range(2)]
-        self.a2h_state = [torch.zeros(self.a2h_eng.state_bytes(), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.apc_i = self.lstm_i = self.a2h_i = 0                                # which buffer holds the current state
-        self.a2h_started = False
-        H = APC_model.hidden_size
-        self.last = torch.zeros(1, H, **f32)                                     # the newest LLE row (odd row of a pair, and the tail)
-        self.pend = torch.zeros(self.a2h_eng.max_audio_frames, 2 * H, **f32)         # pair rows not yet handed to the head-pose generator
-        self.pend_row0 = self.pend_n = 0
-        self._mel = self._feats = self._rows = self._x = None
-        self._out_mouth: list = []
-        self._out_pose: list = []
-
-    # ---- the stages (run_plan calls them in order) ----------------------------------------------------------------------
-    def feed(self, samples, first: int, keep_from: int) -> None:
-        keep = keep_from - self.sbase                                           # samples before the next window are no longer read
-        if keep > 0:
-            self.sbuf[: self.slen - keep] = self.sbuf[keep: self.slen].clone()
-            self.sbase += keep
-            self.slen -= keep
-        n = samples.shape[0]
-        if self.slen + n > self.scap or first != self.sbase + self.slen:
-            raise RuntimeError("internal: sample buffer overflow or gap")
-        self.sbuf[self.slen: self.slen + n] = samples
-        self.slen += n
-
-    def mel(self, w0: int, w1: int, ended: bool) -> None:
-        from . import mel as mel_mod
-        off = window_start(w0) - self.sbase
-        self._mel = mel_mod.compute_mel_range(self.sbuf[off: self.slen], self.sbase + off, w0, w1 - w0, ended, workspace=self.mel_ws)
-
-    def apc(self, w0: int, w1: int) -> None:
-        i = self.apc_i
-        self._feats = self.apc_eng.forward_state(self._mel, self.apc_state[i] if w0 > 0 else None, self.apc_state[1 - i])
-        self.apc_i = 1 - i
-
-    def lle(self, w0: int, w1: int) -> None:
-        from . import manifold
-        f = self._feats
-        if self.use_lle:
-            f = manifold.project(f, self.db, self.knear, self.lle_percent)
-        self._rows = self.torch.cat([self.last, f]) if w0 % 2 else f            # LLE rows from 2 * (w0 // 2) on
-        self.last = f[-1:].clone()                                              # the odd row of the next pair; the tail at the end
-
-    def pairs(self, p0: int, p1: int) -> None:
-        x = self._rows[: 2 * (p1 - p0)].reshape(p1 - p0, -1)
-        if self.pend_n + (p1 - p0) > self.pend.shape[0]:
-            raise RuntimeError("internal: head-pose row buffer overflow")
-        self.pend[self.pend_n: self.pend_n + (p1 - p0)] = x                    # waits there until the head-pose generator takes it
-        self._x = (p0, self.pend[self.pend_n: self.pend_n + (p1 - p0)])
-        self.pend_n += p1 - p0
-
-    def mouth(self, steps, npairs: int, frames) -> None:
-        torch = self.torch
-        a0, a1 = steps
-        parts = []
-        if a0 < npairs:
-            p0, x = self._x
-            if p0 != a0 or p0 + x.shape[0] != npairs:
-                raise RuntimeError("internal: Audio2Feature steps out of step with the pair rows")
-            parts.append(x)
-        if a1 > npairs:                                                         # the tail (finish): the last LLE row repeated
-            parts.append(self.last.expand(2 * (a1 - max(a0, npairs)), -1).reshape(-1, 2 * self.last.shape[1]))
-        x = torch.cat(parts) if len(parts) > 1 else parts[0].contiguous()
-        pk = self.a2f_pk
-        i = self.lstm_i
-        h = pk["lstm"].forward_state(pk["d3"](pk["d0"](x)), self.lstm_state[i] if a0 > 0 else None, self.lstm_state[1 - i])
-        self.lstm_i = 1 - i
-        y = pk["f6"](pk["f3"](pk["f0"](h)))
-        m0, m1 = frames
-        if m1 > m0:
-            self._out_mouth.append((m0, y[m0 + self.ff_mouth - a0:]))
-
-    def poses(self, rows, frames) -> None:
-        torch = self.torch
-        (r0, r1), (h0, h1) = rows, frames
-        if r0 != self.pend_row0 or r1 != self.pend_row0 + self.pend_n:
-            raise RuntimeError("internal: head-pose rows out of step")
-        nf = h1 - h0
-        noise = expq = None
-        if self.gmm:
-            g = self.generator
-            noise = torch.empty(nf, self.nd)
-            expq = torch.empty(nf, self.nc)
-            for k in range(nf):                 # draw_gmm_noise's order: the Exp(1) draws of multinomial, then randn, per frame
-                expq[k] = torch.empty(1, self.nc).exponential_(1, generator=g)[0]
-                noise[k] = torch.randn(1, self.nd, generator=g).float()[0]
-            noise = noise.to(self.device)
-            expq = expq.to(self.device) if self.nc > 1 else None
-        i = self.a2h_i
-        out = self.a2h_eng.generate_resume(self.pend[: self.pend_n] if self.pend_n else None, self.pend_row0, self.pre, noise, expq,
-                                           self.sigma_scale, self.ff_head, h0, nf, self.a2h_state[i] if self.a2h_started else None,
-                                           self.a2h_state[1 - i])
-        self.a2h_i, self.a2h_started = 1 - i, True
-        self.pend_row0 += self.pend_n
-        self.pend_n = 0
-        self._out_pose.append((h0, out))
-
-    # ---- public --------------------------------------------------------------------------------------------------------
-    def _run(self, plans, samples, host: bool) -> LiveFrames:
-        torch = self.torch
-        self._out_mouth, self._out_pose = [], []
-        off = 0
-        for plan in plans:
-            n = plan.samples[1] - plan.samples[0]
-            run_plan(self, plan, samples[off: off + n] if n else None)
-            off += n
-        # the status words, once per push (each read waits for the stream)
-        for eng, what in ((self.apc_eng, "APC GRU"), (self.a2f_pk["lstm"], "Audio2Feature LSTM")):
-            code = eng.status()
-            if code != 0:
-                raise RuntimeError("%s: inter-workgroup hand-off timed out (status 0x%x); the live session cannot continue" % (what, code))
-        if self._out_pose:
-            code = self.a2h_eng.status()
-            if code != 0:
-                raise RuntimeError("head-pose generator: status 0x%x (the carried state did not match its frame)" % code)
-        mouth = torch.cat([t for _, t in self._out_mouth]) if self._out_mouth else torch.empty(0, self._mouth_dim(), device=self.device)
-        poses = torch.cat([t for _, t in self._out_pose]) if self._out_pose else torch.empty(0, self.nd, device=self.device)
-        m0 = self._out_mouth[0][0] if self._out_mouth else self.sched.m
-        h0 = self._out_pose[0][0] if self._out_pose else self.sched.h
-        self._mel = self._feats = self._rows = self._x = None
-        if host:
-            mouth, poses = mouth.cpu().numpy(), poses.cpu().numpy()
-        return LiveFrames(mouth, m0, poses, h0)
-
-    def _mouth_dim(self) -> int:
-        return int(self.a2f_pk["f6"].out_features)
-
-    def _samples(self, samples):
-        torch = self.torch
-        if isinstance(samples, torch.Tensor):
-            if samples.dtype != torch.float32 or samples.dim() != 1:
-                raise ValueError("samples must be a 1-d float32 array of 16 kHz audio (got %s %s)" % (samples.dtype, tuple(samples.shape)))
-            return samples.to(self.device).contiguous()
-        a = np.asarray(samples)
-        if a.dtype != np.float32 or a.ndim != 1:
-            raise ValueError("samples must be a 1-d float32 array of 16 kHz audio (got %s %s)" % (a.dtype, a.shape))
-        return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+                 generator=None, prime_steps_per_tick: int = 16):
+        from .live_pool import LiveSessionPool
+        self.pool = LiveSessionPool(APC_model, Audio2Feature, Audio2Headpose, APC_feat_database, use_LLE, Knear, LLE_percent,
+                                    sigma_scale=sigma_scale, device=device, max_sessions=1, max_chunk_samples=max_chunk_samples,
+                                    feature_opt=feature_opt, headpose_opt=headpose_opt, prime_steps_per_tick=prime_steps_per_tick)
+        self.sid = self.pool.open(pre_headpose, generator)
+        self.ff_mouth, self.ff_head = self.pool.ff_mouth, self.pool.ff_head
+        self.sched = self.pool.plan.sched[self.sid]                              # held here: it outlives the close that finish() causes
+        self.ended = False
 
     def push(self, samples, host: bool = False) -> LiveFrames:
         """Take float32 16 kHz samples (host array or device tensor, any length); return the frames that became final."""
-        if self.sched.ended:
+        if self.ended:
             raise RuntimeError("the clip has ended (finish() was called): no more audio can be pushed")
-        x = self._samples(samples)
-        with self.torch.cuda.device(self.device):
-            return self._run(self.sched.plan_push(x.shape[0]), x, host)
+        return self.pool.tick({self.sid: samples}, host=host)[self.sid]
 
     def finish(self, host: bool = False) -> LiveFrames:
         """End of the clip: the zero-padded last windows, the Audio2Feature tail and the remaining head poses."""
-        with self.torch.cuda.device(self.device):
-            return self._run([self.sched.plan_finish()], None, host)
+        if self.ended:
+            raise RuntimeError("finish() was already called")
+        self.ended = True
+        return self.pool.tick(finish=[self.sid], host=host)[self.sid]

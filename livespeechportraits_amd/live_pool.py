@@ -1,5 +1,5 @@
-"""Many live audio streams from one pool: ``LiveSessionPool`` advances up to 16 independent ``LiveAudioFrontEnd``-like sessions with
-ONE call per stage and tick, whatever the number of open sessions (DESIGN.md "Live session pool").
+"""The device side of the live audio path, written once: ``LiveSessionPool`` advances 1..16 independent live sessions with ONE call per
+stage and tick, whatever the number of open sessions (DESIGN.md "Live session pool").  ``live.LiveAudioFrontEnd`` is a pool of one.
 
 The sessions share the models, the packed weights and the feature database; each has its own ``LiveScheduler`` (unchanged rules) and a
 ``PrimingPlanner`` that spreads the head-pose WaveNet's priming over the ticks.  ``run_pool_round`` merges the sessions' plans of one round
@@ -19,10 +19,13 @@ MAX_SESSIONS = 16          # LSPRNN_MAX_SEQUENCES == LSPA2H_MAX_STREAMS == LSPME
 
 def run_pool_round(backend, work) -> None:
     """One round of a tick.  ``work``: (key, LivePlan, samples, rows, steps) per session that has something to do, in ascending key order;
-    rows / steps come from the session's PrimingPlanner.  Each stage of ``backend`` is called at most once, with the sessions that take
-    part in it (run_plan's stages, each taking a list):
-    feed [(key, samples, first_sample, keep_from)]      mel [(key, w0, w1, ended)]      apc / lle [(key, w0, w1)]
-    pairs [(key, p0, p1)]      mouth [(key, steps, npairs, frames)]      poses [(key, rows, steps, frames)]"""
+    rows / steps come from the session's PrimingPlanner.  Each stage of ``backend`` is called at most once, in this order, with the
+    sessions that take part in it:
+    feed [(key, samples, first_sample, keep_from)]   append the new samples; samples before `keep_from` are no longer read
+    mel [(key, w0, w1, ended)]   apc / lle [(key, w0, w1)]   windows == rows [w0, w1)
+    pairs [(key, p0, p1)]                     pair rows [p0, p1) from LLE rows [2 p0, 2 p1)
+    mouth [(key, steps, npairs, frames)]      Audio2Feature steps [a0, a1) (>= npairs: the tail); emit mouth frames [m0, m1)
+    poses [(key, rows, steps, frames)]        hand pair rows [r0, r1) to the head-pose generator, run its steps [s0, s1); emit poses [h0, h1)"""
     feed = [(k, smp, p.samples[0], window_start(p.windows[0])) for k, p, smp, _, _ in work if p.samples[1] > p.samples[0]]
     if feed:
         backend.feed(feed)
@@ -133,16 +136,19 @@ class _Slot:
 class LiveSessionPool:
     """Up to ``max_sessions`` (<= 16) live streams on one device, advanced together.
 
-    Built from what LiveAudioFrontEnd takes, minus the per-session ``pre_headpose`` / ``generator`` (arguments of ``open``).  ``tick``
+    Built from what demo.py:146-166 builds and reads from the config (see LiveAudioFrontEnd, the pool of one); the per-session
+    ``pre_headpose`` / ``generator`` are arguments of ``open``.  ``tick``
     pushes samples to any subset of the open sessions and returns each one's LiveFrames; per stage it makes one call, so the number of
-    launches per tick does not depend on the number of sessions.  A session's outputs are bit for bit those of LiveAudioFrontEnd / the
+    launches per tick does not depend on the number of sessions.  A session's outputs are bit for bit those of the
     whole-clip path on its own audio, whoever else is in the pool.  The head-pose WaveNet's priming (field - 1 steps before pose 0) runs
     ``prime_steps_per_tick`` steps per tick from the first pair row on, so a session that joins does not stall the others' tick.
     GMM noise: per session, per head-pose frame, in frame order, from the session's ``generator`` in draw_gmm_noise's order; sessions
     opened with ``generator=None`` share the global generator, and the draws of a round go in ascending session id -- so with the global
     generator a session's poses depend on who else draws; give every session its own generator for poses that do not.
     Device memory is fixed at construction.  The status words are read once per round (a tick is one round unless a push is longer
-    than ``max_chunk_samples``); a lost hand-off ends the pool with an error."""
+    than ``max_chunk_samples``); a lost inter-workgroup hand-off (another stream holding the CUs for the whole time-out) ends the pool
+    with an error.  Every stage keeps its input state in a buffer of its own (two per stage and slot, used in turn), so a caller that
+    drives the C entry points directly can run a failed call again from the same state."""
 
     def __init__(self, APC_model, Audio2Feature, Audio2Headpose, APC_feat_database, use_LLE: bool, Knear: int, LLE_percent: float,
                  sigma_scale: float = 0.3, device="cuda:0", max_sessions: int = 16, max_chunk_samples: int = 16000, feature_opt=None,
@@ -171,13 +177,14 @@ class LiveSessionPool:
         self.sigma_scale = float(sigma_scale)
         self.nd, self.nc, self.gmm = int(ho.A2H_GMM_ndim), int(ho.A2H_GMM_ncenter), ho.loss == "GMM"
         f32 = dict(dtype=torch.float32, device=dev)
-        max_win = 2 * (max_chunk_samples // MEL_WIN + 2) + 2                   # windows that one step can make final (as LiveAudioFrontEnd)
+        max_win = 2 * (max_chunk_samples // MEL_WIN + 2) + 2                   # windows that one step can make final
         max_pairs = max_win // 2 + 1
         self.apc_eng = APC_model._get_engine(dev, S * max_win)
         a2f = Audio2Feature.Audio2Feature
         a2f = a2f.module if hasattr(a2f, "module") else a2f
         self.a2f_pk = a2f._pack(dev, S * (max_pairs + self.ff_mouth))
         net = Audio2Headpose._net()
+        # a head-pose engine of its own: its workspace holds the sessions' projection rings (whole-clip calls would overwrite a shared one)
         from .a2h_engine import HeadposeEngine
         o = net.opt
         ring = max_pairs + self.ff_head + 1                                    # >= PrimingPlanner.ring_rows_needed(ff_head, max_pairs)

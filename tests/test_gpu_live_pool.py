@@ -405,21 +405,28 @@ def test_pool_sessions_equal_whole_clip(models, scenario_refs, kw):
 
 
 def test_pool_of_one_equals_front_end(models):
+    """LiveAudioFrontEnd is a pool of one, so the comparison with a pool session pins the wrapper's mapping (start indices, finish, the
+    generator handed over); the independent leg is the whole-clip path, which the pool session's rows equal bit for bit."""
     wave = wave_of(CLIP_SAMPLES, seed=31)
+    ref_mouth, ref_poses = whole_clip(models, wave, seed=5)
     pieces = frame_pieces(16000) + _random_pieces(CLIP_SAMPLES - 16000, 3)
     fe = session(models, generator=torch.Generator().manual_seed(5))
     pool = pool_of(models, max_sessions=1)
     sid = pool.open(np.zeros(12, np.float32), generator=torch.Generator().manual_seed(5))
-    pos = 0
+    pos, mouth, poses = 0, [], []
     for k in pieces:
         a = fe.push(wave[pos:pos + k], host=True)
         b = pool.tick({sid: wave[pos:pos + k]}, host=True)[sid]
         pos += k
         assert (a.mouth_start, a.pose_start) == (b.mouth_start, b.pose_start)
         assert np.array_equal(a.mouth, b.mouth) and np.array_equal(a.poses, b.poses), "at sample %d" % pos
+        mouth.append(b.mouth)
+        poses.append(b.poses)
     a, b = fe.finish(host=True), pool.tick(finish=[sid], host=True)[sid]
     assert (a.mouth_start, a.pose_start) == (b.mouth_start, b.pose_start)
     assert np.array_equal(a.mouth, b.mouth) and np.array_equal(a.poses, b.poses)
+    assert np.array_equal(np.concatenate(mouth + [b.mouth]), ref_mouth)
+    assert np.array_equal(np.concatenate(poses + [b.poses]).astype(np.float64), ref_poses)
     # device tensors in, device tensors out
     sid = pool.open(np.zeros(12, np.float32))
     out = pool.tick({sid: torch.from_numpy(wave[:8000]).to(DEV)}, finish=[sid])[sid]
@@ -515,8 +522,8 @@ def test_pool_refusals(models, tmp_path):
 def test_pool_real_time(models):
     """16 sessions opened two ticks apart, each pushed one frame of audio per tick over the 687-frame clip, with the feature database of
     bench.py's pipeline (30 000 rows).  The whole pool's tick (call -> frames of all sessions on the host) must fit a frame time, 1/60 s:
-    the bound of test_session_real_time, derived from demo.py's 60 fps.  The parent commit's way of serving 16 streams -- 16
-    LiveAudioFrontEnd objects pushed one after another -- is timed in the same process; only the direction is asserted."""
+    the bound of test_session_real_time, derived from demo.py's 60 fps.  The other way of serving 16 streams -- 16 pools of one
+    (LiveAudioFrontEnd objects) pushed one after another -- is timed in the same process; only the direction is asserted."""
     from livespeechportraits_amd import synth
     m = dict(models, db=synth.make_feature_database(30000, 8, 512, 24)[0])
     wave = wave_of(CLIP_SAMPLES, seed=11)
@@ -549,7 +556,7 @@ def test_pool_real_time(models):
     q50, q99 = np.percentile(fes[full], 50), np.percentile(fes[full], 99)
     print("\n[live pool] 16 sessions, tick: p50 %.3f ms, p99 %.3f ms, max %.3f ms (ticks with all 16: p50 %.3f ms)"
           % (p50 * 1e3, p99 * 1e3, tp.max() * 1e3, np.percentile(tp[full], 50) * 1e3))
-    print("[live pool] 16 LiveAudioFrontEnd objects one after another, ticks with all 16: p50 %.3f ms, p99 %.3f ms, max %.3f ms; ratio of the p50s %.2f"
+    print("[live pool] 16 pools of one (LiveAudioFrontEnd) one after another, ticks with all 16: p50 %.3f ms, p99 %.3f ms, max %.3f ms; ratio of the p50s %.2f"
           % (q50 * 1e3, q99 * 1e3, fes[full].max() * 1e3, q50 / np.percentile(tp[full], 50)))
     assert p99 < 1.0 / 60
     assert np.percentile(tp[full], 50) < q50

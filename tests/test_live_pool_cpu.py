@@ -199,7 +199,7 @@ def test_priming_planner(field, ff, per_tick):
             # the point of the slices: from the first pair row on there are ff ticks before pose 0, enough for every step that reads row 0
             first_pose_tick = min(frame_tick)
             assert per_tick_steps[first_pose_tick] <= max(per_tick, ff), "%s: priming left for the tick of pose 0: %d steps" % (name, per_tick_steps[first_pose_tick])
-    # LiveAudioFrontEnd's ring (max_pairs + ff + 1 rows) is long enough
+    # LiveSessionPool's ring (max_pairs + ff + 1 rows) is long enough
     assert PrimingPlanner.ring_rows_needed(ff, 10) <= 10 + ff + 1
     with pytest.raises(ValueError):
         PrimingPlanner(field, ff, 0)

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Latency of the live audio front-end (livespeechportraits_amd/live.py) on the GPU, recorded to profiles/<name>.json (+ .txt).
+"""Latency of the live audio front-end (livespeechportraits_amd/live.py: LiveAudioFrontEnd, a LiveSessionPool of one) on the GPU,
+recorded to profiles/<name>.json (+ .txt).
 Synthetic weights and stand-in data from `synth`, as bench.py's pipeline_extra uses them (APC 3x GRU-512, Audio2Feature, the default
 head-pose WaveNet, a 30 000-row feature database, a 687-frame = 183 200-sample clip):
   (a) per-push wall time, from the call to the returned frames being on the host, for pushes of exactly one frame of audio (alternating
       266 and 267 samples) over the whole clip: p50, p99, max; and the total time of that stream (pushes + finish);
-  (b) the whole-clip audio stages of the parent path in the same session: mel.compute_mel -> APC_encoder -> manifold.project ->
+  (b) the whole-clip audio stages (all the audio at once) in the same session: mel.compute_mel -> APC_encoder -> manifold.project ->
       Audio2FeatureModel / Audio2HeadposeModel.generate_sequences, median of 3 after a warm-up.
     python tools/live_latency.py [name, default live_latency] [output directory, default profiles/]"""
 import argparse
@@ -111,7 +112,7 @@ for _ in range(3):
     whole()
     wt.append(time.perf_counter() - t0)
 rec["b"] = {"whole_clip_s": sorted(round(v, 4) for v in wt)}
-say("(b) whole clip, parent path (compute_mel -> APC_encoder -> manifold.project -> generate_sequences x2): %s s (median %.3f s)"
+say("(b) whole clip at once (compute_mel -> APC_encoder -> manifold.project -> generate_sequences x2): %s s (median %.3f s)"
     % (rec["b"]["whole_clip_s"], sorted(wt)[1]))
 os.makedirs(out_dir, exist_ok=True)
 with open(os.path.join(out_dir, name + ".json"), "w") as fh:

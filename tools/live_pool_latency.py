@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Latency of the live session pool (livespeechportraits_amd/live_pool.py) against the parent's way of serving several streams, recorded to
+"""Latency of the live session pool (livespeechportraits_amd/live_pool.py) against serving every stream from a pool of one, recorded to
 profiles/<name>.txt (+ .json).  Set-up as tools/live_latency.py (synthetic weights, 30 000-row database, the 687-frame clip).
   (a) per tick p50 / p99 / max, call to frames of all sessions on the host, for S in {1, 2, 4, 8, 16} sessions that each push one frame of
-      audio per tick, opened two ticks apart; and the same S served by S separate LiveAudioFrontEnd objects pushed one after another (the
-      parent commit's code path), alternated pool - objects - pool - objects per S so that box noise shows.  The percentiles are over the
+      audio per tick, opened two ticks apart; and the same S served by S pools of one (LiveAudioFrontEnd objects) pushed one after
+      another, alternated pool - objects - pool - objects per S so that box noise shows.  The percentiles are over the
       ticks in which all S sessions push.
   (b) the max tick of one session with prime_steps_per_tick 16 against 254 (priming in one go).
-  (c) 60 fps streams one process sustains = 1 / (60 x p50 tick / S) at the best S, beside the parent's figure from (a) at S = 1.
+  (c) 60 fps streams one process sustains = 1 / (60 x p50 tick / S) at the best S, beside the pools-of-one figure from (a) at S = 1.
 `--trace S TICKS`: no timing, only 2 (S - 1) + 40 + TICKS ticks of S sessions, for a `rocprofv3 --kernel-trace --stats` run of its own (own
 process after `--`, no counters in it).  Two such runs that differ only in TICKS differ by TICKS steady-state ticks (every session past its
 priming), so `--diff A_results.db B_results.db TICKS` prints launches and device time per steady tick, per kernel:
@@ -145,16 +145,16 @@ for S in (1, 2, 4, 8, 16):
     runs = [("pool", run_pool(S)), ("objects", run_objects(S)), ("pool", run_pool(S)), ("objects", run_objects(S))]
     rec["a"][S] = [(kind, stat(ts[full])) for kind, ts in runs]
     for kind, ts in runs:
-        say("    S = %2d  %-28s %s" % (S, "LiveSessionPool.tick" if kind == "pool" else "S LiveAudioFrontEnd.push", fmt(stat(ts[full]))))
+        say("    S = %2d  %-28s %s" % (S, "LiveSessionPool.tick" if kind == "pool" else "S pools of one, .push", fmt(stat(ts[full]))))
     p50 = min(d["p50_ms"] for kind, d in rec["a"][S] if kind == "pool")
     if best is None or p50 / S < best[1] / best[0]:
         best = (S, p50)
 say("(b) one session, max tick over the whole clip: prime_steps_per_tick 16: %.3f ms; 254 (priming in one go): %.3f ms"
     % (run_pool(1, prime_steps_per_tick=16).max() * 1e3, run_pool(1, prime_steps_per_tick=254).max() * 1e3))
-parent = min(d["p50_ms"] for kind, d in rec["a"][1] if kind == "objects")
-rec["c"] = {"best_S": best[0], "pool_streams_60fps": round(1e3 / (60 * best[1] / best[0]), 1), "parent_streams_60fps": round(1e3 / (60 * parent), 1)}
-say("(c) 60 fps streams one process sustains, 1 / (60 x p50 tick / S): pool %.1f (S = %d); S separate LiveAudioFrontEnd objects %.1f"
-    % (rec["c"]["pool_streams_60fps"], best[0], rec["c"]["parent_streams_60fps"]))
+single = min(d["p50_ms"] for kind, d in rec["a"][1] if kind == "objects")
+rec["c"] = {"best_S": best[0], "pool_streams_60fps": round(1e3 / (60 * best[1] / best[0]), 1), "pools_of_one_streams_60fps": round(1e3 / (60 * single), 1)}
+say("(c) 60 fps streams one process sustains, 1 / (60 x p50 tick / S): pool %.1f (S = %d); S separate pools of one (LiveAudioFrontEnd) %.1f"
+    % (rec["c"]["pool_streams_60fps"], best[0], rec["c"]["pools_of_one_streams_60fps"]))
 os.makedirs(out_dir, exist_ok=True)
 with open(os.path.join(out_dir, name + ".json"), "w") as fh:
     json.dump(rec, fh, indent=1)
