@@ -60,11 +60,24 @@
  * A block with progressive files costs ONE more launch, whatever their number: jpegdec_progressive, one wave per progressive file, which zeroes
  * the file's coefficients and walks its scans in file order over them (a refinement needs what the earlier scans left).  Stages 2 and 3 then run
  * once for all files; baseline and progressive files mix freely.  Not done: parallelism inside a progressive file (the restart intervals of one
- * scan, or independent scans, on several waves): two waves writing different coefficients of one block would break the 16-byte block moves.
- * Progressive files are decoded in parallel with each other only, as baseline files without restart markers are.
+ * scan, or independent scans, on several waves): two waves writing different coefficients of one block would break the 16-byte block moves, and a
+ * refinement scan reads what the earlier scans left.  That stays out of scope under LSPJPEG_DEC_FLAG_PARALLEL too: progressive files are decoded
+ * in parallel with each other only.
  * For a progressive file lspjpeg_dec_info.restart_interval is the interval in force at the first scan, mcus the interleaved MCUs of the frame,
  * segments the restart intervals of ALL scans, scan_offset / scan_bytes the bytes from the first scan's data up to the EOI marker (the markers
  * between the scans included); default_tables is 0.
+ *
+ * Parallel decode INSIDE a restart interval of a baseline file is an option: LSPJPEG_DEC_FLAG_PARALLEL in lspjpeg_dec_plan_flags()
+ * (lspjpeg_dec_probe_flags() accepts the flag and ignores it).  Without the flag nothing above changes: the block is byte for byte the same and
+ * the same kernels run.  Under the flag every restart interval of every baseline file is cut into subsequences of a fixed number of bytes of the
+ * stuffed stream (lspjpeg_dec_plan_parallel() reports it), and stage 1 of those files is ONE launch of another kernel, jpegdec_entropy_parallel:
+ * one workgroup per restart interval whose lanes each decode one subsequence from a guessed parser state, repair the guesses by handing exit
+ * states on until nothing changes (self-synchronising Huffman decoding, Weissenberger and Schmidt 2018 / 2021: exact, because the first lane's
+ * state is true; uncapped, so at the worst as slow as the serial walk), and then write the coefficients in today's layout.  Status words are the
+ * serial decoder's for every file, the earliest failure in stream order inside an interval included; stages 2 and 3 are untouched.
+ * lspjpeg_dec_decode() under the flag still enqueues 3 launches whatever the content (4 when the block holds progressive files, which go through
+ * jpegdec_progressive exactly as without the flag), synchronises nothing and allocates nothing; the route keeps its state in LDS, so
+ * summary.workspace_bytes does not grow.  The flag combines freely with LSPJPEG_DEC_FLAG_PROGRESSIVE.
  *
  * Conventions as in lspjpeg.h: device pointers, nothing allocated on the device by the library, no synchronisation, everything enqueued on the
  * given hipStream_t, no environment reads; returns 0 or a negative code (lspjpeg_dec_last_error()).
@@ -125,6 +138,7 @@ typedef struct lspjpeg_dec_summary {
 
 /* flags of lspjpeg_dec_probe_flags / lspjpeg_dec_plan_flags */
 #define LSPJPEG_DEC_FLAG_PROGRESSIVE 1u
+#define LSPJPEG_DEC_FLAG_PARALLEL 2u    /* baseline files: stage 1 decodes inside a restart interval in parallel (plan only; the probe ignores it) */
 #define LSPJPEG_DEC_MAX_SCANS 64    /* of one progressive file; more is UNSUPPORTED */
 
 /* one scan of a progressive file, as the planner recorded it */
@@ -157,6 +171,9 @@ int64_t lspjpeg_dec_plan_flags(const unsigned char *const *files, const size_t *
 /* for checks: the number of scans of file i (0 for a file that was not planned as a progressive one), and scan s of it */
 int lspjpeg_dec_plan_scans(const void *blob, int i);
 int lspjpeg_dec_plan_scan(const void *blob, int i, int s, lspjpeg_dec_scan *out);
+/* for checks: how restart interval k (as lspjpeg_dec_plan_segment counts them) is cut under LSPJPEG_DEC_FLAG_PARALLEL: the bytes of one
+ * subsequence and their number.  Negative on a block planned without the flag. */
+int lspjpeg_dec_plan_parallel(const void *blob, int k, uint32_t *subseq_bytes, uint32_t *subsequences);
 int lspjpeg_dec_summary_of(const void *blob, lspjpeg_dec_summary *out);
 /* what the planner recorded, for checks: file i's info (scan_offset is then the offset of its data inside the block), its quantisation table of
  * component c in natural order, and segment k as (file, first MCU, MCUs, begin, end) with begin / end offsets inside the block */
@@ -167,6 +184,10 @@ int lspjpeg_dec_plan_segment(const void *blob, int k, uint32_t *file, uint32_t *
  * Returns the file's status word after stage 1 (>= 0) or a negative code; out must hold mcus * blocks-per-MCU * 64 values, and its content
  * means something only on status 0.  A progressive file's scans are run in file order with the procedures the kernel runs. */
 int lspjpeg_dec_host_coefficients(const void *blob, int i, int16_t *out, size_t cap_values);
+/* for checks: what this thread's last lspjpeg_dec_host_coefficients did on a block planned with LSPJPEG_DEC_FLAG_PARALLEL (it then runs the kernel's
+ * subsequence decoder, fixed point and write pass with the lanes as loops): the most rounds the fixed point took in any chunk, and the number of
+ * true entry states that stood inside a block.  Both 0 for any other block. */
+int lspjpeg_dec_host_parallel_stats(uint32_t *rounds, uint32_t *midblock_entries);
 
 /* Enqueues the three stages (and, between stages 1 and 2, the progressive files' launch when the block holds any).  blob_host is the planner's block, blob_dev its copy on the device (16-byte aligned; the kernels write only its
  * status words), workspace_dev 256-byte aligned with summary.workspace_bytes bytes; its content on entry is irrelevant. */

@@ -364,6 +364,8 @@ JPEGDEC_SIGNATURES = {
     "lspjpeg_dec_plan_scans": (c_int, [c_void_p, c_int]),
     "lspjpeg_dec_plan_scan": (c_int, [c_void_p, c_int, c_int, POINTER(JpegDecScan)]),
     "lspjpeg_dec_summary_of": (c_int, [c_void_p, POINTER(JpegDecSummary)]),
+    "lspjpeg_dec_plan_parallel": (c_int, [c_void_p, c_int, POINTER(ctypes.c_uint32), POINTER(ctypes.c_uint32)]),
+    "lspjpeg_dec_host_parallel_stats": (c_int, [POINTER(ctypes.c_uint32), POINTER(ctypes.c_uint32)]),
     "lspjpeg_dec_plan_file": (c_int, [c_void_p, c_int, POINTER(JpegDecInfo)]),
     "lspjpeg_dec_plan_qtable": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "lspjpeg_dec_plan_segment": (c_int, [c_void_p, c_int, POINTER(ctypes.c_uint32), POINTER(ctypes.c_uint32), POINTER(ctypes.c_uint32),

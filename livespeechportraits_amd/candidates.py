@@ -36,7 +36,7 @@ def candidate_paths(data_root: str) -> list:
 
 
 def load_candidates(paths_or_data_root: Union[str, Sequence], device="cuda:0", size: int = 512, decoder=None, resize=None, resizer=None,
-                    progressive: bool = False) -> torch.Tensor:
+                    progressive: bool = False, parallel: bool = False) -> torch.Tensor:
     """float32 ``[1, 12, size, size]`` on ``device`` from four JPEG files: a data root (``<root>/candidates/normalized_full_{0..3}.jpg``), four
     paths, or four ``bytes`` objects.  Files that are not 3-component ``size`` x ``size`` are refused (ValueError); files the decoder
     cannot take raise jpeg.JpegError.
@@ -46,7 +46,9 @@ def load_candidates(paths_or_data_root: Union[str, Sequence], device="cuda:0", s
     above.  ``resizer``: a resize.Resizer to reuse.
 
     ``progressive``: complete progressive files (SOF2, what photo tools and the web mostly export) are taken as well, to the pixels Pillow
-    returns for them; handed on to the decoder this call creates (a ``decoder`` passed in decides for itself)."""
+    returns for them; handed on to the decoder this call creates (a ``decoder`` passed in decides for itself).
+
+    ``parallel``: the decoder this call creates decodes inside each file in parallel (jpeg.JpegDecoder's ``parallel``); the tensor is the same."""
     from .jpeg import JpegDecoder, probe
     if resize is not None:
         from .resize import Resizer, check_filter
@@ -69,7 +71,7 @@ def load_candidates(paths_or_data_root: Union[str, Sequence], device="cuda:0", s
                 raise ValueError("candidate %d is %dx%d with %d components, the generator takes %dx%d RGB" % (j, i.width, i.height, i.components, size, size))
             other.append((j, max(i.width, i.height)))
     device = torch.device(device)
-    decoder = decoder or JpegDecoder(device, max_side=max([size] + [side for _, side in other]), max_batch=CANDIDATES, progressive=progressive)
+    decoder = decoder or JpegDecoder(device, max_side=max([size] + [side for _, side in other]), max_batch=CANDIDATES, progressive=progressive, parallel=parallel)
     out = torch.empty((3 * CANDIDATES, size, size), dtype=torch.float32, device=device)
     table = torch.from_numpy(normalisation_table()).to(device)
     if not other:

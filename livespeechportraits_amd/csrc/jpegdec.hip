@@ -1,5 +1,5 @@
 // jpegdec.hip -- the JPEG decoder of include/lspjpegdec.h: three stages on the device (entropy decode, dequantise + IDCT, upsample +
-// colour + store) behind a host planner; stage 1 has a second kernel for complete progressive files (LSPJPEG_DEC_FLAG_PROGRESSIVE).  The arithmetic is libjpeg's integer arithmetic step by step (jdhuff.c, jidctint.c, jdsample.c,
+// colour + store) behind a host planner; stage 1 has a second kernel for complete progressive files (LSPJPEG_DEC_FLAG_PROGRESSIVE) and a third that decodes inside a restart interval in parallel (LSPJPEG_DEC_FLAG_PARALLEL).  The arithmetic is libjpeg's integer arithmetic step by step (jdhuff.c, jidctint.c, jdsample.c,
 // jdcolor.c): for a file Pillow can open the output equals Pillow's pixels.  The parser and the segment decoder live in jpegdec_core.h, which is
 // also built for the host alone and run under sanitizers (make check-jpegdec).
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@ namespace {
 using namespace lspdec;
 
 thread_local std::string g_err;
+thread_local ParStats g_par_stats;           // of this thread's last lspjpeg_dec_host_coefficients
 int fail(int code, const std::string &msg)
 {
     g_err = msg;
@@ -97,6 +98,150 @@ __global__ __launch_bounds__(kWave) void jpegdec_entropy(Params p)
         }
     }
     if (st != ST_OK && lane == 0) atomicCAS(p.status + sg.file, 0u, st);
+}
+
+// ---- stage 1 on the parallel route (LSPJPEG_DEC_FLAG_PARALLEL): one workgroup of kParLanes lanes per restart interval, decoding INSIDE the
+// interval in parallel (jpegdec_core.h: decode_subsequence and the fixed point it serves; jpegdec_plan.h host_parallel_segment is this kernel with
+// the lanes as loops).  The interval is walked in chunks of kParLanes subsequences.  Per chunk: the stream bytes are staged into LDS in 16-byte
+// loads (with 16 bytes in front for the stuffed-pair test and 32 behind for the code that runs past the last boundary); every lane decodes its
+// subsequence from its entry state without writing and the lanes hand their exit states on through LDS until no entry changes (a lane behind a
+// dead exit keeps its own guess); an exclusive scan over blocks started, DC sums and dead exits gives each lane its block index and DC
+// predictions and says whether its entry is true (no dead exit in front of it); each such lane decodes once more and writes coefficients.  The last exit state, the block count and the predictions carry over to the next chunk in LDS: no host loop, no
+// global scratch.  Nothing is capped: a stream that never resynchronises costs one round per subsequence, the serial decode.
+// Reads are bounded by the interval's end (BitReader) and the block's end (the staging); writes by the interval's block count nmcu * bpm, which
+// decode_subsequence checks before every block it enters.
+// Hazards.  (1) The interval's coefficient range is zeroed with 16-byte stores by all waves, and the write pass later stores 2-byte values to the
+// same addresses from OTHER waves: a device-scope fence (__threadfence) after the zeroing and the workgroup barrier behind it order the two
+// (each wave's zero stores are complete and visible device-wide before any wave passes the barrier).  Stage 2 reads the coefficients behind a
+// kernel boundary.  (2) LDS: every exchange (window, exit states, scan inputs, carry, failure word) has a barrier between its writers and
+// its readers, and one more before the words are written again.  (3) Two lanes never write the same coefficient: a block belongs to the lanes
+// its codes start in, each code to one lane.
+constexpr unsigned kParWindow = kParLanes * kSubseqBytes + 64;
+static_assert(kParWindow % 16 == 0 && kParLanes % kWave == 0 && kParLanes <= 1024, "the window is staged in 16-byte loads by whole waves");
+
+struct WindowSrc {
+    const unsigned char *win;
+    unsigned long long base;                // offset inside the block of win[0]
+    __device__ uint8_t at(uint64_t pos) const { return win[pos - base]; }
+};
+
+__global__ __launch_bounds__(kParLanes) void jpegdec_entropy_parallel(Params p)
+{
+    __shared__ uint4 s_tab[4 * sizeof(HuffTable) / 16];
+    __shared__ uint4 s_win[kParWindow / 16];
+    __shared__ ParState s_exit[kParLanes];
+    __shared__ unsigned s_blocks[kParLanes];
+    __shared__ int s_dc[3][kParLanes];
+    __shared__ unsigned s_dead[kParLanes];
+    __shared__ unsigned s_wave_blocks[kParLanes / kWave], s_wave_dead[kParLanes / kWave];
+    __shared__ int s_wave_dc[3][kParLanes / kWave];
+    __shared__ ParState s_carry;
+    __shared__ unsigned s_carry_blocks;
+    __shared__ int s_carry_pred[3];
+    __shared__ unsigned s_fail, s_done;
+    if (blockIdx.x >= p.nsegs) return;
+    const SegDesc sg = p.segs[blockIdx.x];
+    const ParGeom g = par_geom(p.files[sg.file]);                              // the geometry in registers: the stores below may alias nothing of it
+    const unsigned table0 = p.files[sg.file].table0;
+    const unsigned long long coef_off = p.files[sg.file].coef_off;
+    const unsigned lane = threadIdx.x;
+    const uint4 *tab = reinterpret_cast<const uint4 *>(p.tables + table0);
+    for (unsigned k = lane; k < 4 * sizeof(HuffTable) / 16; k += kParLanes) s_tab[k] = tab[k];
+    const unsigned total = sg.nmcu * g.bpm;
+    short *coef = p.coef + (coef_off + (unsigned long long)sg.mcu0 * g.bpm) * 64;
+    for (unsigned long long k = lane; k < (unsigned long long)total * 8; k += kParLanes) reinterpret_cast<uint4 *>(coef)[k] = make_uint4(0, 0, 0, 0);
+    if (lane == 0) {
+        s_carry = ParState{sg.begin * 8, 0, 0, 0};
+        s_carry_blocks = 0;
+        s_carry_pred[0] = s_carry_pred[1] = s_carry_pred[2] = 0;
+        s_fail = ~0u;
+        s_done = 0;
+    }
+    __threadfence();                                                           // hazard (1)
+    __syncthreads();
+    const HuffTable *tables = reinterpret_cast<const HuffTable *>(s_tab);
+    const unsigned nsub = subsequences_of(sg.begin, sg.end);
+    for (unsigned c0 = 0; c0 < nsub; c0 += kParLanes) {
+        const unsigned nl = nsub - c0 < kParLanes ? nsub - c0 : kParLanes;
+        const unsigned long long cb = sg.begin + (unsigned long long)c0 * kSubseqBytes;
+        const WindowSrc src{reinterpret_cast<const unsigned char *>(s_win), (cb - 16) & ~15ull};
+        for (unsigned k = lane; k < kParWindow / 16; k += kParLanes) {
+            const unsigned long long off = src.base + (unsigned long long)k * 16;
+            if (off + 16 <= p.bytes) s_win[k] = *reinterpret_cast<const uint4 *>(p.blob + off);
+        }
+        __syncthreads();                                                       // the window, and the carry of the chunk before
+        const bool active = lane < nl;
+        unsigned long long limit = cb + (unsigned long long)(lane + 1) * kSubseqBytes;
+        if (limit > sg.end) limit = sg.end;
+        const ParState guess = guess_state(src, sg.begin, sg.end, cb + (unsigned long long)lane * kSubseqBytes);
+        ParState entry = lane ? guess : s_carry;
+        ParResult res;
+        bool changed = active;
+        for (;;) {                                                             // the fixed point
+            if (changed) {
+                decode_subsequence<false>(src, sg.begin, sg.end, limit, entry, tables, g, 0, 0, nullptr, nullptr, false, &res);
+                s_exit[lane] = res.exit;
+            }
+            __syncthreads();
+            changed = false;
+            if (active && lane) {
+                const ParState before = s_exit[lane - 1], want = before.dead ? guess : before;     // behind a dead exit the lane's own guess stands again
+                if (!same_state(want, entry)) {
+                    entry = want;
+                    changed = true;
+                }
+            }
+            if (!__syncthreads_or(changed)) break;                             // also: every exit state is read before one is written again
+        }
+        // the exclusive scan, in two levels: per wave, then over the waves
+        s_blocks[lane] = active ? res.blocks : 0u;
+        s_dead[lane] = active && res.exit.dead ? 1u : 0u;
+        for (int c = 0; c < 3; ++c) s_dc[c][lane] = active ? res.dc[c] : 0;
+        __syncthreads();
+        if (lane < kParLanes / kWave) {
+            unsigned nb = 0, nd = 0;
+            int dc[3] = {0, 0, 0};
+            for (unsigned j = lane * kWave; j < (lane + 1) * kWave; ++j) {
+                nb += s_blocks[j];
+                nd += s_dead[j];
+                for (int c = 0; c < 3; ++c) dc[c] += s_dc[c][j];
+            }
+            s_wave_blocks[lane] = nb;
+            s_wave_dead[lane] = nd;
+            for (int c = 0; c < 3; ++c) s_wave_dc[c][lane] = dc[c];
+        }
+        __syncthreads();
+        unsigned blocks = s_carry_blocks, dead = 0;                            // dead exits in front of this lane: its entry is true when there is none
+        int pred[3] = {s_carry_pred[0], s_carry_pred[1], s_carry_pred[2]};
+        for (unsigned w = 0; w < lane / kWave; ++w) {
+            blocks += s_wave_blocks[w];
+            dead += s_wave_dead[w];
+            for (int c = 0; c < 3; ++c) pred[c] += s_wave_dc[c][w];
+        }
+        for (unsigned j = lane / kWave * kWave; j < lane; ++j) {
+            blocks += s_blocks[j];
+            dead += s_dead[j];
+            for (int c = 0; c < 3; ++c) pred[c] += s_dc[c][j];
+        }
+        // the write pass, from the true entries
+        if (active && !dead && !entry.dead && (entry.k == 0 || blocks > 0)) {
+            ParResult w;
+            decode_subsequence<true>(src, sg.begin, sg.end, limit, entry, tables, g, entry.k ? blocks - 1 : blocks, total, pred, coef, c0 + lane + 1 == nsub, &w);
+            if (w.status != ST_OK) atomicMin(&s_fail, (lane << 2) | w.status);  // the lowest lane is the earliest failure in stream order
+            if (w.done) s_done = 1;
+        }
+        __syncthreads();                                                       // the carry has been read by every lane
+        if (lane == nl - 1) {
+            s_carry = res.exit;
+            s_carry_blocks = blocks + res.blocks;
+            for (int c = 0; c < 3; ++c) s_carry_pred[c] = pred[c] + res.dc[c];
+        }
+        __syncthreads();
+        if (s_fail != ~0u || s_done) break;                                    // behind a failure or the last block nothing is a state of the file
+    }
+    // neither a failure nor the last block: unreachable (a true entry with a dead exit fails or finishes in the write pass, and the interval's
+    // last lane reports data that ends early); CORRUPT, as host_parallel_segment answers
+    if (lane == 0 && (s_fail != ~0u || !s_done)) atomicCAS(p.status + sg.file, 0u, s_fail != ~0u ? s_fail & 3u : (unsigned)ST_CORRUPT);
 }
 
 // ---- stage 1 of the progressive files: one wave per file, every scan of the file in file order over the same coefficients (a refinement reads
@@ -449,7 +594,7 @@ int lspjpeg_dec_probe(const unsigned char *bytes, size_t len, lspjpeg_dec_info *
 int lspjpeg_dec_probe_flags(const unsigned char *bytes, size_t len, unsigned flags, lspjpeg_dec_info *info)
 {
     if (!bytes || !info) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "null argument");
-    if (flags & ~LSPJPEG_DEC_FLAG_PROGRESSIVE) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "unknown flag");
+    if (flags & ~(LSPJPEG_DEC_FLAG_PROGRESSIVE | LSPJPEG_DEC_FLAG_PARALLEL)) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "unknown flag");
     Parsed f;
     ProgFile pf;
     uint32_t nseg;
@@ -472,7 +617,7 @@ int64_t lspjpeg_dec_plan(const unsigned char *const *files, const size_t *lens, 
 int64_t lspjpeg_dec_plan_flags(const unsigned char *const *files, const size_t *lens, const lspjpeg_dec_output *outs, int n, int max_side, unsigned flags,
                                void *blob, size_t cap)
 {
-    if (flags & ~LSPJPEG_DEC_FLAG_PROGRESSIVE) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "unknown flag");
+    if (flags & ~(LSPJPEG_DEC_FLAG_PROGRESSIVE | LSPJPEG_DEC_FLAG_PARALLEL)) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "unknown flag");
     if (!files || !lens || n < 1 || n > 65535) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "files, lens and 1..65535 files are required");
     if (max_side < 1 || max_side > LSPJPEG_MAX_SIDE) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "max_side must be in 1.." + std::to_string(LSPJPEG_MAX_SIDE));
     for (int i = 0; i < n; ++i)
@@ -601,7 +746,27 @@ int lspjpeg_dec_host_coefficients(const void *blob, int i, int16_t *out, size_t 
     const BlobHeader *h = header_of(blob);
     if (!h || !out || i < 0 || (uint32_t)i >= h->nfiles) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "no such file in the block");
     if (cap_values < (size_t)files_of(blob)[i].nblk * 64) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "out is too small for the file's blocks");
-    return (int)host_coefficients(blob, i, out);
+    g_par_stats = ParStats{};
+    return (int)host_coefficients(blob, i, out, &g_par_stats);
+}
+
+int lspjpeg_dec_plan_parallel(const void *blob, int k, uint32_t *subseq_bytes, uint32_t *subsequences)
+{
+    const BlobHeader *h = header_of(blob);
+    if (!h || k < 0 || (uint32_t)k >= h->nsegs || !subseq_bytes || !subsequences) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "no such segment in the block");
+    if (!h->parallel) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "the block was planned without LSPJPEG_DEC_FLAG_PARALLEL");
+    const SegDesc &s = segs_of(blob)[k];
+    *subseq_bytes = kSubseqBytes;
+    *subsequences = subsequences_of(s.begin, s.end);
+    return LSPJPEG_DEC_OK;
+}
+
+int lspjpeg_dec_host_parallel_stats(uint32_t *rounds, uint32_t *midblock_entries)
+{
+    if (!rounds || !midblock_entries) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "null argument");
+    *rounds = g_par_stats.rounds;
+    *midblock_entries = g_par_stats.midblock;
+    return LSPJPEG_DEC_OK;
 }
 
 int lspjpeg_dec_decode(const void *blob_host, void *blob_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream)
@@ -629,7 +794,10 @@ int lspjpeg_dec_decode(const void *blob_host, void *blob_dev, void *workspace_de
     p.ptables = reinterpret_cast<const HuffTable *>(b + h->ptables_off);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const auto grid = [](unsigned items, unsigned per) { return items ? (items + per - 1) / per : 1u; };     // a batch of refused files still launches
-    hipLaunchKernelGGL(jpegdec_entropy, dim3(grid(h->nsegs, 1)), dim3(kWave), 0, st, p);
+    if (h->parallel)
+        hipLaunchKernelGGL(jpegdec_entropy_parallel, dim3(grid(h->nsegs, 1)), dim3(kParLanes), 0, st, p);
+    else
+        hipLaunchKernelGGL(jpegdec_entropy, dim3(grid(h->nsegs, 1)), dim3(kWave), 0, st, p);
     if (h->nprog) hipLaunchKernelGGL(jpegdec_progressive, dim3(h->nfiles), dim3(kWave), 0, st, p);     // the files of the two kinds are disjoint
     hipLaunchKernelGGL(jpegdec_idct, dim3(grid(h->max_blocks, kIdctThreads), h->nfiles), dim3(kIdctThreads), 0, st, p);
     hipLaunchKernelGGL(jpegdec_store, dim3(grid(h->max_pixels, kStoreThreads), h->nfiles), dim3(kStoreThreads), 0, st, p);

@@ -9,6 +9,9 @@
 // Under kFlagProgressive also SOF2 (jdphuff.c): walk_progressive() is the parser and scan walker of such a file (every scan, the tables and the
 // restart interval in force at each, libjpeg's coef_bits bookkeeping), prog_units() the four procedures of ITU T.81 Annex G.  A progressive file
 // is decoded only when it is complete (every coefficient of every component refined down to bit 0): its coefficients are then a baseline file's.
+//
+// Under kFlagParallel a restart interval of a baseline file is decoded by many lanes: decode_subsequence() is the decoder of one lane, shared by the
+// kernel and its host twin (jpegdec_plan.h host_parallel_segment; jpegdec_par_check.cpp runs it against the serial decoder under sanitizers).
 #ifndef LSPJPEGDEC_CORE_H
 #define LSPJPEGDEC_CORE_H
 
@@ -354,15 +357,18 @@ inline bool build_table(const uint8_t bits[17], const uint8_t vals[256], HuffTab
 // The entropy decode of one restart interval.  Src is the byte source: `uint8_t at(uint64_t pos) const` for pos in [begin, end) -- plain memory on
 // the host, a window in LDS on the device.  The reader never asks for a byte outside [begin, end).
 // ---------------------------------------------------------------------------------------------------------------------------------------------
-template <class Src>
+// Track (the parallel route, kFlagParallel): the reader also remembers which of the bytes it holds were followed by a stuffed 0x00, so that
+// at_bit() can say where in the STUFFED stream the next unread bit stands, and start() can take up a stream at such a place.
+template <class Src, bool Track = false>
 struct BitReader {
     const Src &src;
     uint64_t pos, end;
     uint64_t buf;              // the low `left` bits are the unread ones, MSB first
     int left;
     uint32_t status;
+    uint32_t stuffed;          // Track: bit j set = the (j + 1)-th last byte fetched was 0xFF 0x00
 
-    LSPDEC_HD BitReader(const Src &s, uint64_t begin, uint64_t end_) : src(s), pos(begin), end(end_), buf(0), left(0), status(ST_OK) {}
+    LSPDEC_HD BitReader(const Src &s, uint64_t begin, uint64_t end_) : src(s), pos(begin), end(end_), buf(0), left(0), status(ST_OK), stuffed(0) {}
 
     LSPDEC_HD void fill()
     {
@@ -378,7 +384,33 @@ struct BitReader {
             }
             buf = (buf << 8) | b;
             left += 8;
+            if (Track) stuffed = (stuffed << 1) | (b == 0xff ? 1u : 0u);
         }
+    }
+    // Track: the byte of the stuffed stream that holds the next unread bit (pos when nothing is buffered), and that bit's position.  Never a
+    // stuffed 0x00: fill() steps over it with its 0xFF.
+    LSPDEC_HD uint64_t at_byte() const
+    {
+        const uint32_t nb = (uint32_t)(left + 7) >> 3;
+        return pos - nb - (uint32_t)__builtin_popcount(stuffed & ((1u << nb) - 1u));
+    }
+    LSPDEC_HD uint64_t at_bit() const { return at_byte() * 8 + (uint32_t)((8 - (left & 7)) & 7); }
+    // Track: take the stream up at bit position `bit` (as at_bit() gives it, or a byte boundary: a boundary that falls on the 0x00 of a
+    // 0xFF 0x00 pair moves to the byte behind it -- the walker leaves 0xFF in a segment only in such pairs, so the pair is recognised by its
+    // two bytes).  `begin` is the segment's first byte: nothing in front of it is read.
+    LSPDEC_HD void start(uint64_t begin, uint64_t bit)
+    {
+        pos = bit >> 3;
+        const int off = (int)(bit & 7);
+        if (off == 0 && pos > begin && pos < end && src.at(pos) == 0 && src.at(pos - 1) == 0xff) ++pos;
+        buf = 0;
+        left = 0;
+        stuffed = 0;
+        fill();
+        if (off > left)
+            status = ST_CORRUPT;                                               // no true state stands behind the data's end
+        else
+            left -= off;
     }
     // the next 16 bits, zero-padded past the end of the data
     LSPDEC_HD uint32_t peek16() const { return left >= 16 ? (uint32_t)(buf >> (left - 16)) & 0xffffu : (uint32_t)(buf << (16 - left)) & 0xffffu; }
@@ -486,6 +518,193 @@ LSPDEC_HD inline void block_components(uint32_t ncomp, uint32_t hs, uint32_t vs,
     }
     for (int k = n; k < kMaxBlocksPerMcu; ++k) comp_of[k] = 0;
     *bpm = n;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// Parallel decode inside a restart interval (kFlagParallel): self-synchronising Huffman decoding (Weissenberger and Schmidt 2018, 2021).
+// The interval's stuffed bytes are cut into subsequences of kSubseqBytes; lane i decodes the codes that START in subsequence i (the last one may
+// run past its end).  Where a lane has to start is not known in advance, so every lane but the first guesses "a DC code of block 0 starts at my
+// boundary", and the guesses are repaired by a fixed point: each lane hands its exit state to the next, which decodes again if that is not the
+// entry it used.  Lane 0's entry is true, so by induction every entry is true once nothing changes -- after one round per lane at the worst,
+// which is the serial decode.  A decode that meets an error ends in a DEAD state: an error met from a guess is no error of the file.  A dead
+// entry gives a dead exit; a lane BEHIND a dead exit does not take it over but falls back on its own guess, so that the parse takes up again behind
+// the place where a wrong guess died (handing the dead state on instead lets it run ahead of the true state at the same one lane per round and
+// wipe out every guess that had already met the true parse: the 512^2 q95 files then take as many rounds as they have subsequences).  The
+// induction holds for the lanes with no dead exit in front of them, and only those take part in the write pass; the first dead exit of a TRUE
+// entry is the file's own failure or lies behind its last block, and either ends the interval's walk.
+// A JPEG stream resynchronises in bits and zigzag position after a few codes, in the block index inside the MCU after a few MCUs: 1 to 1.5 KB on
+// the 512^2 test files.  The depth of a chunk is about (resynchronisation distance + one subsequence) whatever the subsequence size, so the gain
+// is the chunk's bytes over that distance, and a chunk is as many lanes as a workgroup has.  The size is small so that files of a few dozen
+// bytes (most test fixtures) take the many-lane path too.  A code (<= 27 bits) may be longer than a subsequence: a lane whose entry lies behind
+// its own end decodes nothing and hands the state on.
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kFlagParallel = 2u;              // include/lspjpegdec.h LSPJPEG_DEC_FLAG_PARALLEL
+constexpr uint32_t kSubseqBytes = 8;                // of the stuffed stream, per lane
+constexpr uint32_t kParLanes = 1024;                // lanes of one workgroup: an interval is walked in chunks of kParLanes subsequences
+
+// the parser's state between two codes
+struct ParState {
+    uint64_t bit;              // position of the next code in the stuffed stream: 8 * (offset inside the block) + bit; never inside a stuffed 0x00
+    uint16_t b, k;             // block index inside the MCU, zigzag position: k = 0 means "a DC code is next"
+    uint32_t dead;             // a decode up to here met an error; a dead entry gives a dead exit
+};
+static_assert(sizeof(ParState) == 16, "ParState is moved as two 64-bit words");
+
+LSPDEC_HD inline bool same_state(const ParState &a, const ParState &b) { return a.bit == b.bit && a.b == b.b && a.k == b.k && a.dead == b.dead; }
+
+// the guess of a lane whose subsequence starts at byte `at`
+template <class Src>
+LSPDEC_HD inline ParState guess_state(const Src &src, uint64_t begin, uint64_t end, uint64_t at)
+{
+    if (at > begin && at < end && src.at(at) == 0 && src.at(at - 1) == 0xff) ++at;     // the 0x00 of a stuffed pair holds no bit
+    return ParState{at * 8, 0, 0, 0};
+}
+
+// how an interval is cut
+LSPDEC_HD inline uint32_t subsequences_of(uint64_t begin, uint64_t end) { return end > begin ? (uint32_t)((end - begin + kSubseqBytes - 1) / kSubseqBytes) : 1u; }
+
+// what the file's geometry gives the subsequence decoder, in registers (no arrays indexed by the state)
+struct ParGeom {
+    uint32_t bpm, nluma;       // blocks per MCU; luma blocks among them (1 for a grey file)
+    uint32_t dc_sel, ac_sel;   // FileDesc's selectors, one byte per component
+};
+LSPDEC_HD inline ParGeom par_geom(const FileDesc &f)
+{
+    ParGeom g;
+    g.bpm = f.ncomp == 1 ? 1 : f.hs * f.vs + 2;
+    g.nluma = f.ncomp == 1 ? 1 : f.hs * f.vs;
+    g.dc_sel = f.dc_sel[0] | ((uint32_t)f.dc_sel[1] << 8) | ((uint32_t)f.dc_sel[2] << 16);
+    g.ac_sel = f.ac_sel[0] | ((uint32_t)f.ac_sel[1] << 8) | ((uint32_t)f.ac_sel[2] << 16);
+    return g;
+}
+
+struct ParResult {
+    ParState exit;             // where the next lane starts (sync mode)
+    uint32_t blocks;           // DC codes decoded: blocks started
+    int dc[3];                 // sum of the DC differences per component
+    uint32_t status;           // write mode: the first failure from this (true) entry, in stream order
+    uint32_t done;             // write mode: this lane finished the interval's last block
+};
+
+// One subsequence from entry state `in`: codes are decoded while the next one starts in front of byte `limit`; reads stay inside [begin, end).
+// Sync mode (Write false) decodes without writing; an error there belongs to the guess, not to the file: the exit state is dead.
+// Write mode starts from a true entry: `block` is the absolute index (inside the interval) of the block `in` stands in -- the one started last
+// when in.k != 0 -- and pred the DC predictions there.  Coefficients go to coef[block][64] in natural order, the running prediction into
+// slot 0 under decode_mcu's int16 check, up to `total` blocks; the lane that finishes block total - 1 applies the drained() rule, and the
+// interval's last lane (`last`) reports data that ends early.  The order of the checks is decode_mcu's.
+template <bool Write, class Src>
+LSPDEC_HD inline void decode_subsequence(const Src &src, uint64_t begin, uint64_t end, uint64_t limit, const ParState &in, const HuffTable *tables, const ParGeom &g,
+                                         uint32_t block, uint32_t total, const int *pred_in, int16_t *coef, bool last, ParResult *o)
+{
+    o->exit = in;
+    o->blocks = 0;
+    o->dc[0] = o->dc[1] = o->dc[2] = 0;
+    o->status = ST_OK;
+    o->done = 0;
+    if (in.dead) return;
+    if (Write && block >= total) return;                                       // behind the interval's last block: nothing of it is decoded
+    BitReader<Src, true> br(src, begin, end);
+    br.start(begin, in.bit);
+    uint32_t b = in.b, k = in.k, st = br.status;
+    int p0 = 0, p1 = 0, p2 = 0;
+    if (Write) {
+        p0 = pred_in[0];
+        p1 = pred_in[1];
+        p2 = pred_in[2];
+    }
+    int16_t *blk = Write ? coef + (size_t)block * 64 : nullptr;
+    while (st == ST_OK && br.at_byte() < limit) {
+        const uint32_t c = b < g.nluma ? 0u : b - g.nluma + 1u;
+        if (k == 0) {
+            const int s = br.symbol(tables[2 * ((g.dc_sel >> (8 * c)) & 1u)]);
+            if (s < 0) {
+                st = br.status;
+                break;
+            }
+            if (s > 11) {
+                st = ST_CORRUPT;
+                break;
+            }
+            const int diff = s ? br.receive_extend(s) : 0;
+            if (br.status) {
+                st = br.status;
+                break;
+            }
+            ++o->blocks;
+            o->dc[0] += c == 0 ? diff : 0;
+            o->dc[1] += c == 1 ? diff : 0;
+            o->dc[2] += c == 2 ? diff : 0;
+            if (Write) {
+                p0 += c == 0 ? diff : 0;
+                p1 += c == 1 ? diff : 0;
+                p2 += c == 2 ? diff : 0;
+                const int pred = c == 0 ? p0 : c == 1 ? p1 : p2;
+                if (pred < -32768 || pred > 32767) {
+                    st = ST_RANGE;
+                    break;
+                }
+                blk[0] = (int16_t)pred;
+            }
+            k = 1;
+        } else {
+            const int rs = br.symbol(tables[2 * ((g.ac_sel >> (8 * c)) & 1u) + 1]);
+            if (rs < 0) {
+                st = br.status;
+                break;
+            }
+            const uint32_t r = (uint32_t)rs >> 4, s = (uint32_t)rs & 15u;
+            if (s == 0) {
+                if (r != 15) {
+                    k = 64;                                                    // EOB
+                } else {
+                    if (k + 15 > 63) {                                         // ZRL: sixteen zeros
+                        st = ST_CORRUPT;
+                        break;
+                    }
+                    k += 16;
+                }
+            } else {
+                if (s > 10) {
+                    st = ST_CORRUPT;
+                    break;
+                }
+                k += r;
+                if (k > 63) {                                                  // a coefficient index past 63
+                    st = ST_CORRUPT;
+                    break;
+                }
+                const int v = br.receive_extend((int)s);
+                if (br.status) {
+                    st = br.status;
+                    break;
+                }
+                if (Write) blk[zigzag_to_natural((int)k)] = (int16_t)v;
+                ++k;
+            }
+        }
+        if (k == 64) {                                                         // the block is complete
+            k = 0;
+            b = b + 1 == g.bpm ? 0 : b + 1;
+            if (Write) {
+                ++block;
+                blk += 64;
+                if (block == total) {
+                    o->done = 1;
+                    if (!br.drained()) st = ST_CORRUPT;                        // whole bytes left over
+                    break;
+                }
+            }
+        }
+    }
+    if (Write) {
+        if (st == ST_OK && last && !o->done) st = ST_CORRUPT;                  // the data ends before the interval's last block does
+        o->status = st;
+        return;
+    }
+    o->exit.bit = br.at_bit();
+    o->exit.b = (uint16_t)b;
+    o->exit.k = (uint16_t)k;
+    o->exit.dead = st != ST_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------

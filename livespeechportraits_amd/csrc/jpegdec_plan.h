@@ -1,6 +1,6 @@
 // jpegdec_plan.h -- the host half of the JPEG decoder behind include/lspjpegdec.h: the planner that lays a batch of files out in one descriptor
 // block, and stage 1 run on the host over that block.  Plain C++ (no HIP, no allocation): jpegdec.hip wraps it in the C ABI, jpegdec_check.cpp
-// builds it with sanitizers and runs it over fixtures, truncations and corruptions.
+// builds it with sanitizers and runs it over fixtures, truncations and corruptions; jpegdec_par_check.cpp does the same for the parallel route.
 #ifndef LSPJPEGDEC_PLAN_H
 #define LSPJPEGDEC_PLAN_H
 
@@ -12,7 +12,9 @@ constexpr uint32_t kMagic = 0x4a44534cu;            // "LSDJ"
 
 struct BlobHeader {
     uint32_t magic, nfiles, nsegs, has_outputs;
-    uint32_t max_blocks, max_pixels, pad0, pad1;
+    uint32_t max_blocks, max_pixels;
+    uint32_t parallel;                              // kFlagParallel: stage 1 of the baseline files decodes inside a restart interval in parallel; 0 without the flag
+    uint32_t pad1;
     uint64_t total_blocks, bytes, workspace_bytes;
     uint64_t files_off, segs_off, tables_off, status_off, data_off;
     uint64_t planes_ws_off;                         // the plane area inside the workspace (the coefficients come first)
@@ -103,6 +105,7 @@ inline int64_t plan(const uint8_t *const *files, const size_t *lens, const Outpu
     BlobHeader h{};
     h.magic = kMagic;
     h.nfiles = (uint32_t)n;
+    h.parallel = flags & kFlagParallel ? 1u : 0u;
     h.files_off = sizeof(BlobHeader);
     h.segs_off = up(h.files_off + (uint64_t)n * sizeof(FileDesc), 16);
     h.tables_off = up(h.segs_off + nsegs * sizeof(SegDesc), 16);
@@ -272,8 +275,77 @@ inline uint32_t host_progressive(const void *blob, const FileDesc &d, int16_t *o
     return ST_OK;
 }
 
+// what the parallel route did, for checks: the most rounds the fixed point of any chunk took, and how many true entry states stood inside a block
+struct ParStats {
+    uint32_t rounds, midblock;
+};
+
+// One restart interval on the parallel route (kFlagParallel), as jpegdec_entropy_parallel runs it with the lanes as loops: per chunk of kParLanes
+// subsequences the fixed point over the entry states, the exclusive scan over blocks started and DC sums, and the write pass from the true
+// entries (those with no dead exit in front of them).  `out` is the file's coefficient array, zeroed by the caller.  Returns the status of the earliest failure in stream order.
+inline uint32_t host_parallel_segment(const void *blob, const FileDesc &d, const SegDesc &sg, int16_t *out, ParStats *stats)
+{
+    const MemSrc src{static_cast<const uint8_t *>(blob)};
+    const ParGeom g = par_geom(d);
+    const HuffTable *tables = tables_of(blob) + d.table0;
+    const uint32_t total = sg.nmcu * g.bpm, nsub = subsequences_of(sg.begin, sg.end);
+    int16_t *coef = out + (uint64_t)sg.mcu0 * g.bpm * 64;
+    ParState entry[kParLanes], guess[kParLanes], carry{sg.begin * 8, 0, 0, 0};
+    ParResult res[kParLanes];
+    bool changed[kParLanes];
+    uint32_t blocks = 0;
+    int pred[3] = {0, 0, 0};
+    for (uint32_t c0 = 0; c0 < nsub; c0 += kParLanes) {
+        const uint32_t nl = nsub - c0 < kParLanes ? nsub - c0 : kParLanes;
+        const uint64_t cb = sg.begin + (uint64_t)c0 * kSubseqBytes;
+        const auto limit = [&](uint32_t lane) {
+            const uint64_t e = cb + (uint64_t)(lane + 1) * kSubseqBytes;
+            return e < sg.end ? e : sg.end;
+        };
+        for (uint32_t lane = 0; lane < nl; ++lane) {
+            guess[lane] = guess_state(src, sg.begin, sg.end, cb + (uint64_t)lane * kSubseqBytes);
+            entry[lane] = lane ? guess[lane] : carry;
+            changed[lane] = true;
+        }
+        for (uint32_t rounds = 1;; ++rounds) {
+            for (uint32_t lane = 0; lane < nl; ++lane)
+                if (changed[lane]) decode_subsequence<false>(src, sg.begin, sg.end, limit(lane), entry[lane], tables, g, 0, 0, nullptr, nullptr, false, &res[lane]);
+            bool any = false;
+            changed[0] = false;
+            for (uint32_t lane = 1; lane < nl; ++lane) {
+                const ParState want = res[lane - 1].exit.dead ? guess[lane] : res[lane - 1].exit;     // behind a dead exit the lane's own guess stands again
+                changed[lane] = !same_state(want, entry[lane]);
+                if (changed[lane]) {
+                    entry[lane] = want;
+                    any = true;
+                }
+            }
+            if (!any) {
+                if (stats && rounds > stats->rounds) stats->rounds = rounds;
+                break;
+            }
+        }
+        bool valid = true;
+        for (uint32_t lane = 0; lane < nl; ++lane) {
+            const ParState &e = entry[lane];
+            valid = valid && !e.dead && !(lane && res[lane - 1].exit.dead);     // true entries reach as far as the exits before them are alive
+            if (valid && (e.k == 0 || blocks > 0)) {
+                if (stats && e.k) ++stats->midblock;
+                ParResult w;
+                decode_subsequence<true>(src, sg.begin, sg.end, limit(lane), e, tables, g, e.k ? blocks - 1 : blocks, total, pred, coef, c0 + lane + 1 == nsub, &w);
+                if (w.status != ST_OK) return w.status;                        // the lanes are visited in stream order: the first failure
+                if (w.done) return ST_OK;                                      // what stands behind the interval's last block is no state of the file
+            }
+            blocks += res[lane].blocks;
+            for (int c = 0; c < 3; ++c) pred[c] += res[lane].dc[c];
+        }
+        carry = res[nl - 1].exit;
+    }
+    return ST_CORRUPT;                                                         // unreachable: a true entry with a dead exit fails or finishes in the write pass, and the last lane reports data that ends early
+}
+
 // stage 1 of file i on the host: the status the kernel would leave, and (on ST_OK only) the coefficients
-inline uint32_t host_coefficients(const void *blob, int i, int16_t *out)
+inline uint32_t host_coefficients(const void *blob, int i, int16_t *out, ParStats *stats = nullptr)
 {
     const FileDesc &d = files_of(blob)[i];
     if (d.status != ST_OK) return d.status;
@@ -285,6 +357,11 @@ inline uint32_t host_coefficients(const void *blob, int i, int16_t *out)
     if (d.progressive) return host_progressive(blob, d, out);
     for (uint32_t s = 0; s < d.nseg; ++s) {
         const SegDesc &sg = segs_of(blob)[d.seg0 + s];
+        if (header_of(blob)->parallel) {
+            const uint32_t st = host_parallel_segment(blob, d, sg, out, stats);
+            if (st != ST_OK) return st;
+            continue;
+        }
         BitReader<MemSrc> br(src, sg.begin, sg.end);
         int pred[3] = {0, 0, 0};
         for (uint32_t m = 0; m < sg.nmcu; ++m) {

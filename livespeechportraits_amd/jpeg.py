@@ -16,6 +16,8 @@ The way back is ``JpegDecoder`` (include/lspjpegdec.h): baseline files -- the ca
 host does the marker parsing and the batch layout (``DecodePlan``, no device needed); the compressed bytes cross PCIe once, in one
 block with the tables.  ``probe`` reports a file's geometry and whether it can be decoded.  With ``progressive=True`` (``probe``,
 ``DecodePlan``, ``JpegDecoder``) complete progressive files are taken as well, scan by scan, to the same pixels; off by default.
+With ``parallel=True`` (``DecodePlan``, ``JpegDecoder``) the entropy decode runs in parallel inside a restart interval, which for a file
+without restart markers means inside the file; same pixels and statuses; off by default.
 """
 from __future__ import annotations
 
@@ -259,6 +261,7 @@ STATUS_NAMES = {0: "OK", UNSUPPORTED: "UNSUPPORTED", CORRUPT: "CORRUPT", RANGE: 
 MAX_SIDE = 8192                                                # LSPJPEG_MAX_SIDE
 FORM_RGB8, FORM_GRAY8, FORM_PLANAR_F32 = 0, 1, 2
 FLAG_PROGRESSIVE = 1                                           # LSPJPEG_DEC_FLAG_PROGRESSIVE
+FLAG_PARALLEL = 2                                              # LSPJPEG_DEC_FLAG_PARALLEL
 
 
 class JpegError(ValueError):
@@ -329,11 +332,13 @@ class DecodePlan:
     """The descriptor block of a batch (``lspjpeg_dec_plan``): per-file tables and output descriptions, the entropy-coded bytes, one
     entry per restart interval.  Host only.  ``outputs`` is a list of ``(ptr, table_ptr, plane_stride, form)`` per file (device
     pointers), or None to plan for the host alone.  ``buffer(nbytes)`` supplies the memory (a pinned tensor's numpy view, say).
-    ``progressive``: complete progressive files are planned too, scan by scan (``scans(i)``); without it they are UNSUPPORTED."""
+    ``progressive``: complete progressive files are planned too, scan by scan (``scans(i)``); without it they are UNSUPPORTED.
+    ``parallel``: stage 1 of the baseline files decodes inside a restart interval in parallel (``parallel_segment(k)`` says how interval k is
+    cut); same statuses, same coefficients, and ``host_coefficients`` then runs that route's code with the lanes as loops."""
 
-    def __init__(self, files: Sequence[bytes], max_side: int = MAX_SIDE, outputs=None, buffer=None, progressive: bool = False):
+    def __init__(self, files: Sequence[bytes], max_side: int = MAX_SIDE, outputs=None, buffer=None, progressive: bool = False, parallel: bool = False):
         self.lib = N.load()
-        flags = FLAG_PROGRESSIVE if progressive else 0
+        flags = (FLAG_PROGRESSIVE if progressive else 0) | (FLAG_PARALLEL if parallel else 0)
         self.files = [bytes(f) for f in files]
         n = len(self.files)
         if n < 1:
@@ -377,6 +382,19 @@ class DecodePlan:
         N.check_jpeg_dec(self.lib.lspjpeg_dec_plan_segment(self.ptr, int(k), ctypes.byref(f), ctypes.byref(m0), ctypes.byref(nm), ctypes.byref(b), ctypes.byref(e)))
         return f.value, m0.value, nm.value, b.value, e.value
 
+    def parallel_segment(self, k: int):
+        """(bytes of one subsequence, subsequences) of restart interval k of a plan made with ``parallel=True``; raises on any other plan"""
+        size, count = ctypes.c_uint32(), ctypes.c_uint32()
+        N.check_jpeg_dec(self.lib.lspjpeg_dec_plan_parallel(self.ptr, int(k), ctypes.byref(size), ctypes.byref(count)))
+        return size.value, count.value
+
+    def parallel_stats(self):
+        """(most rounds the fixed point took in any chunk, true entry states inside a block) of the last ``host_coefficients`` call on this
+        thread; (0, 0) unless that plan was made with ``parallel=True``"""
+        rounds, mid = ctypes.c_uint32(), ctypes.c_uint32()
+        N.check_jpeg_dec(self.lib.lspjpeg_dec_host_parallel_stats(ctypes.byref(rounds), ctypes.byref(mid)))
+        return rounds.value, mid.value
+
     def scans(self, i: int) -> List[JpegScan]:
         """the scans of file i in file order; empty for a file that was not planned as a progressive one"""
         out = []
@@ -403,9 +421,12 @@ class JpegDecoder:
     """Baseline JPEG files -> pixels on the device, equal to Pillow's (include/lspjpegdec.h states the arithmetic and what is refused).
     One call takes files of different sizes and kinds; batches above ``max_batch`` are split.  ``max_side`` bounds width and height
     (larger files are UNSUPPORTED).  The device buffers grow to the largest batch seen and are kept.  ``progressive=True`` also takes complete
-    progressive files (SOF2), mixed freely with baseline ones: one more launch per call that holds any, one wave per such file."""
+    progressive files (SOF2), mixed freely with baseline ones: one more launch per call that holds any, one wave per such file.
+    ``parallel=True`` decodes inside every restart interval of the baseline files in parallel (one workgroup per interval instead of one lane of
+    one wave: the route for files without restart markers, Pillow's default and the encoder's own); same pixels, same statuses, same number of
+    launches; off by default."""
 
-    def __init__(self, device="cuda:0", max_side: int = 1024, max_batch: int = 64, progressive: bool = False):
+    def __init__(self, device="cuda:0", max_side: int = 1024, max_batch: int = 64, progressive: bool = False, parallel: bool = False):
         self.lib = N.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -413,6 +434,7 @@ class JpegDecoder:
         if not 1 <= int(max_side) <= MAX_SIDE or int(max_batch) < 1:
             raise ValueError("max_side must be in 1..%d and max_batch >= 1" % MAX_SIDE)
         self.max_side, self.max_batch, self.progressive = int(max_side), int(max_batch), bool(progressive)
+        self.parallel = bool(parallel)
         self._host = torch.empty(0, dtype=torch.uint8)
         self._dev = torch.empty(0, dtype=torch.uint8, device=self.device)
         self._ws = torch.empty(0, dtype=torch.uint8, device=self.device)
@@ -425,7 +447,7 @@ class JpegDecoder:
 
     def _run(self, files: Sequence[bytes], outputs) -> List[int]:
         """plan, upload, the three stages, and the status words back: the one synchronisation of a call"""
-        plan = DecodePlan(files, self.max_side, outputs, self._buffer, self.progressive)
+        plan = DecodePlan(files, self.max_side, outputs, self._buffer, self.progressive, self.parallel)
         if all(plan.statuses()):
             return plan.statuses()                             # nothing to decode: the parser refused every file
         n, ws = int(plan.bytes), int(plan.summary.workspace_bytes)

@@ -361,14 +361,15 @@ class AviReader:
         raw = b"".join(bytes(self._data[at:at + n]) for at, n in self._audio)
         return np.frombuffer(raw, dtype="<f4" if self.audio_format == "f32" else "<i2")
 
-    def frames(self, start: int = 0, stop: Optional[int] = None, decoder=None, batch: int = 64):
+    def frames(self, start: int = 0, stop: Optional[int] = None, decoder=None, batch: int = 64, parallel: bool = False):
         """Yields frames start .. stop - 1 as uint8 device tensors ([H, W, 3], or [H, W] for a grayscale file), decoded ``batch`` chunks per
         call of ``decoder`` (a jpeg.JpegDecoder; by default one on cuda:0 sized for this file).  A chunk the decoder refuses raises
-        jpeg.JpegError."""
+        jpeg.JpegError.  ``parallel``: the decoder this call makes decodes inside each frame in parallel (jpeg.JpegDecoder's ``parallel``; a
+        ``decoder`` passed in decides for itself)."""
         start, stop, _ = slice(start, stop).indices(self.nframes)
         if decoder is None:
             from .jpeg import JpegDecoder
-            decoder = JpegDecoder("cuda:0", max_side=max(self.width, self.height, 1), max_batch=batch)
+            decoder = JpegDecoder("cuda:0", max_side=max(self.width, self.height, 1), max_batch=batch, parallel=parallel)
         for k in range(start, stop, batch):
             for frame in decoder.decode([self.jpeg(i) for i in range(k, min(k + batch, stop))]):
                 yield frame
