@@ -1,4 +1,4 @@
-"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h, include/lspjpegdec.h, include/lsplmk.h, include/lspavi.h, include/lsprs.h, include/lspresize.h).
+"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h, include/lspjpegdec.h, include/lsppng.h, include/lsplmk.h, include/lspavi.h, include/lsprs.h, include/lspresize.h).
 
 There is deliberately no fallback: if the shared library is missing or does not
 load, importing the hot path raises -- a GPU box must never silently run
@@ -375,6 +375,30 @@ JPEGDEC_SIGNATURES = {
 }
 
 
+class PngDecInfo(ctypes.Structure):
+    """lsppng_dec_info"""
+    _fields_ = [("status", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("color_type", ctypes.c_int32),
+                ("depth", ctypes.c_int32), ("components", ctypes.c_int32), ("idat_bytes", ctypes.c_uint64), ("raw_bytes", ctypes.c_uint64)]
+
+
+class PngDecSummary(ctypes.Structure):
+    """lsppng_dec_summary"""
+    _fields_ = [("files", ctypes.c_uint32), ("max_pixels", ctypes.c_uint32), ("bytes", ctypes.c_uint64), ("workspace_bytes", ctypes.c_uint64),
+                ("status_offset", ctypes.c_uint64)]
+
+
+# every symbol include/lsppng.h declares (lsppng_dec_output has the layout of lspjpeg_dec_output: JpegDecOutput)
+PNGDEC_SIGNATURES = {
+    "lsppng_dec_last_error": (c_char_p, []),
+    "lsppng_dec_probe": (c_int, [c_void_p, c_size_t, POINTER(PngDecInfo)]),
+    "lsppng_dec_plan": (c_int64, [POINTER(c_void_p), POINTER(c_size_t), POINTER(JpegDecOutput), c_int, c_int, c_void_p, c_size_t]),
+    "lsppng_dec_summary_of": (c_int, [c_void_p, POINTER(PngDecSummary)]),
+    "lsppng_dec_plan_file": (c_int, [c_void_p, c_int, POINTER(PngDecInfo)]),
+    "lsppng_dec_host_scanlines": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "lsppng_dec_host_pixels": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "lsppng_dec_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 
 class LmkConfig(Structure):
     """lsplmk_config (include/lsplmk.h)"""
@@ -517,7 +541,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise NativeLibraryError("failed to load %s: %s" % (LIB_PATH, e)) from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JPEGDEC_SIGNATURES.items()) + list(LMK_SIGNATURES.items()) + list(AVI_SIGNATURES.items()) + list(RS_SIGNATURES.items()) + list(RSZ_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JPEGDEC_SIGNATURES.items()) + list(PNGDEC_SIGNATURES.items()) + list(LMK_SIGNATURES.items()) + list(AVI_SIGNATURES.items()) + list(RS_SIGNATURES.items()) + list(RSZ_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -635,6 +659,18 @@ def check_jpeg_dec(rc: int) -> int:
     if rc < 0:
         msg = load().lspjpeg_dec_last_error()
         raise LspjpegError(rc, msg.decode() if msg else "")
+    return rc
+
+
+class LsppngError(RuntimeError):
+    """negative return code of include/lsppng.h"""
+
+
+def check_png_dec(rc: int) -> int:
+    """negative codes of include/lsppng.h raise; anything else (0, a size, a status word) is handed back"""
+    if rc < 0:
+        msg = load().lsppng_dec_last_error()
+        raise LsppngError("lsppng_dec error %d: %s" % (rc, msg.decode() if msg else "?"))
     return rc
 
 
