@@ -387,7 +387,7 @@ class PngDecSummary(ctypes.Structure):
                 ("status_offset", ctypes.c_uint64)]
 
 
-# every symbol include/lsppng.h declares (lsppng_dec_output has the layout of lspjpeg_dec_output: JpegDecOutput)
+# every symbol include/lsppng.h declares (lsppng_dec_output has the layout of lspjpeg_dec_output, which csrc/pngdec.hip asserts: JpegDecOutput)
 PNGDEC_SIGNATURES = {
     "lsppng_dec_last_error": (c_char_p, []),
     "lsppng_dec_probe": (c_int, [c_void_p, c_size_t, POINTER(PngDecInfo)]),

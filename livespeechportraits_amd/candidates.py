@@ -55,56 +55,17 @@ def load_candidates(paths_or_data_root: Union[str, Sequence], device="cuda:0", s
     (colour types 2, 3, 6) and be ``size`` x ``size`` unless ``resize`` is set, with which it is decoded at its own size and resampled exactly as
     a JPEG is; a PNG the decoder refuses raises png.PngError.  Given a data root, candidate j is ``normalized_full_{j}.jpg`` if that exists, else
     ``normalized_full_{j}.png``."""
-    if png:
-        return _load_candidates_mixed(paths_or_data_root, torch.device(device), size, decoder, resize, resizer, progressive, parallel, png_decoder)
-    from .jpeg import JpegDecoder, probe
-    if resize is not None:
-        from .resize import Resizer, check_filter
-        resize = check_filter(resize)
-    src = candidate_paths(paths_or_data_root) if isinstance(paths_or_data_root, (str, os.PathLike)) else list(paths_or_data_root)
-    if len(src) != CANDIDATES:
-        raise ValueError("%d candidate images, demo.py reads %d" % (len(src), CANDIDATES))
-    files = []
-    for s in src:
-        if isinstance(s, (bytes, bytearray, memoryview)):
-            files.append(bytes(s))
-        else:
-            with open(s, "rb") as f:
-                files.append(f.read())
-    other = []                                                  # the files to resample
-    for j, data in enumerate(files):
-        i = probe(data, progressive if decoder is None else getattr(decoder, "progressive", False))
-        if i.status == 0 and (i.width, i.height, i.components) != (size, size, 3):
-            if resize is None or i.components != 3:
-                raise ValueError("candidate %d is %dx%d with %d components, the generator takes %dx%d RGB" % (j, i.width, i.height, i.components, size, size))
-            other.append((j, max(i.width, i.height)))
-    device = torch.device(device)
-    decoder = decoder or JpegDecoder(device, max_side=max([size] + [side for _, side in other]), max_batch=CANDIDATES, progressive=progressive, parallel=parallel)
-    out = torch.empty((3 * CANDIDATES, size, size), dtype=torch.float32, device=device)
-    table = torch.from_numpy(normalisation_table()).to(device)
-    if not other:
-        decoder.decode_into(files, out, 0, table)
-        return out.unsqueeze(0)
-    resizer = resizer or Resizer(device, max_batch=1)
-    for j in range(CANDIDATES):
-        if j not in [k for k, _ in other]:
-            decoder.decode_into([files[j]], out, 3 * j, table)
-    for (j, _), pixels in zip(other, decoder.decode([files[j] for j, _ in other])):
-        resizer.resize_planes(pixels, size, table, out[3 * j:3 * j + 3], resize)
-    return out.unsqueeze(0)
-
-
-def _load_candidates_mixed(paths_or_data_root, device, size, decoder, resize, resizer, progressive, parallel, png_decoder) -> torch.Tensor:
-    """load_candidates(png=True): the same tensor, each file through the decoder of its kind"""
     from . import jpeg as J
-    from . import png as P
+    P = None
+    if png:
+        from . import png as P
     if resize is not None:
         from .resize import Resizer, check_filter
         resize = check_filter(resize)
     if isinstance(paths_or_data_root, (str, os.PathLike)):
-        src = []
-        for path in candidate_paths(paths_or_data_root):
-            src.append(path if os.path.exists(path) else path[:-4] + ".png")
+        src = candidate_paths(paths_or_data_root)
+        if png:
+            src = [path if os.path.exists(path) else path[:-4] + ".png" for path in src]
     else:
         src = list(paths_or_data_root)
     if len(src) != CANDIDATES:
@@ -116,7 +77,7 @@ def _load_candidates_mixed(paths_or_data_root, device, size, decoder, resize, re
         else:
             with open(s, "rb") as f:
                 files.append(f.read())
-    is_png = [data.startswith(P.SIGNATURE) for data in files]
+    is_png = [png and data.startswith(P.SIGNATURE) for data in files]
     other = []                                                  # the files to resample
     for j, data in enumerate(files):
         i = P.probe(data) if is_png[j] else J.probe(data, progressive if decoder is None else getattr(decoder, "progressive", False))
@@ -124,6 +85,7 @@ def _load_candidates_mixed(paths_or_data_root, device, size, decoder, resize, re
             if resize is None or i.components != 3:
                 raise ValueError("candidate %d is %dx%d with %d components, the generator takes %dx%d RGB" % (j, i.width, i.height, i.components, size, size))
             other.append((j, max(i.width, i.height)))
+    device = torch.device(device)
     side = max([size] + [s for _, s in other])
     if not all(is_png):
         decoder = decoder or J.JpegDecoder(device, max_side=side, max_batch=CANDIDATES, progressive=progressive, parallel=parallel)

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/lspjpeg.h"
 #include "../../include/lspjpegdec.h"
@@ -529,20 +530,7 @@ __global__ __launch_bounds__(kStoreThreads) void jpegdec_store(Params p)
         px[1] = clamp255(yy + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
         px[2] = clamp255(yy + ((116130 * cb + 32768) >> 16));
     }
-    if (f.form == LSPJPEG_DEC_FORM_PLANAR_F32) {
-        float *out = reinterpret_cast<float *>(f.out_ptr);
-        const float *table = reinterpret_cast<const float *>(f.table_ptr);
-        for (unsigned c = 0; c < f.ncomp; ++c) out[(size_t)c * f.plane_stride + g] = table[px[c]];
-    } else {
-        unsigned char *out = reinterpret_cast<unsigned char *>(f.out_ptr);
-        if (f.ncomp == 3) {
-            out[(size_t)g * 3 + 0] = (unsigned char)px[0];
-            out[(size_t)g * 3 + 1] = (unsigned char)px[1];
-            out[(size_t)g * 3 + 2] = (unsigned char)px[2];
-        } else {
-            out[g] = (unsigned char)px[0];
-        }
-    }
+    lspout::store_pixel(f.form, f.out_ptr, f.table_ptr, f.plane_stride, f.ncomp, g, px);
 }
 
 void fill_info(const Parsed &f, uint32_t status, uint32_t nseg, uint64_t scan_end, lspjpeg_dec_info *info)
@@ -627,17 +615,10 @@ int64_t lspjpeg_dec_plan_flags(const unsigned char *const *files, const size_t *
     if (!blob) return need;
     if (cap < (size_t)need || reinterpret_cast<uintptr_t>(blob) % 16)
         return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "blob must be 16-byte aligned and hold " + std::to_string(need) + " bytes");
-    std::string keep;                                                          // OutputDesc is the planner's own view of lspjpeg_dec_output
-    keep.resize(outs ? (size_t)n * sizeof(OutputDesc) : 0);
-    OutputDesc *od = outs ? reinterpret_cast<OutputDesc *>(&keep[0]) : nullptr;
-    for (int i = 0; outs && i < n; ++i) {
-        od[i].ptr = reinterpret_cast<uint64_t>(outs[i].ptr);
-        od[i].table = reinterpret_cast<uint64_t>(outs[i].table);
-        od[i].plane_stride = outs[i].plane_stride;
-        od[i].form = (uint32_t)outs[i].form;
-    }
-    const int64_t got = plan(files, lens, od, n, (uint32_t)max_side, blob, flags);
-    if (got == -1) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, "an output's form does not fit its file (RGB8: 3 components, GRAY8: 1, PLANAR_F32: a table and plane_stride >= H * W)");
+    std::vector<OutputDesc> od(outs ? (size_t)n : 0);
+    if (outs) lspout::describe_outputs(outs, n, od.data());
+    const int64_t got = plan(files, lens, outs ? od.data() : nullptr, n, (uint32_t)max_side, blob, flags);
+    if (got == -1) return fail(LSPJPEG_DEC_ERR_INVALID_ARGUMENT, lspout::kOutputRefusal);
     return got;
 }
 

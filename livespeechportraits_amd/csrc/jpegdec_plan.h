@@ -4,6 +4,7 @@
 #ifndef LSPJPEGDEC_PLAN_H
 #define LSPJPEGDEC_PLAN_H
 
+#include "decode_out.h"
 #include "jpegdec_core.h"
 
 namespace lspdec {
@@ -25,13 +26,8 @@ struct BlobHeader {
 };
 static_assert(sizeof(BlobHeader) % 16 == 0, "the areas behind the header stay 16-byte aligned");
 
-inline uint64_t up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
-
-struct OutputDesc {
-    uint64_t ptr, table;
-    int64_t plane_stride;
-    uint32_t form;
-};
+using lspout::OutputDesc;
+using lspout::up;
 
 inline const BlobHeader *header_of(const void *blob)
 {
@@ -225,8 +221,7 @@ inline int64_t plan(const uint8_t *const *files, const size_t *lens, const Outpu
         if (d.width * d.height > h.max_pixels) h.max_pixels = d.width * d.height;
         if (outs && outs[i].ptr) {
             const OutputDesc &o = outs[i];
-            if (o.form > 2 || (o.form == 0 && f.ncomp != 3) || (o.form == 1 && f.ncomp != 1) || (o.form == 2 && (!o.table || o.plane_stride < (int64_t)d.width * d.height)))
-                return -1;
+            if (!lspout::output_fits(o, f.ncomp, (int64_t)d.width * d.height)) return -1;
             d.out_ptr = o.ptr;
             d.table_ptr = o.table;
             d.plane_stride = o.plane_stride;

@@ -8,8 +8,17 @@
 #include <string>
 #include <vector>
 
+#include "../../include/lspjpegdec.h"
 #include "../../include/lsppng.h"
 #include "pngdec_plan.h"
+
+// one ctypes structure serves both planners (_native.py JpegDecOutput), and decode_out.h's forms are both headers' words
+static_assert(sizeof(lsppng_dec_output) == sizeof(lspjpeg_dec_output), "the two output descriptions are one layout");
+static_assert(offsetof(lsppng_dec_output, ptr) == offsetof(lspjpeg_dec_output, ptr) && offsetof(lsppng_dec_output, table) == offsetof(lspjpeg_dec_output, table), "the two output descriptions are one layout");
+static_assert(offsetof(lsppng_dec_output, plane_stride) == offsetof(lspjpeg_dec_output, plane_stride) && offsetof(lsppng_dec_output, form) == offsetof(lspjpeg_dec_output, form), "the two output descriptions are one layout");
+static_assert(offsetof(lsppng_dec_output, reserved) == offsetof(lspjpeg_dec_output, reserved), "the two output descriptions are one layout");
+static_assert(LSPPNG_DEC_FORM_RGB8 == lspout::kFormRgb8 && LSPPNG_DEC_FORM_GRAY8 == lspout::kFormGray8 && LSPPNG_DEC_FORM_PLANAR_F32 == lspout::kFormPlanarF32, "the forms of lsppng.h");
+static_assert(LSPJPEG_DEC_FORM_RGB8 == lspout::kFormRgb8 && LSPJPEG_DEC_FORM_GRAY8 == lspout::kFormGray8 && LSPJPEG_DEC_FORM_PLANAR_F32 == lspout::kFormPlanarF32, "the forms of lspjpegdec.h");
 
 namespace {
 
@@ -154,20 +163,7 @@ __global__ __launch_bounds__(kStoreThreads) void pngdec_store(Params p)
     const unsigned x = g % f.width, y = g / f.width;
     unsigned px[3];
     pixel_of(f, p.ws + f.ws_off + (size_t)y * (1 + f.rowbytes) + 1, x, px);
-    if (f.form == LSPPNG_DEC_FORM_PLANAR_F32) {
-        float *out = reinterpret_cast<float *>(f.out_ptr);
-        const float *table = reinterpret_cast<const float *>(f.table_ptr);
-        for (unsigned c = 0; c < f.ncomp; ++c) out[(size_t)c * f.plane_stride + g] = table[px[c]];
-    } else {
-        unsigned char *out = reinterpret_cast<unsigned char *>(f.out_ptr);
-        if (f.ncomp == 3) {
-            out[(size_t)g * 3 + 0] = (unsigned char)px[0];
-            out[(size_t)g * 3 + 1] = (unsigned char)px[1];
-            out[(size_t)g * 3 + 2] = (unsigned char)px[2];
-        } else {
-            out[g] = (unsigned char)px[0];
-        }
-    }
+    lspout::store_pixel(f.form, f.out_ptr, f.table_ptr, f.plane_stride, f.ncomp, g, px);
 }
 
 void fill_info(const Parsed &f, lsppng_dec_info *info)
@@ -210,15 +206,10 @@ int64_t lsppng_dec_plan(const unsigned char *const *files, const size_t *lens, c
     if (!blob) return need;
     if (cap < (size_t)need || reinterpret_cast<uintptr_t>(blob) % 16)
         return fail(LSPPNG_DEC_ERR_INVALID_ARGUMENT, "blob must be 16-byte aligned and hold " + std::to_string(need) + " bytes");
-    std::vector<OutputDesc> od(outs ? (size_t)n : 0);                          // OutputDesc is the planner's own view of lsppng_dec_output
-    for (int i = 0; outs && i < n; ++i) {
-        od[i].ptr = reinterpret_cast<uint64_t>(outs[i].ptr);
-        od[i].table = reinterpret_cast<uint64_t>(outs[i].table);
-        od[i].plane_stride = outs[i].plane_stride;
-        od[i].form = (uint32_t)outs[i].form;
-    }
+    std::vector<OutputDesc> od(outs ? (size_t)n : 0);
+    if (outs) lspout::describe_outputs(outs, n, od.data());
     const int64_t got = plan(files, lens, outs ? od.data() : nullptr, n, (uint32_t)max_side, blob);
-    if (got == -1) return fail(LSPPNG_DEC_ERR_INVALID_ARGUMENT, "an output's form does not fit its file (RGB8: 3 components, GRAY8: 1, PLANAR_F32: a table and plane_stride >= H * W)");
+    if (got == -1) return fail(LSPPNG_DEC_ERR_INVALID_ARGUMENT, lspout::kOutputRefusal);
     return got;
 }
 

@@ -4,6 +4,7 @@
 #ifndef LSPPNGDEC_PLAN_H
 #define LSPPNGDEC_PLAN_H
 
+#include "decode_out.h"
 #include "pngdec_core.h"
 
 namespace lsppng {
@@ -18,13 +19,8 @@ struct BlobHeader {
 };
 static_assert(sizeof(BlobHeader) % 16 == 0, "the areas behind the header stay 16-byte aligned");
 
-inline uint64_t up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
-
-struct OutputDesc {
-    uint64_t ptr, table;
-    int64_t plane_stride;
-    uint32_t form;
-};
+using lspout::OutputDesc;
+using lspout::up;
 
 inline const BlobHeader *header_of(const void *blob)
 {
@@ -203,8 +199,7 @@ inline int64_t plan(const uint8_t *const *files, const size_t *lens, const Outpu
         if (d.width * d.height > h.max_pixels) h.max_pixels = d.width * d.height;
         if (outs && outs[i].ptr) {
             const OutputDesc &o = outs[i];
-            if (o.form > 2 || (o.form == 0 && f.ncomp != 3) || (o.form == 1 && f.ncomp != 1) || (o.form == 2 && (!o.table || o.plane_stride < (int64_t)d.width * d.height)))
-                return -1;
+            if (!lspout::output_fits(o, f.ncomp, (int64_t)d.width * d.height)) return -1;
             d.out_ptr = o.ptr;
             d.table_ptr = o.table;
             d.plane_stride = o.plane_stride;
@@ -239,7 +234,7 @@ inline uint32_t host_pixels(const void *blob, int i, uint8_t *scanlines, uint8_t
         for (uint32_t x = 0; x < d.width; ++x) {
             uint32_t v[3];
             pixel_of(d, scanlines + (size_t)y * (1 + d.rowbytes) + 1, x, v);
-            for (uint32_t c = 0; c < d.ncomp; ++c) px[((size_t)y * d.width + x) * d.ncomp + c] = (uint8_t)v[c];
+            lspout::store_pixel(d.ncomp == 3 ? lspout::kFormRgb8 : lspout::kFormGray8, reinterpret_cast<uint64_t>(px), 0, 0, d.ncomp, (size_t)y * d.width + x, v);
         }
     return ST_OK;
 }

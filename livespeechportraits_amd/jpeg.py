@@ -30,6 +30,8 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import imagedec
+from .imagedec import FORM_GRAY8, FORM_PLANAR_F32, FORM_RGB8, MAX_SIDE, DecodeError, _aligned, _info  # noqa: F401  (the decoder half's shared names)
 
 
 def _header_of(lib, h) -> bytes:
@@ -258,22 +260,13 @@ def save_images(save_root: str, jpegs: Sequence[bytes], index0: int = 0, prefix:
 # ---- decode -------------------------------------------------------------------------------------------------------------------------
 UNSUPPORTED, CORRUPT, RANGE = 1, 2, 3                          # the per-file status words of include/lspjpegdec.h
 STATUS_NAMES = {0: "OK", UNSUPPORTED: "UNSUPPORTED", CORRUPT: "CORRUPT", RANGE: "RANGE"}
-MAX_SIDE = 8192                                                # LSPJPEG_MAX_SIDE
-FORM_RGB8, FORM_GRAY8, FORM_PLANAR_F32 = 0, 1, 2
 FLAG_PROGRESSIVE = 1                                           # LSPJPEG_DEC_FLAG_PROGRESSIVE
 FLAG_PARALLEL = 2                                              # LSPJPEG_DEC_FLAG_PARALLEL
 
 
-class JpegError(ValueError):
-    """A file of a batch was refused: ``index`` and ``code`` (UNSUPPORTED / CORRUPT / RANGE) of the first one, ``statuses`` of all.
-    The outputs of the refused files were left untouched; the others are complete."""
-
-    def __init__(self, statuses: Sequence[int]):
-        self.statuses = [int(v) for v in statuses]
-        self.index = next(i for i, v in enumerate(self.statuses) if v)
-        self.code = self.statuses[self.index]
-        bad = ["%d: %s" % (i, STATUS_NAMES.get(v, str(v))) for i, v in enumerate(self.statuses) if v]
-        super().__init__("JPEG file %d of the batch is %s (refused files: %s)" % (self.index, STATUS_NAMES.get(self.code, str(self.code)), ", ".join(bad)))
+class JpegError(DecodeError):
+    """``code`` is UNSUPPORTED / CORRUPT / RANGE"""
+    kind, names = "JPEG", STATUS_NAMES
 
 
 class JpegInfo(NamedTuple):
@@ -289,10 +282,6 @@ class JpegInfo(NamedTuple):
     default_tables: int         # bit (2 * id + class): that Huffman table is Annex K's because the file carries none
     scan_offset: int
     scan_bytes: int
-
-
-def _info(i: "N.JpegDecInfo") -> JpegInfo:
-    return JpegInfo(*(int(getattr(i, name)) for name in JpegInfo._fields))
 
 
 class JpegScan(NamedTuple):
@@ -319,56 +308,21 @@ def probe(data: bytes, progressive: bool = False) -> JpegInfo:
     info = N.JpegDecInfo()
     N.check_jpeg_dec(lib.lspjpeg_dec_probe_flags(ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p), len(data), FLAG_PROGRESSIVE if progressive else 0,
                                                  ctypes.byref(info)))
-    return _info(info)
+    return _info(JpegInfo, info)
 
 
-def _aligned(nbytes: int) -> np.ndarray:
-    raw = np.zeros(nbytes + 16, np.uint8)
-    at = (-raw.ctypes.data) % 16
-    return raw[at:at + nbytes]
-
-
-class DecodePlan:
+class DecodePlan(imagedec.DecodePlan):
     """The descriptor block of a batch (``lspjpeg_dec_plan``): per-file tables and output descriptions, the entropy-coded bytes, one
-    entry per restart interval.  Host only.  ``outputs`` is a list of ``(ptr, table_ptr, plane_stride, form)`` per file (device
-    pointers), or None to plan for the host alone.  ``buffer(nbytes)`` supplies the memory (a pinned tensor's numpy view, say).
+    entry per restart interval.  ``file(i).scan_offset`` is the offset of the file's data inside the block.
     ``progressive``: complete progressive files are planned too, scan by scan (``scans(i)``); without it they are UNSUPPORTED.
     ``parallel``: stage 1 of the baseline files decodes inside a restart interval in parallel (``parallel_segment(k)`` says how interval k is
     cut); same statuses, same coefficients, and ``host_coefficients`` then runs that route's code with the lanes as loops."""
+    check = staticmethod(N.check_jpeg_dec)
+    plan_symbol, summary_symbol, file_symbol = "lspjpeg_dec_plan_flags", "lspjpeg_dec_summary_of", "lspjpeg_dec_plan_file"
+    info_struct, summary_struct, info_type = N.JpegDecInfo, N.JpegDecSummary, JpegInfo
 
     def __init__(self, files: Sequence[bytes], max_side: int = MAX_SIDE, outputs=None, buffer=None, progressive: bool = False, parallel: bool = False):
-        self.lib = N.load()
-        flags = (FLAG_PROGRESSIVE if progressive else 0) | (FLAG_PARALLEL if parallel else 0)
-        self.files = [bytes(f) for f in files]
-        n = len(self.files)
-        if n < 1:
-            raise ValueError("no files")
-        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(f), ctypes.c_void_p) for f in self.files])
-        lens = (ctypes.c_size_t * n)(*[len(f) for f in self.files])
-        outs = None
-        if outputs is not None:
-            outs = (N.JpegDecOutput * n)()
-            for o, spec in zip(outs, outputs):
-                if spec is not None:
-                    o.ptr, o.table, o.plane_stride, o.form = spec[0], spec[1] or None, int(spec[2]), int(spec[3])
-        need = N.check_jpeg_dec(self.lib.lspjpeg_dec_plan_flags(ptrs, lens, outs, n, int(max_side), flags, None, 0))
-        self.blob = buffer(need) if buffer is not None else _aligned(need)
-        if self.blob.dtype != np.uint8 or self.blob.size < need or self.blob.ctypes.data % 16:
-            raise ValueError("the plan needs a 16-byte aligned uint8 buffer of %d bytes" % need)
-        self.ptr = ctypes.c_void_p(self.blob.ctypes.data)
-        self.bytes = N.check_jpeg_dec(self.lib.lspjpeg_dec_plan_flags(ptrs, lens, outs, n, int(max_side), flags, self.ptr, self.blob.size))
-        self.summary = N.JpegDecSummary()
-        N.check_jpeg_dec(self.lib.lspjpeg_dec_summary_of(self.ptr, ctypes.byref(self.summary)))
-
-    def file(self, i: int) -> JpegInfo:
-        """what the planner recorded for file i; ``scan_offset`` is the offset of its data inside the block"""
-        info = N.JpegDecInfo()
-        N.check_jpeg_dec(self.lib.lspjpeg_dec_plan_file(self.ptr, int(i), ctypes.byref(info)))
-        return _info(info)
-
-    def statuses(self) -> List[int]:
-        at = int(self.summary.status_offset)
-        return [int(v) for v in self.blob[at:at + 4 * len(self.files)].view(np.uint32)]
+        super().__init__(files, max_side, outputs, buffer, ((FLAG_PROGRESSIVE if progressive else 0) | (FLAG_PARALLEL if parallel else 0), ))
 
     def qtable(self, i: int, c: int) -> np.ndarray:
         out = np.zeros(64, np.uint16)
@@ -417,7 +371,7 @@ class DecodePlan:
         return st, (out if st == 0 else None)
 
 
-class JpegDecoder:
+class JpegDecoder(imagedec.Decoder):
     """Baseline JPEG files -> pixels on the device, equal to Pillow's (include/lspjpegdec.h states the arithmetic and what is refused).
     One call takes files of different sizes and kinds; batches above ``max_batch`` are split.  ``max_side`` bounds width and height
     (larger files are UNSUPPORTED).  The device buffers grow to the largest batch seen and are kept.  ``progressive=True`` also takes complete
@@ -425,102 +379,14 @@ class JpegDecoder:
     ``parallel=True`` decodes inside every restart interval of the baseline files in parallel (one workgroup per interval instead of one lane of
     one wave: the route for files without restart markers, Pillow's default and the encoder's own); same pixels, same statuses, same number of
     launches; off by default."""
+    kind, error, decode_symbol, check = "JPEG", JpegError, "lspjpeg_dec_decode", staticmethod(N.check_jpeg_dec)
 
     def __init__(self, device="cuda:0", max_side: int = 1024, max_batch: int = 64, progressive: bool = False, parallel: bool = False):
-        self.lib = N.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("the JPEG decoder runs on the MI355X only (no CPU path); the reference's host path is cv2.imread / Pillow")
-        if not 1 <= int(max_side) <= MAX_SIDE or int(max_batch) < 1:
-            raise ValueError("max_side must be in 1..%d and max_batch >= 1" % MAX_SIDE)
-        self.max_side, self.max_batch, self.progressive = int(max_side), int(max_batch), bool(progressive)
-        self.parallel = bool(parallel)
-        self._host = torch.empty(0, dtype=torch.uint8)
-        self._dev = torch.empty(0, dtype=torch.uint8, device=self.device)
-        self._ws = torch.empty(0, dtype=torch.uint8, device=self.device)
-        self.last_status: List[int] = []
+        super().__init__(device, max_side, max_batch)
+        self.progressive, self.parallel = bool(progressive), bool(parallel)
 
-    def _buffer(self, nbytes: int) -> np.ndarray:
-        if self._host.numel() < nbytes:
-            self._host = torch.empty(max(nbytes, 2 * self._host.numel()), dtype=torch.uint8, pin_memory=True)
-        return self._host.numpy()
+    def probe(self, data: bytes) -> JpegInfo:
+        return probe(data, self.progressive)
 
-    def _run(self, files: Sequence[bytes], outputs) -> List[int]:
-        """plan, upload, the three stages, and the status words back: the one synchronisation of a call"""
-        plan = DecodePlan(files, self.max_side, outputs, self._buffer, self.progressive, self.parallel)
-        if all(plan.statuses()):
-            return plan.statuses()                             # nothing to decode: the parser refused every file
-        n, ws = int(plan.bytes), int(plan.summary.workspace_bytes)
-        if self._dev.numel() < n:
-            self._dev = torch.empty(max(n, 2 * self._dev.numel()), dtype=torch.uint8, device=self.device)
-        if self._ws.numel() < ws:
-            self._ws = torch.empty(max(ws, 2 * self._ws.numel()), dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            self._dev[:n].copy_(self._host[:n], non_blocking=True)
-            N.check_jpeg_dec(self.lib.lspjpeg_dec_decode(plan.ptr, ctypes.c_void_p(self._dev.data_ptr()), ctypes.c_void_p(self._ws.data_ptr()),
-                                                         self._ws.numel(), ctypes.c_void_p(stream.cuda_stream)))
-            at = int(plan.summary.status_offset)
-            status = self._dev[at:at + 4 * len(files)].cpu()
-        return [int(v) for v in status.numpy().view(np.uint32)]
-
-    def _infos(self, files: Sequence[bytes]) -> List[JpegInfo]:
-        infos = [probe(f, self.progressive) for f in files]
-        for i in infos:
-            if i.status == 0 and max(i.width, i.height) > self.max_side:
-                raise ValueError("a %dx%d file: this decoder was made with max_side=%d" % (i.width, i.height, self.max_side))
-        return infos
-
-    def decode(self, files: Sequence[bytes], strict: bool = True, outs: Optional[Sequence[torch.Tensor]] = None) -> List[Optional[torch.Tensor]]:
-        """One uint8 tensor per file, ``[H, W, 3]`` (colour) or ``[H, W]`` (grey).  A refused file raises ``JpegError``; with
-        ``strict=False`` it gives None in the list instead and ``last_status`` holds the status words.  ``outs`` supplies the tensors
-        (contiguous, right shape); a refused file's tensor is left untouched."""
-        files = [bytes(f) for f in files]
-        infos = self._infos(files)
-        result: List[Optional[torch.Tensor]] = []
-        for k, i in enumerate(infos):
-            shape = (i.height, i.width, 3) if i.components == 3 else (i.height, i.width)
-            if i.status:
-                result.append(None)
-                continue
-            t = outs[k] if outs is not None else torch.empty(shape, dtype=torch.uint8, device=self.device)
-            if tuple(t.shape) != shape or t.dtype != torch.uint8 or t.device != self.device or not t.is_contiguous():
-                raise ValueError("outs[%d] must be a contiguous uint8 tensor of shape %s on %s" % (k, shape, self.device))
-            result.append(t)
-        specs = [None if t is None else (t.data_ptr(), 0, 0, FORM_RGB8 if t.dim() == 3 else FORM_GRAY8) for t in result]
-        self.last_status = []
-        for at in range(0, len(files), self.max_batch):
-            self.last_status += self._run(files[at:at + self.max_batch], specs[at:at + self.max_batch])
-        if any(self.last_status):
-            if strict:
-                raise JpegError(self.last_status)
-            result = [None if s else t for s, t in zip(self.last_status, result)]
-        return result
-
-    def decode_into(self, files: Sequence[bytes], out: torch.Tensor, channel0: int, table: torch.Tensor) -> None:
-        """``table[pixel]`` of every file as float32 planes of ``out`` ([C, H, W], contiguous): file j's channels follow file j - 1's,
-        the first at ``channel0``.  ``table`` is 256 float32 on the device.  Every file must be H x W.  Raises ``JpegError`` when a file
-        is refused; the channels of the others are complete, its own untouched."""
-        files = [bytes(f) for f in files]
-        if not (isinstance(out, torch.Tensor) and out.dim() == 3 and out.dtype == torch.float32 and out.device == self.device and out.is_contiguous()):
-            raise ValueError("out must be a contiguous float32 [C, H, W] tensor on %s" % self.device)
-        if not (isinstance(table, torch.Tensor) and tuple(table.shape) == (256,) and table.dtype == torch.float32 and table.device == self.device
-                and table.is_contiguous()):
-            raise ValueError("table must be 256 contiguous float32 values on %s" % self.device)
-        c, h, w = out.shape
-        specs, ch = [], int(channel0)
-        for k, i in enumerate(self._infos(files)):
-            if i.status:
-                specs.append(None)
-                continue
-            if (i.height, i.width) != (h, w):
-                raise ValueError("file %d is %dx%d, out is %dx%d" % (k, i.width, i.height, w, h))
-            if ch < 0 or ch + i.components > c:
-                raise ValueError("file %d would land at channels %d..%d of %d" % (k, ch, ch + i.components - 1, c))
-            specs.append((out.data_ptr() + 4 * ch * h * w, table.data_ptr(), h * w, FORM_PLANAR_F32))
-            ch += i.components
-        self.last_status = []
-        for at in range(0, len(files), self.max_batch):
-            self.last_status += self._run(files[at:at + self.max_batch], specs[at:at + self.max_batch])
-        if any(self.last_status):
-            raise JpegError(self.last_status)
+    def plan(self, files: Sequence[bytes], outputs) -> DecodePlan:
+        return DecodePlan(files, self.max_side, outputs, self._buffer, self.progressive, self.parallel)

@@ -177,6 +177,24 @@ def test_load_candidates_resamples_photographs_of_any_size(gpu_device):
     assert torch.equal(load_candidates(right, gpu_device, size=64), load_candidates(right, gpu_device, size=64, resize="bicubic"))
 
 
+def test_load_candidates_gives_one_tensor_with_and_without_png(gpu_device):
+    """[plain, plain, to resample, plain] JPEG files: with png=False the plain neighbours now share a decode_into call as they always did with
+    png=True; the two tensors are equal, and the plain files' channels are the table applied to the fixtures' pixels"""
+    import jpeg_decode_cases as K
+    from livespeechportraits_amd.candidates import load_candidates, normalisation_table
+    _, files, pixels = K.fixtures()
+    names = ["candidate_0_64x64_q95", "candidate_1_64x64_q95", K.find("smooth_420_47x33"), "candidate_3_64x64_q95"]
+    batch = [files[n] for n in names]
+    plain = load_candidates(batch, gpu_device, size=64, resize="bicubic", png=False)
+    mixed = load_candidates(batch, gpu_device, size=64, resize="bicubic", png=True)
+    assert plain.shape == (1, 12, 64, 64) and plain.dtype == torch.float32 and torch.equal(plain, mixed)
+    table, got = normalisation_table(), plain.cpu().numpy()
+    for j in (0, 1, 3):
+        assert np.array_equal(got[0, 3 * j:3 * j + 3], table[pixels[names[j]]].transpose(2, 0, 1)), j
+    want = table[_host_resize(pixels[names[2]][None], 64, "bicubic")[0]].transpose(2, 0, 1)
+    assert np.array_equal(got[0, 6:9], want)
+
+
 def _render_problem(tmp_path, gpu_device, frames=5):
     from test_gpu_jpeg import _model
     model, topo, cand = _model(tmp_path, "normal_s64_b3")
