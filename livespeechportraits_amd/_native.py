@@ -1,4 +1,4 @@
-"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h, include/lspjpegdec.h, include/lsppng.h, include/lsplmk.h, include/lspavi.h, include/lsprs.h, include/lspresize.h).
+"""ctypes binding of liblspf2f.so (include/lspf2f.h, include/lspa2h.h, include/lsplle.h, include/lsprnn.h, include/lspraster.h, include/lspmel.h, include/lspunet.h, include/lspjpeg.h, include/lspjpegdec.h, include/lsppng.h, include/lsppngenc.h, include/lsplmk.h, include/lspavi.h, include/lsprs.h, include/lspresize.h).
 
 There is deliberately no fallback: if the shared library is missing or does not
 load, importing the hot path raises -- a GPU box must never silently run
@@ -400,6 +400,28 @@ PNGDEC_SIGNATURES = {
 }
 
 
+class PngEncOptions(ctypes.Structure):
+    """lsppng_enc_options"""
+    _fields_ = [(n, c_int32) for n in ("abi_version", "level", "filter")]
+
+
+PNGENC_ABI_VERSION = 1
+PNGENC_CHUNK = 16384
+PNGENC_HEADER_BYTES = 33
+# every symbol include/lsppngenc.h declares
+PNGENC_SIGNATURES = {
+    "lsppng_enc_create": (c_int, [c_int, c_int, c_int, POINTER(PngEncOptions), POINTER(c_void_p)]),
+    "lsppng_enc_destroy": (c_int, [c_void_p]),
+    "lsppng_enc_last_error": (c_char_p, []),
+    "lsppng_enc_header": (c_int64, [c_void_p, c_void_p, c_size_t]),
+    "lsppng_enc_capacity_bytes": (c_size_t, [c_void_p]),
+    "lsppng_enc_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "lsppng_enc_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "lsppng_enc_host_file": (c_int64, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "lsppng_enc_host_code_lengths": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+}
+
+
 class LmkConfig(Structure):
     """lsplmk_config (include/lsplmk.h)"""
     _fields_ = [(n, c_int32) for n in ("abi_version", "amp_method", "proj_f64", "n_candidates", "max_sessions", "ring_rows", "radius_mouth",
@@ -541,7 +563,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise NativeLibraryError("failed to load %s: %s" % (LIB_PATH, e)) from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JPEGDEC_SIGNATURES.items()) + list(PNGDEC_SIGNATURES.items()) + list(LMK_SIGNATURES.items()) + list(AVI_SIGNATURES.items()) + list(RS_SIGNATURES.items()) + list(RSZ_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(A2H_SIGNATURES.items()) + list(LLE_SIGNATURES.items()) + list(RNN_SIGNATURES.items()) + list(RASTER_SIGNATURES.items()) + list(MEL_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JPEGDEC_SIGNATURES.items()) + list(PNGDEC_SIGNATURES.items()) + list(PNGENC_SIGNATURES.items()) + list(LMK_SIGNATURES.items()) + list(AVI_SIGNATURES.items()) + list(RS_SIGNATURES.items()) + list(RSZ_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -671,6 +693,14 @@ def check_png_dec(rc: int) -> int:
     if rc < 0:
         msg = load().lsppng_dec_last_error()
         raise LsppngError("lsppng_dec error %d: %s" % (rc, msg.decode() if msg else "?"))
+    return rc
+
+
+def check_png_enc(rc: int) -> int:
+    """negative codes of include/lsppngenc.h raise; anything else (0, a size) is handed back"""
+    if rc < 0:
+        msg = load().lsppng_enc_last_error()
+        raise LsppngError("lsppng_enc error %d: %s" % (rc, msg.decode() if msg else "?"))
     return rc
 
 

@@ -129,6 +129,8 @@ class JpegEncoder:
     frame, sizes, workspace) are allocated once, here.  ``quality`` may be a ``JpegOptions``; ``optimize`` / ``restart_rows`` /
     ``restart_blocks`` are Pillow's ``optimize`` / ``restart_marker_rows`` / ``restart_marker_blocks``, and the files Pillow's with them."""
 
+    _encode_symbol, _destroy_symbol, _check_rc = "lspjpeg_encode", "lspjpeg_destroy", staticmethod(N.check_jpeg)      # (png.PngEncoder: its own)
+
     def __init__(self, size: Union[int, Sequence[int]], channels: int = 3, quality: Union[int, JpegOptions] = 75, device="cuda:0", max_batch: int = 8,
                  optimize: bool = False, restart_rows: int = 0, restart_blocks: int = 0, subsampling=None):
         self.lib = N.load()
@@ -148,8 +150,10 @@ class JpegEncoder:
         h = _create(self.lib, self.width, self.height, self.channels, self.options)
         self._h = h
         self.header = _header_of(self.lib, h)
-        self.capacity = int(self.lib.lspjpeg_capacity_bytes(h))
-        self._ws_bytes = int(self.lib.lspjpeg_workspace_bytes(h, self.max_batch))
+        self._allocate(int(self.lib.lspjpeg_capacity_bytes(h)), int(self.lib.lspjpeg_workspace_bytes(h, self.max_batch)))
+
+    def _allocate(self, capacity: int, ws_bytes: int) -> None:
+        self.capacity, self._ws_bytes = capacity, ws_bytes
         self._dst = torch.empty((self.max_batch, self.capacity), dtype=torch.uint8, device=self.device)
         self._sizes = torch.empty(self.max_batch, dtype=torch.int32, device=self.device)
         self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
@@ -159,7 +163,7 @@ class JpegEncoder:
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.lspjpeg_destroy(self._h)
+            getattr(self.lib, self._destroy_symbol)(self._h)
             self._h = None
 
     def __del__(self):
@@ -181,9 +185,17 @@ class JpegEncoder:
         if not 1 <= b <= self.max_batch:
             raise ValueError("batch %d outside 1..max_batch=%d" % (b, self.max_batch))
         # (a format handle reads bytes unless its geometry is that of lspjpeg_create; the library then states the rule itself)
-        if self.options.subsampling is None and frames.data_ptr() % 16:
+        if self._aligned_src() and frames.data_ptr() % 16:
             raise ValueError("frames must start on a 16-byte boundary (a view with a storage offset does not)")
         return b
+
+    def _aligned_src(self) -> bool:
+        return self.options.subsampling is None
+
+    def _launch(self, frames: torch.Tensor, b: int, stream) -> None:
+        self._check_rc(getattr(self.lib, self._encode_symbol)(self._h, ctypes.c_void_p(frames.data_ptr()), b, ctypes.c_void_p(self._dst.data_ptr()),
+                                                              ctypes.c_void_p(self._sizes.data_ptr()), ctypes.c_void_p(self._ws.data_ptr()), self._ws_bytes,
+                                                              ctypes.c_void_p(stream.cuda_stream)))
 
     def submit(self, frames: torch.Tensor) -> None:
         """Enqueue the encode and the copy of the byte counts on the current stream; collect() hands out the files."""
@@ -192,9 +204,7 @@ class JpegEncoder:
         b = self._check(frames)
         stream = torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
-            N.check_jpeg(self.lib.lspjpeg_encode(self._h, ctypes.c_void_p(frames.data_ptr()), b, ctypes.c_void_p(self._dst.data_ptr()),
-                                                 ctypes.c_void_p(self._sizes.data_ptr()), ctypes.c_void_p(self._ws.data_ptr()), self._ws_bytes,
-                                                 ctypes.c_void_p(stream.cuda_stream)))
+            self._launch(frames, b, stream)
             self._sizes_host[:b].copy_(self._sizes[:b], non_blocking=True)
         self._pending = (b, stream)
 
@@ -211,9 +221,7 @@ class JpegEncoder:
         b = self._check(frames)
         stream = torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
-            N.check_jpeg(self.lib.lspjpeg_encode(self._h, ctypes.c_void_p(frames.data_ptr()), b, ctypes.c_void_p(self._dst.data_ptr()),
-                                                 ctypes.c_void_p(self._sizes.data_ptr()), ctypes.c_void_p(self._ws.data_ptr()), self._ws_bytes,
-                                                 ctypes.c_void_p(stream.cuda_stream)))
+            self._launch(frames, b, stream)
         return b
 
     def collect(self) -> List[bytes]:
@@ -225,7 +233,7 @@ class JpegEncoder:
         sizes = [int(v) for v in self._sizes_host[:b].tolist()]
         if any(not 2 <= n <= self.capacity for n in sizes):
             self._pending = None
-            raise RuntimeError("lspjpeg_encode returned byte counts %s outside 2..%d" % (sizes, self.capacity))
+            raise RuntimeError("%s returned byte counts %s outside 2..%d" % (self._encode_symbol, sizes, self.capacity))
         total = sum(sizes)
         if self._host.numel() < total:
             self._host = torch.empty(max(total, 2 * self._host.numel()), dtype=torch.uint8, pin_memory=True)

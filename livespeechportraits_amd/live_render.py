@@ -210,11 +210,12 @@ class LivePortraitPool:
         return sorted(self._lm)
 
     # ---- a tick ------------------------------------------------------------------------------------------------------------------
-    def tick(self, samples=None, finish=(), host: bool = False, jpeg_quality=None):
+    def tick(self, samples=None, finish=(), host: bool = False, jpeg_quality=None, png=None):
         """Push ``samples`` ({session id: float32 16 kHz samples -- or, for a session opened with ``input_rate``, its raw samples: int16 or
         float32, [n] or [n, channels]}) and end the sessions in ``finish`` (closed afterwards).  -> {id:
         (frame_start, frames)} for every session named: the frames that became final, uint8 [k, H, W, 3] on the device (a numpy array with
-        ``host``), or a list of k complete JPEG files (``bytes``) with ``jpeg_quality`` (1..100, or a ``jpeg.JpegOptions``).  Nothing is changed when an argument is refused."""
+        ``host``), or a list of k complete JPEG files (``bytes``) with ``jpeg_quality`` (1..100, or a ``jpeg.JpegOptions``), or of k complete PNG files with ``png`` (True or a ``png.PngOptions``: lossless; not
+        together with ``jpeg_quality``).  Nothing is changed when an argument is refused."""
         torch = self.torch
         pairs = list(samples.items()) if hasattr(samples, "items") else list(samples or ())
         finish = list(finish)
@@ -230,6 +231,13 @@ class LivePortraitPool:
             if sid not in self._lm:
                 self.audio.plan.check(sid)                                         # raises what the audio pool raises for a closed / unknown id
                 raise KeyError("unknown session id %r" % (sid,))
+        if png is not None and png is not False:
+            from .png import PngOptions
+            png = PngOptions.of(png)
+            if jpeg_quality is not None:
+                raise ValueError("png and jpeg_quality: a frame leaves as one file, PNG or JPEG")
+        else:
+            png = None
         if jpeg_quality is not None:
             from .jpeg import JpegOptions
             if isinstance(jpeg_quality, JpegOptions):
@@ -297,8 +305,8 @@ class LivePortraitPool:
                         self._resizer.resize(self._full[:g1 - g0], self.out_size, self.resample, out=frames[g0:g1])
                     self.last_groups.append(owner[g0:g1])
             result = {}
-            if jpeg_quality is not None:                                           # 5. complete files; only the compressed bytes cross PCIe
-                enc = self._encoder(jpeg_quality)
+            if jpeg_quality is not None or png is not None:                        # 5. complete files; only the compressed bytes cross PCIe
+                enc = self._encoder(jpeg_quality) if png is None else self._png_encoder(png)
                 files: List[bytes] = []
                 for g0 in range(0, total, self.max_batch):
                     files += enc.encode(frames[g0:min(total, g0 + self.max_batch)])
@@ -434,4 +442,11 @@ class LivePortraitPool:
         if enc is None:
             from .jpeg import JpegEncoder
             enc = self._jpeg[quality] = JpegEncoder((self.frame_height, self.frame_width), 3, quality, self.device, max_batch=self.max_batch)
+        return enc
+
+    def _png_encoder(self, options):
+        enc = self._jpeg.get(("png", options))                                     # (one table of encoders; a JpegOptions is no such pair)
+        if enc is None:
+            from .png import PngEncoder
+            enc = self._jpeg[("png", options)] = PngEncoder((self.frame_height, self.frame_width), 3, self.device, max_batch=self.max_batch, level=options)
         return enc

@@ -29,7 +29,7 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
                   device: Optional[torch.device] = None,
                   on_frame: Optional[Callable[[int, np.ndarray], None]] = None, streams: int = 2,
                   jpeg_quality=None, video=None, audio=None, video_route: Optional[str] = None,
-                  out_size=None, resample: str = "bicubic") -> List[np.ndarray]:
+                  out_size=None, resample: str = "bicubic", png=None) -> List[np.ndarray]:
     """``feature_maps`` yields [1,H,W] (or [C,H,W]) CPU/GPU tensors as
     ``facedataset.dataset.get_data_test_mode`` does (demo.py:262); ``cand_image`` is demo.py's
     ``img_candidates`` ([1,12,H,W], already on the device).  Returns (or streams to ``on_frame``) uint8 HWC
@@ -57,11 +57,15 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
 
     ``out_size`` (an int or ``(width, height)``, as Pillow's ``size``; None: off) with ``resample`` ("box", "bilinear", "hamming", "bicubic", "lanczos"): every lane
     resamples its batch on its own stream right behind the generator (resize.Resizer, include/lspresize.h: ``Image.resize``, bit for bit) into a buffer it owns; the host
-    copy, the JPEG encoder and the video sink then see ``out_size`` frames, and ``video`` must be a writer of that geometry."""
+    copy, the JPEG encoder and the video sink then see ``out_size`` frames, and ``video`` must be a writer of that geometry.
+
+    ``png`` (True or a ``png.PngOptions``; None: off): as ``jpeg_quality``, but the frames leave as PNG files, losslessly (png.PngEncoder, include/lsppngenc.h): Pillow
+    reads back exactly the frames the call returns without it.  Frames of any ``out_size``.  Not together with ``jpeg_quality`` or ``video``, and not on a host model."""
     device = device or cand_image.device
     frames: List[np.ndarray] = []
     idx = 0
     on_gpu = device.type == "cuda"
+    png = _check_png(png, jpeg_quality, video, on_gpu)
     if out_size is not None:
         out_size = _check_out_size(out_size, resample, on_gpu, video)
     if video is not None and jpeg_quality is None:
@@ -157,10 +161,9 @@ def render_frames(model, feature_maps: Iterable[torch.Tensor], cand_image: torch
                 if lane["sink"] is None:
                     lane["sink"] = VideoSink(video, tuple(u8.shape[1:3]), jpeg_quality, device, batch, audio_dev, audio_host, video_route)
                 lane["sink"].submit(u8, frame_base + idx)       # on the lane's stream, behind the generator
-            elif jpeg_quality is not None:
+            elif jpeg_quality is not None or png is not None:
                 if lane["jpeg"] is None:
-                    from .jpeg import JpegEncoder
-                    lane["jpeg"] = JpegEncoder(tuple(u8.shape[1:3]), 3, jpeg_quality, device, max_batch=batch)
+                    lane["jpeg"] = _frame_encoder(tuple(u8.shape[1:3]), 3, jpeg_quality, png, device, batch)
                 lane["jpeg"].submit(u8)                         # on the lane's stream, behind the generator
             else:
                 if lane["host"] is None:
@@ -188,6 +191,30 @@ def _check_out_size(out_size, resample, on_gpu, video):
     return out_size
 
 
+def _check_png(png, jpeg_quality, video, on_gpu):
+    """``png=`` as a PngOptions, or None; what cannot go with it is refused here, before anything runs"""
+    if png is None or png is False:
+        return None
+    from .png import PngOptions
+    png = PngOptions.of(png)
+    if jpeg_quality is not None:
+        raise ValueError("png and jpeg_quality: a frame leaves as one file, PNG or JPEG")
+    if video is not None:
+        raise ValueError("png and video: the AVI files are Motion-JPEG")
+    if not on_gpu:
+        raise ValueError("png: the PNG encoder runs on the device only, and this model renders on the host")
+    return png
+
+
+def _frame_encoder(size, channels, jpeg_quality, png, device, batch):
+    """the JPEG or the PNG encoder of one lane: the same submit / collect"""
+    if png is not None:
+        from .png import PngEncoder
+        return PngEncoder(size, channels, device, max_batch=batch, level=png)
+    from .jpeg import JpegEncoder
+    return JpegEncoder(size, channels, jpeg_quality, device, max_batch=batch)
+
+
 def _lane_resizer(device, batch, out_size):
     """a Resizer (its plans and workspace) and the uint8 buffer of the resized frames, both owned by one lane"""
     from .resize import Resizer
@@ -206,7 +233,7 @@ def render_frames_from_landmarks(model, landmarks: Iterable, shoulders: Iterable
                                  pad=None, load_size: int = 512, batch: int = 8,
                                  on_frame: Optional[Callable[[int, np.ndarray], None]] = None,
                                  jpeg_quality=None, save_input: bool = False, video=None, audio=None, video_input=None,
-                                 video_route: Optional[str] = None, out_size=None, resample: str = "bicubic") -> List[np.ndarray]:
+                                 video_route: Optional[str] = None, out_size=None, resample: str = "bicubic", png=None) -> List[np.ndarray]:
     """demo.py:260-272 with the edge map drawn on the device: per frame the loop moves the 73 landmarks and the shoulder
     points (~1.5 KB) instead of a host-rasterised 1 MiB feature map.  ``landmarks`` yields [73, 2] arrays (``pred_landmarks[i]``
     of demo.py:262), ``shoulders`` yields [n, 2] arrays (``pred_shoulders[i]``); ``pad`` as ``facedataset.dataset.image_pad``.
@@ -219,9 +246,12 @@ def render_frames_from_landmarks(model, landmarks: Iterable, shoulders: Iterable
     with ``save_input`` a second, grayscale writer for the edge maps may be passed as ``video_input`` (it gets the same ``audio`` if it has an audio stream).
 
     ``out_size`` / ``resample`` as render_frames: the frames are resampled behind the generator and leave (host copy, JPEG, ``video``) at ``out_size``; the edge maps
-    of ``save_input`` / ``video_input`` stay ``load_size``."""
+    of ``save_input`` / ``video_input`` stay ``load_size``.
+
+    ``png`` as render_frames: the frames are handed out as PNG files, and with ``save_input`` the edge maps as grey PNG files, both lossless."""
     from .feature_map import FeatureMapRasteriser
     device = cand_image.device
+    png = _check_png(png, jpeg_quality, video, device.type == "cuda")
     if out_size is not None:
         out_size = _check_out_size(out_size, resample, device.type == "cuda", video)
     resizer = small = None
@@ -283,11 +313,10 @@ def render_frames_from_landmarks(model, landmarks: Iterable, shoulders: Iterable
                     on_frame(idx + k, None)
             idx += b
             continue
-        if jpeg_quality is not None:
-            from .jpeg import JpegEncoder
+        if jpeg_quality is not None or png is not None:
             if enc is None:
-                enc = JpegEncoder(tuple(u8.shape[1:3]), 3, jpeg_quality, device, max_batch=batch)
-                enc_in = JpegEncoder(load_size, 1, jpeg_quality, device, max_batch=batch) if save_input else None
+                enc = _frame_encoder(tuple(u8.shape[1:3]), 3, jpeg_quality, png, device, batch)
+                enc_in = _frame_encoder(load_size, 1, jpeg_quality, png, device, batch) if save_input else None
             enc.submit(u8)
             if save_input:
                 enc_in.submit(edges)
