@@ -110,7 +110,7 @@ int lspf2f_create(const lspf2f_config *cfg, lspf2f_handle **out);
  * before the plan is built.  Keys (default): graph (1) | wino (1), wino4 (flag), winoup (1): the Winograd kernels | wino_ureg (1:
  * U fragments of wino3x3<1> in registers; 0: through LDS; any other value is LSPF2F_ERR_INVALID_ARGUMENT), in_wino_stats (1: InstanceNorm statistics from the wino3x3 epilogue), in_small_regs (1: the one-launch InstanceNorm pass keeps its rows in registers -- one read of the slab instead of three), in_smallm_fused (1: the tiny-M kernel normalises in its own epilogue under InstanceNorm plans), wino_prio (wave priority by K-loop progress: 1 = the workgroup that is behind leads, 2 = the one ahead, 3 = 1 with the older half of the grid kept at level 1 through its last quarter -- on wino3x3<1>'s register form; 4..6 = the same three schemes on every Winograd loop; 0 = off; default 1), wino_pre (1), wino_il (1), wino_rot (1), wino_xcd (-1), igemm_xcd (-1), winoup_nb (0), winoup_target (1024): their tiling / issue-order variants |
  * bandconv (1), bandconv_min_blocks (128), bandconv_min_frames, patch16 (1: the stride-1 convs of the 64x64 / 32x32 levels on the patch-staged kernel), patch16_deep (1: its 64-channel tiles run the deep-ring form conv3x3_patch16d), patchup16 (1: and the sub-pixel up-convs over 32x32 / 64x64 sources on its up-conv form), patch16_min_blocks (192), rowup (1), rowlast (1), rowlast_fused (1: rowlast128 shuffles + applies tanh in its epilogue when only fp32 frames are wanted), rowconv (1): kernels of the 16-bit plans |
- * fullk_split (1), fullk_split_tiles (128), fullk_s2 (0): the full-K kernel's K split | fused_splitk (1), fused_splitk16 (0: the 16-bit plans combine 2..8 K-splits in the launch too), out_wt (1: the Winograd kernels write their output through to memory, sc1 stores; 0: plain stores, left dirty in L2), prefetch (1), smallm_dma (1: the tiny-M kernel stages its input tensor by LDS-DMA, every piece in flight at once; 0: through registers), smallm_kb (128: largest input tensor, in KB, the tiny-M kernel takes; 64 = rounds 2-4) |
+ * fullk_split (1), fullk_split_tiles (128), fullk_s2 (0): the full-K kernel's K split | fused_splitk (1), fused_splitk16 (0: the 16-bit plans combine 2..8 K-splits in the launch too), out_wt (1: the Winograd kernels write their output through to memory, sc1 stores; 0: plain stores, left dirty in L2), prefetch (1), smallm_dma (1: the tiny-M kernel stages its input tensor by LDS-DMA, every piece in flight at once; 0: through registers), smallm_kb (128: largest input tensor, in KB, the tiny-M kernel takes; 64 = rounds 2-4), smallm_static (1: one frame of a 4x4 / 2x2 level runs the tiny-M kernel's static-geometry instance -- input pixels in registers, compile-time tap map, the same bits; 0: the run-time geometry at every shape; any other value is LSPF2F_ERR_INVALID_ARGUMENT) |
  * fullk16 (3: which small levels of a 16-bit plan run on conv3x3_fullk16 -- bit 0 the 4x4 / 2x2 levels, bit 1 the stride-2 / upsampling convs that write 8x8, bit 2 the stride-1 8x8 layers; 0 = none), fullk16_min_frames (2) |
  * in_small_max_hw (1024: InstanceNorm plans take the one-launch statistics route up to this many pixels per frame), all_forms (0; 1: the packed blob carries every weight form whatever the
  * handle's batch range -- tests that look at forms other batches would use), blob_pad_kb (0: empty KB in front of the first layer's weights, placement experiments) |
@@ -232,7 +232,8 @@ int lspf2f_subset_timed(lspf2f_handle *h, const float *feat_dev, const float *ca
  *   c0, c1 % 64 == 0).
  *   tile_m/tile_n/split_k/k_group = 0 selects the planner's choice (k_group = K-tiles fetched
  *   per pipeline step: 1, 2 or 4); scratch is needed when split_k != 1
- *   (size from lspf2f_conv3x3_scratch_bytes).  Special tiles: 1 x 1 = the tiny-M kernel (<= 16 output pixels);
+ *   (size from lspf2f_conv3x3_scratch_bytes).  Special tiles: 1 x 1 = the tiny-M kernel (<= 16 output pixels; cout % 2 == 0 is enough here;
+ *   k_group bit 0: its run-time-geometry form even where a static-geometry instance exists, bit 1: its prefetch wave runs and requests w_packed itself -- tests);
  *   16 x 16 / 32 x 16 = the full-K single-launch kernel of the 16x16 / 8x8 levels (fp32, stride 1, extents 2..16,
  *   c0 in {128, 256, 512}, c1 in {0, c0}, cout % 128 == 0; no scratch).  With k_group == -1 the full-K kernel takes w_packed in
  *   its own tile-blocked layout, [cout/16][source][tap][4 waves][g][64 lanes][4] with lane (li, kq) of block (nt, T, w, g) holding

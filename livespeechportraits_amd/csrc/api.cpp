@@ -52,6 +52,7 @@ struct lspf2f_handle {
     bool prefetch = true;         // prefetch=0: weight-streaming layers do not request the next launch's weights
     bool in_small_regs = true;    // in_small_regs=0: InstanceNorm plans run in_small in its three-pass form (re-reads the slab for the variance and the normalisation)
     bool smallm_dma = true;       // smallm_dma=0: conv3x3_smallm stages its input tensor through registers (the form of rounds 2-4) instead of LDS-DMA pieces
+    bool smallm_static = true;    // smallm_static=0: conv3x3_smallm takes its geometry from its arguments at every shape (the only form until the static-geometry instances)
     bool fuse_splitk = true;      // fused_splitk=0: always combine split-K slabs with a separate launch
     bool counters_clean = false;  // the arrival counters at the head of the workspace were zeroed since it was bound
     int first_direct = 0;         // firstconv=1: vector-ALU first conv; 2: register-staged matrix-core kernel
@@ -178,6 +179,10 @@ int lspf2f_create_tuned(const lspf2f_config *cfg, const char *tune, lspf2f_handl
         else if (k == "prefetch") h->prefetch = v != 0;
         else if (k == "smallm_dma") h->smallm_dma = v != 0;
         else if (k == "smallm_kb") P.smallm_kb = v;
+        else if (k == "smallm_static") {
+            if (v != 0 && v != 1) { delete h; return fail(LSPF2F_ERR_INVALID_ARGUMENT, "tune: smallm_static takes 0 (run-time geometry) or 1 (static-geometry instances)"); }
+            h->smallm_static = v != 0;
+        }
         else if (k == "in_small_regs") h->in_small_regs = v != 0;
         else if (k == "in_smallm_fused") P.in_smallm_fused = v != 0;
         else if (k == "in_small_max_hw") P.in_small_max_hw = v;
@@ -650,6 +655,7 @@ static int run_layer(lspf2f_handle *h, const LayerDesc &l, const float *feat, co
         SmallMParams p = smallm_params(io, l);
         p.in_fused = in_fused ? 1 : 0;
         p.stage_regs = h->smallm_dma ? 0 : 1;
+        p.runtime_geo = h->smallm_static ? 0 : 1;
         if (h->prefetch && P.dtype == 0 && !l.inorm) {
             // the next launch, if it is another weight-streaming layer: its weights (in the form its route reads) are requested from inside this one
             const size_t li = (size_t)(&l - P.layers.data());
@@ -1045,7 +1051,7 @@ static int conv3x3_run(const void *src0, const void *src1, const void *w_packed,
     const TileCode t = decode_tile(tile_m, tile_n, split_k, k_group, dtype);
     if (!t.k8 && ((c0 % ktc) || (c1 % ktc) || c0 <= 0 || c1 < 0 || (c1 > 0 && !src1)))
         return fail(LSPF2F_ERR_UNSUPPORTED, "channel counts must be multiples of 32 (fp32) / 64 (bf16, fp16)");
-    if (cout % 4) return fail(LSPF2F_ERR_UNSUPPORTED, "cout must be a multiple of 4");
+    if (cout % 4 && !(t.route == kRouteSmallM && cout % 2 == 0)) return fail(LSPF2F_ERR_UNSUPPORTED, "cout must be a multiple of 4");     // (the tiny-M kernel: channel pairs)
     if (stride != 1 && stride != 2) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "stride must be 1 or 2");
     if (upsample && stride != 1) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "upsample requires stride 1");
     if ((scale == nullptr) != (shift == nullptr)) return fail(LSPF2F_ERR_INVALID_ARGUMENT, "scale and shift come together");
@@ -1073,6 +1079,10 @@ static int conv3x3_run(const void *src0, const void *src1, const void *w_packed,
     if (t.route == kRouteSmallM || t.planner) {
         SmallMParams q = smallm_params(io, L);
         q.in_fused = in ? 1 : 0;
+        if (t.route == kRouteSmallM && k_group > 0) {           // the forms of the tile 1 x 1 code (include/lspf2f.h)
+            q.runtime_geo = k_group & 1;
+            if ((k_group & 2) && dtype == 0 && !in) { q.pf = w_packed; q.pf_bytes = (unsigned)((size_t)cout * 9 * c0 * sizeof(float)); }
+        }
         if (c1 == 0 && upsample != 2 && smallm_supported(q)) return launched(launch_smallm(q, s), "lspf2f_conv3x3 (tiny-M) launch");
         if (!t.planner) return fail(LSPF2F_ERR_UNSUPPORTED, "tiny-M kernel does not support this shape");
     }

@@ -186,7 +186,11 @@ struct SmallMParams {
     int in_fused;                // InstanceNorm plans: InstanceNorm2d(affine=False, eps=1e-5) over each frame's pixels in the epilogue, then residual / ReLU (instead of an in_small launch)
     int stage_regs;              // 1: stage the input tensor through registers (the form of rounds 2-4: pairs of loads, each pair waited for before the next -- four dependent round trips
                                  // for a 4x4x512 tensor); 0 (default): LDS-DMA pieces, all in flight at once (fp32 storage; 16-bit inputs are widened on the way and keep the registers)
+    int runtime_geo;             // 1: always the instance that takes its geometry from these arguments (tune key smallm_static = 0; A-B runs, tests); 0 (default): one frame of
+                                 // 4x4 -> 4x4, 4x4 -> 2x2 (stride 2), 2x2 -> 2x2 or 2x2 -> 4x4 (up) with Cin 256 | 512, fp32, no fused InstanceNorm, runs its static-geometry
+                                 // instance (input pixels in registers, compile-time tap map; the same bits)
 };
+int smallm_static_geo(const SmallMParams &p);    // the static-geometry instance launch_smallm gives p to (1..4, the order above), 0 = the run-time form
 bool smallm_supported(const SmallMParams &p);
 hipError_t launch_smallm(const SmallMParams &p, hipStream_t s);
 

@@ -1,4 +1,6 @@
 // gfx950: single-launch convolution for the <= 4x4 levels (pure weight streaming).  DESIGN.md section 4.2.
+#include <utility>
+
 #include "device_common.h"
 #include "kernels.h"
 
@@ -23,9 +25,64 @@ namespace lspf2f {
 // INF (InstanceNorm plans, fp32): the workgroup holds EVERY pixel of its channels, i.e. the whole population of InstanceNorm2d(affine=False, eps=1e-5) per (frame, channel) -- the
 // normalisation (+ residual, ReLU; models/networks.py:587-590, 650-675) runs in the epilogue instead of a launch of its own (in_small): two-pass variance in double over the <= 16
 // values of a frame, in pixel order.  Its own instances: the BatchNorm plans' kernel carries none of it.
-template <typename T, int NC, bool PF, int MM, bool INF = false>
+//
+// GEO (fp32 BatchNorm plans, one frame, Cin = 4 C4S in {256, 512}): the four geometries a one-frame plan runs, fixed at compile time -- 1: 4x4 -> 4x4, 2: 4x4 -> 2x2 (stride 2),
+// 3: 2x2 -> 2x2, 4: 2x2 -> 4x4 (nearest x2 in front of the taps); 0 = the geometry of the arguments (every other shape, the 16-bit and the InstanceNorm instances).  The
+// run-time form reads act[pix[m]] once per (tap, m) -- 80 ds_read_b128 per thread at 16 pixels for 16 distinct input pixels, plus the gather table -- because a thread's
+// channel quad c4 = tid % C4S is the same for every one of its taps.  A static instance reads its quad of every input pixel ONCE (16 or 4 reads, all in flight before the
+// first multiply), keeps them in registers and applies the tap -> pixel map as a compile-time table in fully unrolled code: no gather table, no zero pixel, no index into
+// the register array, and a padding tap is no instruction at all (its product was +-0 added to an accumulator that is never -0: the same bits).  A thread's taps are
+// tid / C4S + (256 / C4S) j: one code path per value of tid / C4S (two at C4S = 128, four at 64), chosen by a wave-uniform branch.
+// Every accumulator takes the same products in the same order as in the run-time form, with the contraction that form compiles to (smallm_mac), so the bits are the same.
+constexpr int smallm_geo_hs(int geo) { return geo == 1 || geo == 2 ? 4 : 2; }
+constexpr int smallm_geo_ho(int geo) { return geo == 1 || geo == 4 ? 4 : 2; }
+// source pixel of (tap, output pixel m), or -1 for a padding tap: the formula of the run-time table below with the geometry's constants
+constexpr int smallm_geo_pix(int geo, int tap, int m)
+{
+    const int hs = smallm_geo_hs(geo), ho = smallm_geo_ho(geo), stride = geo == 2 ? 2 : 1, up = geo == 4 ? 1 : 0;
+    const int oy = m / ho, ox = m - oy * ho;
+    const int uy = oy * stride + tap / 3 - 1, ux = ox * stride + tap % 3 - 1;
+    const int hl = up ? 2 * hs : hs;
+    if (uy < 0 || uy >= hl || ux < 0 || ux >= hl) return -1;
+    return (up ? uy >> 1 : uy) * hs + (up ? ux >> 1 : ux);
+}
+
+// One (tap, output pixel) of a static instance: both output channels of the workgroup in one packed chain.  The run-time form's `acc += a.x*w.x + a.y*w.y + a.z*w.z + a.w*w.w`
+// compiles (SLP pairs the two channels, then the products are contracted) to  t = a.x*w.x; t = fma(a.y, w.y, t)  for channel 0 but  t = a.y*w.y; t = fma(a.x, w.x, t)  for
+// channel 1, then fma z, fma w and acc + t for both: restated here product by product, so that it no longer depends on the optimiser.
+// wq[0..3] = (w0.x, w1.y), (w0.y, w1.x), (w0.z, w1.z), (w0.w, w1.w).
+template <int GEO, int TAP, int M, int NPIX, int MM>
+__device__ __forceinline__ void smallm_mac(const float4 (&a)[NPIX], const v2f (&wq)[4], v2f (&acc)[MM])
+{
+#pragma clang fp contract(off)
+    constexpr int px = smallm_geo_pix(GEO, TAP, M);
+    if constexpr (px >= 0) {
+        v2f t = v2f{a[px].x, a[px].y} * wq[0];
+        t = __builtin_elementwise_fma(v2f{a[px].y, a[px].x}, wq[1], t);
+        t = __builtin_elementwise_fma(v2f{a[px].z, a[px].z}, wq[2], t);
+        t = __builtin_elementwise_fma(v2f{a[px].w, a[px].w}, wq[3], t);
+        acc[M] = acc[M] + t;
+    }
+}
+template <int GEO, int TAP, int NPIX, int MM, int... Ms>
+__device__ __forceinline__ void smallm_tap(const float4 (&a)[NPIX], const float4 &w0, const float4 &w1, v2f (&acc)[MM], std::integer_sequence<int, Ms...>)
+{
+    if constexpr (TAP < 9) {
+        const v2f wq[4] = {v2f{w0.x, w1.y}, v2f{w0.y, w1.x}, v2f{w0.z, w1.z}, v2f{w0.w, w1.w}};
+        (smallm_mac<GEO, TAP, Ms>(a, wq, acc), ...);
+    }
+}
+// the taps T0 + TS j of one thread group, j ascending
+template <int GEO, int T0, int TS, int NPIX, int MM, int NJ, int... Js>
+__device__ __forceinline__ void smallm_taps(const float4 (&a)[NPIX], const float4 (&wv)[2][NJ], v2f (&acc)[MM], std::integer_sequence<int, Js...>)
+{
+    (smallm_tap<GEO, T0 + TS * Js>(a, wv[0][Js], wv[1][Js], acc, std::make_integer_sequence<int, MM>()), ...);
+}
+
+template <typename T, int NC, bool PF, int MM, bool INF = false, int GEO = 0, int C4S = 0>
 __global__ __launch_bounds__(PF ? 320 : 256) void conv3x3_smallm(const SmallMParams p)
 {
+    static_assert(GEO == 0 || (sizeof(T) == 4 && NC == 2 && !INF && MM == smallm_geo_ho(GEO) * smallm_geo_ho(GEO) && (C4S == 64 || C4S == 128)), "static geometry: fp32, two channels");
     constexpr int NJ = 5;                                  // K/4 <= 5*256 float4 per weight row (Cin <= 512... 568)
     constexpr int RS = 264;                                // reduction row pitch (floats)
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -37,7 +94,7 @@ __global__ __launch_bounds__(PF ? 320 : 256) void conv3x3_smallm(const SmallMPar
     // activation requests
     asm volatile("" :: "s"(p.src), "s"(p.w), "s"(p.scale), "s"(p.shift), "s"(p.residual), "s"(p.out), "s"(p.B), "s"(p.Hs), "s"(p.Ws), "s"(p.Ho),
                        "s"(p.Wo), "s"(p.Cin), "s"(p.Cout), "s"(p.stride), "s"(p.up), "s"(p.relu), "s"(p.M));
-    const int C4 = p.Cin >> 2, K4 = 9 * C4;
+    const int C4 = GEO ? C4S : p.Cin >> 2, K4 = 9 * C4;
     if (PF && tid >= 256) {
         typedef __attribute__((address_space(3))) float lds_float;
         const unsigned dump = (unsigned)(unsigned long long)(lds_float *)sm + p.pf_dump;
@@ -66,7 +123,7 @@ __global__ __launch_bounds__(PF ? 320 : 256) void conv3x3_smallm(const SmallMPar
         }
     // 2. input tensor -> LDS, (m, tap) -> source pixel table.  The epilogue's operands (folded BatchNorm, residual) of the threads that will write
     //    an output are requested here as well: asked for at the end they were a dependent L2 round trip per launch
-    const int npix = p.B * p.Hs * p.Ws;
+    const int npix = GEO ? smallm_geo_hs(GEO) * smallm_geo_hs(GEO) : p.B * p.Hs * p.Ws;
     const int nin4 = npix * C4;
     const int eo = tid >> 3, em = eo / NC, en = n0 + eo % NC;
     const bool ewrite = tid < MM * NC * 8 && (tid & 7) == 0 && em < p.M && en < p.Cout;
@@ -92,20 +149,22 @@ __global__ __launch_bounds__(PF ? 320 : 256) void conv3x3_smallm(const SmallMPar
     if (!dma)
         for (int i = tid; i < nin4; i += 256)
             reinterpret_cast<float4 *>(act)[i] = load4(static_cast<const T *>(p.src) + (size_t)i * 4);   // LDS copy is fp32
-    for (int i = tid; i < C4; i += 256) reinterpret_cast<float4 *>(act)[nin4 + i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (tid < MM * 9) {
-        const int t = tid / MM, m = tid - t * MM;
-        int pix = npix;                                    // zero pixel: padding taps and rows past M
-        if (m < p.M) {
-            const int hw = p.Ho * p.Wo;
-            const int b = m / hw, r = m - b * hw;
-            const int oy = r / p.Wo, ox = r - oy * p.Wo;
-            const int uy = oy * p.stride + t / 3 - 1, ux = ox * p.stride + t % 3 - 1;
-            const int hl = p.up ? 2 * p.Hs : p.Hs, wl = p.up ? 2 * p.Ws : p.Ws;
-            if (uy >= 0 && uy < hl && ux >= 0 && ux < wl)
-                pix = (b * p.Hs + (p.up ? uy >> 1 : uy)) * p.Ws + (p.up ? ux >> 1 : ux);
+    if constexpr (GEO == 0) {                              // (a static instance has neither a zero pixel nor a table)
+        for (int i = tid; i < C4; i += 256) reinterpret_cast<float4 *>(act)[nin4 + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tid < MM * 9) {
+            const int t = tid / MM, m = tid - t * MM;
+            int pix = npix;                                // zero pixel: padding taps and rows past M
+            if (m < p.M) {
+                const int hw = p.Ho * p.Wo;
+                const int b = m / hw, r = m - b * hw;
+                const int oy = r / p.Wo, ox = r - oy * p.Wo;
+                const int uy = oy * p.stride + t / 3 - 1, ux = ox * p.stride + t % 3 - 1;
+                const int hl = p.up ? 2 * p.Hs : p.Hs, wl = p.up ? 2 * p.Ws : p.Ws;
+                if (uy >= 0 && uy < hl && ux >= 0 && ux < wl)
+                    pix = (b * p.Hs + (p.up ? uy >> 1 : uy)) * p.Ws + (p.up ? ux >> 1 : ux);
+            }
+            pixtab[tid] = pix;
         }
-        pixtab[tid] = pix;
     }
     if (dma) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's copies have landed (its weight rows too: needed next)
     __syncthreads();
@@ -117,28 +176,48 @@ __global__ __launch_bounds__(PF ? 320 : 256) void conv3x3_smallm(const SmallMPar
     for (int m = 0; m < MM; ++m)
 #pragma unroll
         for (int nc = 0; nc < NC; ++nc) acc[m][nc] = 0.f;
+    if constexpr (GEO != 0) {
+        // static geometry: this thread's channel quad of every input pixel, once; then its taps from registers
+        constexpr int NPIX = smallm_geo_hs(GEO) * smallm_geo_hs(GEO), TS = 256 / C4S;
+        float4 a[NPIX];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int k4 = tid + 256 * j;
-        if (k4 >= K4) continue;
-        const int tap = k4 / C4, c4 = k4 - tap * C4;
-        // branch-free: 4 table reads, then 16 independent pixel reads, then the FMAs
-        int pix[MM];
+        for (int q = 0; q < NPIX; ++q) a[q] = reinterpret_cast<const float4 *>(act)[q * C4S + (tid & (C4S - 1))];
+        v2f acc2[MM];
 #pragma unroll
-        for (int q = 0; q < MM / 4; ++q) {
-            const int4 t4 = reinterpret_cast<const int4 *>(pixtab + tap * MM)[q];
-            pix[4 * q] = t4.x; pix[4 * q + 1] = t4.y; pix[4 * q + 2] = t4.z; pix[4 * q + 3] = t4.w;
+        for (int m = 0; m < MM; ++m) acc2[m] = v2f{0.f, 0.f};
+        const std::make_integer_sequence<int, NJ> js;
+        switch (__builtin_amdgcn_readfirstlane(tid / C4S)) {       // a wave lies inside one group (C4S >= 64)
+        case 0: smallm_taps<GEO, 0, TS>(a, wv, acc2, js); break;
+        case 1: smallm_taps<GEO, 1, TS>(a, wv, acc2, js); break;
+        case 2: if constexpr (TS == 4) smallm_taps<GEO, 2, TS>(a, wv, acc2, js); break;
+        default: if constexpr (TS == 4) smallm_taps<GEO, 3, TS>(a, wv, acc2, js); break;
         }
-        float4 a[MM];
 #pragma unroll
-        for (int m = 0; m < MM; ++m) a[m] = reinterpret_cast<const float4 *>(act)[pix[m] * C4 + c4];
+        for (int m = 0; m < MM; ++m) { acc[m][0] = acc2[m].x; acc[m][1] = acc2[m].y; }
+    } else {
 #pragma unroll
-        for (int m = 0; m < MM; ++m)
+        for (int j = 0; j < NJ; ++j) {
+            const int k4 = tid + 256 * j;
+            if (k4 >= K4) continue;
+            const int tap = k4 / C4, c4 = k4 - tap * C4;
+            // branch-free: 4 table reads, then 16 independent pixel reads, then the FMAs
+            int pix[MM];
 #pragma unroll
-            for (int nc = 0; nc < NC; ++nc) {
-                const float4 w4 = wv[nc][j];
-                acc[m][nc] += a[m].x * w4.x + a[m].y * w4.y + a[m].z * w4.z + a[m].w * w4.w;
+            for (int q = 0; q < MM / 4; ++q) {
+                const int4 t4 = reinterpret_cast<const int4 *>(pixtab + tap * MM)[q];
+                pix[4 * q] = t4.x; pix[4 * q + 1] = t4.y; pix[4 * q + 2] = t4.z; pix[4 * q + 3] = t4.w;
             }
+            float4 a[MM];
+#pragma unroll
+            for (int m = 0; m < MM; ++m) a[m] = reinterpret_cast<const float4 *>(act)[pix[m] * C4 + c4];
+#pragma unroll
+            for (int m = 0; m < MM; ++m)
+#pragma unroll
+                for (int nc = 0; nc < NC; ++nc) {
+                    const float4 w4 = wv[nc][j];
+                    acc[m][nc] += a[m].x * w4.x + a[m].y * w4.y + a[m].z * w4.z + a[m].w * w4.w;
+                }
+        }
     }
     __syncthreads();                                       // everyone is done with act
     // 4. block reduction: red[o][tid], then 8 threads per output sum 32 interleaved values each
@@ -191,6 +270,31 @@ bool smallm_supported(const SmallMParams &p)
     return p.M <= 16 && p.Cin % 256 == 0 && 9 * (p.Cin / 4) <= 5 * 256 && act_bytes <= (p.dtype == 0 ? 128 : 64) * 1024 && p.Cout % 2 == 0;      // (fp32: staged by LDS-DMA, one workgroup per CU above 64 KB)
 }
 
+int smallm_static_geo(const SmallMParams &p)
+{
+    if (p.runtime_geo || p.dtype != 0 || p.in_fused || p.B != 1 || p.Hs != p.Ws || p.Ho != p.Wo || p.M != p.Ho * p.Wo) return 0;
+    if (p.Cin != 256 && p.Cin != 512) return 0;               // c4 = tid % C4 needs C4 | 256
+    if (p.Hs == 4 && p.Ho == 4 && p.stride == 1 && !p.up) return 1;
+    if (p.Hs == 4 && p.Ho == 2 && p.stride == 2 && !p.up) return 2;
+    if (p.Hs == 2 && p.Ho == 2 && p.stride == 1 && !p.up) return 3;
+    if (p.Hs == 2 && p.Ho == 4 && p.stride == 1 && p.up) return 4;
+    return 0;
+}
+
+// (a static instance's input is <= 32 KB: within the default dynamic LDS limit, no attribute to set)
+template <int GEO>
+static void launch_smallm_static(const SmallMParams &p, bool pf, unsigned grid, size_t smem, hipStream_t s)
+{
+    constexpr int MM = smallm_geo_ho(GEO) * smallm_geo_ho(GEO);
+    if (p.Cin == 512) {
+        if (pf) hipLaunchKernelGGL((conv3x3_smallm<float, 2, true, MM, false, GEO, 128>), dim3(grid), dim3(320), smem, s, p);
+        else hipLaunchKernelGGL((conv3x3_smallm<float, 2, false, MM, false, GEO, 128>), dim3(grid), dim3(256), smem, s, p);
+    } else {
+        if (pf) hipLaunchKernelGGL((conv3x3_smallm<float, 2, true, MM, false, GEO, 64>), dim3(grid), dim3(320), smem, s, p);
+        else hipLaunchKernelGGL((conv3x3_smallm<float, 2, false, MM, false, GEO, 64>), dim3(grid), dim3(256), smem, s, p);
+    }
+}
+
 hipError_t launch_smallm(const SmallMParams &p, hipStream_t s)
 {
     if (!smallm_supported(p)) return hipErrorInvalidValue;
@@ -226,9 +330,24 @@ hipError_t launch_smallm(const SmallMParams &p, hipStream_t s)
         else hipLaunchKernelGGL((conv3x3_smallm<float, NC, false, 16, true>), dim3(grid), dim3(256), smem, s, p);
         return hipGetLastError();
     }
-    if (p.dtype == 2) hipLaunchKernelGGL((conv3x3_smallm<f16_t, NC, false, 16>), dim3(grid), dim3(256), smem, s, p);
+    const int geo = smallm_static_geo(p);
+    const bool pf = p.dtype == 0 && p.pf != nullptr && p.pf_bytes >= 1024u * grid;
+    if (geo) {
+        SmallMParams q = p;
+        if (pf) {
+            q.pf_dump = (unsigned)((smem + 15) & ~(size_t)15);
+            smem = q.pf_dump + 1024;
+        }
+        switch (geo) {
+        case 1: launch_smallm_static<1>(q, pf, grid, smem, s); break;
+        case 2: launch_smallm_static<2>(q, pf, grid, smem, s); break;
+        case 3: launch_smallm_static<3>(q, pf, grid, smem, s); break;
+        default: launch_smallm_static<4>(q, pf, grid, smem, s); break;
+        }
+    }
+    else if (p.dtype == 2) hipLaunchKernelGGL((conv3x3_smallm<f16_t, NC, false, 16>), dim3(grid), dim3(256), smem, s, p);
     else if (p.dtype == 1) hipLaunchKernelGGL((conv3x3_smallm<bf16_t, NC, false, 16>), dim3(grid), dim3(256), smem, s, p);
-    else if (p.pf != nullptr && p.pf_bytes >= 1024u * grid) {
+    else if (pf) {
         SmallMParams q = p;
         q.pf_dump = (unsigned)((smem + 15) & ~(size_t)15);                    // one 1-KB slot behind everything the working waves use
         smem = q.pf_dump + 1024;
